@@ -42,6 +42,11 @@ and read back through rt_hip_stats), carries the HBM figures next to it, and —
 own instruction stream runs to the vector issue rate (counter figures of profiles/pmc_counters.json, used only when they
 were measured on the kernels of this build).  `cpu_baseline` times the reference-faithful CPU model (oracle/, mt19937
 mode) on a bounded sample of the same workload on this box's host cores.
+
+A plain run measures the headline figure only: set-up, warm-up, the K timed steps, the result line.  `--full` adds every
+other figure of one GPU — `plug_in_call`, `other_frame_mode`, `kernel_only`, `interactive`, `cpu_baseline` — and the
+check of the timed frame against the oracle's digest (`frame_matches_oracle`).  `--dump-outputs DIR` writes the frame the
+timed path delivered in its last step to DIR (see dump_outputs) so that two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -193,6 +198,29 @@ def spread(values: list[float]) -> dict:
     return {"kernel_ms": [round(v, 4) for v in values], "kernel_ms_min": round(min(values), 4), "kernel_ms_max": round(max(values), 4)}
 
 
+DUMP_BYTES_MAX = 64 << 20  # --dump-outputs writes at most this much
+
+
+def dump_outputs(directory, back_buffer) -> None:
+    """--dump-outputs: what the caller of the timed path receives — its back buffer, packed RGBA8888 — as DIR/frame_rgba.npy,
+    float32 [H, W, 4] (R, G, B, A channel values 0..255).  A frame that would take more than DUMP_BYTES_MAX so is written as
+    a fixed sample instead: frame_rgba.npy [n, 4] of the pixels whose row-major indices frame_pixel_index.npy (float64,
+    ascending, a seeded choice that depends on the frame size only) lists."""
+    import numpy as np
+
+    out = Path(directory)
+    out.mkdir(parents=True, exist_ok=True)
+    packed = np.asarray(back_buffer).view(np.uint32)
+    rgba = np.stack([(packed >> shift) & 255 for shift in (24, 16, 8, 0)], axis=-1).astype(np.float32)
+    (out / "frame_pixel_index.npy").unlink(missing_ok=True)
+    if rgba.nbytes > DUMP_BYTES_MAX:
+        count = (DUMP_BYTES_MAX - 4096) // (rgba.itemsize * 4 + 8)  # (room for the two .npy headers)
+        index = np.sort(np.random.default_rng(0).choice(packed.size, size=count, replace=False))
+        np.save(out / "frame_pixel_index.npy", index.astype(np.float64))
+        rgba = rgba.reshape(-1, 4)[index]
+    np.save(out / "frame_rgba.npy", rgba)
+
+
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -209,16 +237,18 @@ def parse_args():
     ap.add_argument("--resident", action="store_true", help="force the LDS-resident kernel (what a scene of 9 to about 1300 primitives gets; scenes of up to 8 take the scalar-register kernel otherwise)")
     ap.add_argument("--tilt", action="store_true", help="single-process only: look down by 8.5 degrees from (0.2, 1.2, 3.0) instead of the scene's axis-aligned camera — the inverse view-projection then carries rounding noise in w's x / y terms (every frame of an interactive session): the general-camera build of the kernels")
     ap.add_argument("--fast", action="store_true", help="RT_HIP_FLAG_FAST: the tolerance-bound arithmetic (raw v_rsq/v_rcp), a second bench line; never the parity contract")
-    ap.add_argument("--cpu-baseline-seconds", type=float, default=15.0, help="0 disables the CPU baseline leg")
+    ap.add_argument("--full", action="store_true", help="one GPU: also the side legs (plug_in_call, other_frame_mode, kernel_only, interactive), the CPU baseline and the timed frame's check against the oracle's digest; a plain run measures the headline figure only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the frame the timed path delivered in its last step to DIR (dump_outputs)")
+    ap.add_argument("--cpu-baseline-seconds", type=float, default=15.0, help="with --full: seconds of the CPU baseline leg; 0 disables it")
     ap.add_argument("--frames-in-flight", type=int, default=1, help="torchrun mode with --gather torch only. 1 (default): one frame at a time, as a blocking render() caller sees it; 2: consecutive frames alternate between two streams (a throughput experiment: reported under `config`, never the default)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="gloo: rehearsal of the N>1 flow on a box with fewer GPUs than ranks (frames staged through host memory)")
     ap.add_argument("--settle-ms", type=float, default=100.0, help="untimed GPU work before the W warm-up steps, so that the clocks have left idle when the timed region starts (an MI355X needs ~35 ms of load: profiles/r02/clock_ramp.txt); 0 disables")
-    ap.add_argument("--no-kernel-only", action="store_true", help="skip the `kernel_only` and `plug_in_call` side legs (profiling runs: every render launch of the process is then a step of the drop-in loop)")
+    ap.add_argument("--no-kernel-only", action="store_true", help="with --full: skip the `kernel_only` and `plug_in_call` side legs (profiling runs: every render launch of the process is then a step of the drop-in loop)")
     ap.add_argument("--gather", default="library", choices=["library", "torch"], help="torchrun mode: `library` (default) = all three forms (see the docstring), `value` from the RCCL-gather form; `torch` = the torch form only")
     ap.add_argument("--library-deadline-s", type=float, default=0.0, help="torchrun mode: seconds the `library` form's child process may take before it is killed and reported as hung (0 = 120); the side forms get 60 s each and the three together at most --forms-budget-s")
     ap.add_argument("--forms-budget-s", type=float, default=300.0, help="torchrun mode: seconds all forms together may take; a side form that no longer fits is skipped (`status: skipped: budget`)")
     ap.add_argument("--form", default=None, choices=["library", "shared_frame", "torch"], help="(internal) this process is the child that runs one form; started by the torchrun-launched process")
-    ap.add_argument("--no-interactive", action="store_true", help="skip the `interactive` side leg (the reference's operating point: ground plane in, camera tilted, frames 16 ms apart)")
+    ap.add_argument("--no-interactive", action="store_true", help="with --full: skip the `interactive` side leg (the reference's operating point: ground plane in, camera tilted, frames 16 ms apart)")
     ap.add_argument("--frame-gap-ms", type=float, default=16.0, help="the `interactive` leg: host-side pause between two blocking calls (a 60 Hz caller that redraws on every frame; the GPU's clocks fall back in such gaps)")
     ap.add_argument("--direct-frame", action="store_true", help="single-process N > 1 only: RT_HIP_MULTI_DIRECT_FRAME — no gather, every GPU stores its pixels straight into the page-locked back buffer")
     ap.add_argument("--locked-frame", action="store_true", help="single-process only: time the opt-in zero-copy mode (RT_HIP_FLAG_PERSISTENT_FRAME: the caller's buffer itself page-locked and mapped) as `value` instead of the default delivery through the module's own frame")
@@ -507,6 +537,8 @@ def single_process_main(args) -> None:
         elapsed = time.perf_counter() - t0
         host_cpu_ms_per_step = (process_cpu_seconds() - cpu0) / args.steps * 1e3
         throttle1 = cgroup_throttle()
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, back_buffer)
         member0 = tracer.member_stats(0) if n_gpus > 1 else stats
         per_rank_kernel_ms = [v / args.steps for v in member_kernel_ms]
         phases = mean_phases(phase_samples)
@@ -521,14 +553,14 @@ def single_process_main(args) -> None:
              "cgroup_throttled": {"periods": throttle1["nr_throttled"] - throttle0["nr_throttled"], "ms": round((throttle1["throttled_usec"] - throttle0["throttled_usec"]) * 1e-3, 3)} if throttle0 and throttle1 else None},
             **{k: phases[k] for k in (*PHASE_KEYS, "bands", "bands_early", "bands_early_min", "helpers") if k in phases},
         )
-        if n_gpus == 1 and not (args.tiled or args.streamed or args.resident or args.fast):
+        if n_gpus == 1 and args.full and not (args.tiled or args.streamed or args.resident or args.fast):
             extras.update(frame_verdict(back_buffer, oracle_frame_digest(args.scene, args.width, args.height, args.spp, args.max_bounces, args.seed, args.tilt)))
         if n_gpus > 1:
             infos = [tracer.comm_info(r) for r in range(n_gpus)]
             extras["rccl"] = {"ranks": infos[0]["ranks"], "devices": [i["device"] for i in infos], "rank_of_member": [i["rank"] for i in infos], "transport": transport, "source": "ncclCommCount / ncclCommUserRank / ncclCommCuDevice per member" if transport == "rccl_gather" else "no communicator (this transport does not use RCCL)"}
             extras["per_rank"] = spread(per_rank_kernel_ms)
 
-        if n_gpus == 1 and not args.no_kernel_only:
+        if n_gpus == 1 and args.full and not args.no_kernel_only:
             # side figure: the call as the plug-in makes it (stats == NULL: nothing but the launch and the wait is enqueued)
             for _ in range(2):
                 tracer.render(pod, args.width, args.height, seed=args.seed, flags=render_flags, out=back_buffer, stats=False)
@@ -565,7 +597,7 @@ def single_process_main(args) -> None:
             torch.cuda.synchronize()
             per_frame = (time.perf_counter() - t1) / args.steps
             kernel_only = {"ms_per_step": round(per_frame * 1e3, 4), "value": round(samples_total / per_frame / 1e6, 1), "unit": "Mrays/s", "what": "scene resident, frame left in HBM, launches back to back (no host frame)"}
-        if n_gpus == 1 and not args.no_kernel_only and not args.no_interactive and not (args.tiled or args.streamed or args.resident or args.fast):
+        if n_gpus == 1 and args.full and not args.no_kernel_only and not args.no_interactive and not (args.tiled or args.streamed or args.resident or args.fast):
             extras["interactive"] = interactive_leg(args, tracer, capi.RT_HIP_FLAG_PERSISTENT_FRAME if args.locked_frame else 0)
         tracers = [tracer]
         parallelism = "1 GPU" if n_gpus == 1 else f"ONE process, {n_gpus} GPUs behind rt_hip_render: row stripes of 8, transport {transport}"
@@ -575,7 +607,7 @@ def single_process_main(args) -> None:
         line["plug_in_call"] = plug_in_call
     if kernel_only:
         line["kernel_only"] = kernel_only
-    if n_gpus == 1 and args.cpu_baseline_seconds > 0:
+    if n_gpus == 1 and args.full and args.cpu_baseline_seconds > 0:
         line["cpu_baseline"] = cpu_baseline(args.scene, args.width, args.height, args.cpu_baseline_seconds)
     print(json.dumps(line), flush=True)
     for t in tracers:
@@ -715,6 +747,8 @@ def form_main(args) -> None:
             settle_collectively(torch_step)
             elapsed, kernels = timed(torch_step, (lambda used: used.stats()["render_ms"]) if in_flight == 1 else (lambda used: float("nan")))
             torch.cuda.synchronize()
+            if args.dump_outputs and rank == 0:  # (the parent moves the dump of the form `value` comes from to --dump-outputs)
+                dump_outputs(result_path + ".outputs", host_frame.numpy())
             transport = "torch.distributed.gather (backend nccl = RCCL)" if args.backend == "nccl" else "torch.distributed.gather over gloo (rehearsal: stripes staged through host memory)"
             return finish("ok", elapsed=elapsed, kernels=kernels, member0=tracers[(args.steps - 1) % in_flight].stats(), transport_text=transport, extras={}, frames_in_flight=in_flight)
 
@@ -785,6 +819,8 @@ def form_main(args) -> None:
 
         settle_collectively(form_step)
         elapsed, kernels = timed(measured_step, lambda s: s["render_ms"] if form != "shared_frame" else tracer.member_stats(rank)["render_ms"])
+        if args.dump_outputs and rank == 0:
+            dump_outputs(result_path + ".outputs", np.asarray(back_buffer))
         phase_samples[:] = phase_samples[-args.steps :]
         infos = [None] * world
         dist.all_gather_object(infos, tracer.comm_info())
@@ -912,6 +948,19 @@ def forms_parent_main(args) -> None:
                 early_line_from = form
 
     exit_code = 3 if any_hung else 0
+    if rank == 0 and args.dump_outputs:
+        import shutil
+
+        chosen = next((f for f in forms if f in results), None)
+        for form in forms:
+            dumped = Path(f"/tmp/rt_bench_{os.getpid()}_{form}.json.outputs")
+            if form == chosen and dumped.is_dir():
+                Path(args.dump_outputs).mkdir(parents=True, exist_ok=True)
+                for name in ("frame_rgba.npy", "frame_pixel_index.npy"):
+                    (Path(args.dump_outputs) / name).unlink(missing_ok=True)
+                for f in dumped.iterdir():
+                    shutil.move(str(f), os.path.join(args.dump_outputs, f.name))
+            shutil.rmtree(dumped, ignore_errors=True)
     if rank == 0:
         # `value` is the form north_star names — the single RCCL gather inside the module — whenever it came up; the others are
         # side keys (`paths`).  Only if it did not: the next form that did, and `paths.library.status` says why.

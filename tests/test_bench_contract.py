@@ -70,6 +70,30 @@ def test_cpu_baseline_counts_the_cpus_the_container_is_granted(tmp_path, monkeyp
         assert leg["cores"] == 2 and "grants the CPU time of 2" in leg["sample"] and leg["kind"] == "port" and leg["value"] > 0
 
 
+def test_dump_outputs_writes_the_frame_or_a_fixed_sample_of_it(tmp_path, monkeypatch):
+    """--dump-outputs: the caller's back buffer as float32 RGBA channels; a frame over the budget as a seeded sample of its
+    pixels, the same pixels on every run."""
+    import numpy as np
+
+    sys.path.insert(0, str(ROOT))
+    import bench
+
+    frame = np.random.default_rng(5).integers(0, 2**32, size=(36, 64), dtype=np.uint32)
+    bench.dump_outputs(tmp_path / "whole", frame)
+    got = np.load(tmp_path / "whole" / "frame_rgba.npy")
+    assert got.dtype == np.float32 and got.shape == (36, 64, 4) and not (tmp_path / "whole" / "frame_pixel_index.npy").exists()
+    assert np.array_equal(got.astype(np.uint32), np.stack([(frame >> s) & 255 for s in (24, 16, 8, 0)], axis=-1))
+    monkeypatch.setattr(bench, "DUMP_BYTES_MAX", 4096 + 24 * 100)
+    for run in ("a", "b"):
+        bench.dump_outputs(tmp_path / run, frame)
+    index = np.load(tmp_path / "a" / "frame_pixel_index.npy")
+    sample = np.load(tmp_path / "a" / "frame_rgba.npy")
+    assert index.dtype == np.float64 and len(index) == 100 and np.all(np.diff(index) > 0) and sample.shape == (100, 4)
+    assert np.array_equal(sample, got.reshape(-1, 4)[index.astype(np.int64)])
+    assert np.array_equal(index, np.load(tmp_path / "b" / "frame_pixel_index.npy")) and np.array_equal(sample, np.load(tmp_path / "b" / "frame_rgba.npy"))
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= bench.DUMP_BYTES_MAX
+
+
 def run_bench(args, launcher=None, timeout=600, expect_rc=0, all_lines=False):
     cmd = (launcher or [sys.executable]) + [str(ROOT / "bench.py")] + args
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
@@ -107,7 +131,7 @@ def test_torchrun_flow_starts_one_child_per_form_and_rank_without_touching_a_gpu
 
 @pytest.mark.gpu
 def test_single_gpu_line_has_the_contract_keys_roofline_and_cpu_baseline():
-    line = run_bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--spp", "32", "--cpu-baseline-seconds", "1"])
+    line = run_bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--spp", "32", "--cpu-baseline-seconds", "1", "--full"])
     assert REQUIRED <= set(line)
     assert line["n_gpus"] == 1 and line["steps"] == 3 and line["warmup"] == 1
     assert line["unit"] == "Mrays/s" and line["higher_is_better"] is True and line["scaling"] == "strong" and line["vs_baseline"] is None
@@ -128,6 +152,26 @@ def test_single_gpu_line_has_the_contract_keys_roofline_and_cpu_baseline():
     assert {"render_ms", "host_issue_ms", "host_wait_ms"} <= set(line["drop_in_breakdown"])
     assert "scenes/basic.toml" in line["data"]
     assert "EPYC" in cpu["sample"] or "CPU" in cpu["sample"] or "Xeon" in cpu["sample"]
+
+
+@pytest.mark.gpu
+def test_a_plain_line_is_the_headline_alone_and_dumps_the_frame_it_timed(tmp_path, tracer):
+    """Without --full the run times the headline and nothing else; --dump-outputs writes the frame its last timed step
+    delivered — the frame the drop-in call gives for this workload."""
+    import numpy as np
+
+    import rt_amd
+    from tests.conftest import unpack
+
+    line = run_bench(["--gpus", "1", "--steps", "4", "--warmup", "1", "--spp", "32", "--dump-outputs", str(tmp_path / "out")])
+    assert REQUIRED <= set(line) and line["steps"] == 4 and line["warmup"] == 1
+    assert line["value"] == pytest.approx(1920 * 1080 * 32 / (line["ms_per_step"] * 1e-3) / 1e6, rel=1e-3)
+    assert not {"cpu_baseline", "kernel_only", "plug_in_call", "other_frame_mode", "interactive", "frame_matches_oracle"} & set(line)
+    dumped = np.load(tmp_path / "out" / "frame_rgba.npy")
+    assert dumped.dtype == np.float32 and dumped.shape == (1080, 1920, 4)
+    pod = rt_amd.Scene.named("basic").set_sampling(32, 10).describe(1920, 1080)
+    want = tracer.render(pod, 1920, 1080, seed=1, stats=False)[0]
+    assert np.array_equal(dumped, unpack(want).astype(np.float32))
 
 
 @pytest.mark.gpu

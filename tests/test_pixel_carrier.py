@@ -51,6 +51,14 @@ def test_helpers_confined_to_fewer_cpus_than_threads_still_deliver_the_frame(tmp
 def test_thread_sanitizer_finds_nothing(tmp_path):
     """The portable build of the carrier (atomic word accesses instead of SSE2 lines) under -fsanitize=thread: the hand-over
     of a job between the caller's thread and the helpers, and every access to the two buffers."""
+    import platform
+
     exe = build(tmp_path, "carrier_tsan", "-fsanitize=thread", "-DRT_HIP_CARRIER_PORTABLE")
-    out = subprocess.run([str(exe), "3", "2"], capture_output=True, text=True, timeout=600, env={"TSAN_OPTIONS": "halt_on_error=1"})
+    # ThreadSanitizer's shadow memory assumes a fixed layout of the address space; a kernel with more bits of mmap randomisation
+    # can map the executable outside it ("unexpected memory mapping").  This one process runs without address randomisation.
+    cmd = [str(exe), "3", "2"]
+    setarch = shutil.which("setarch")
+    if setarch and subprocess.run([setarch, platform.machine(), "-R", "true"], capture_output=True).returncode == 0:
+        cmd = [setarch, platform.machine(), "-R"] + cmd
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env={"TSAN_OPTIONS": "halt_on_error=1"})
     assert out.returncode == 0 and out.stdout.startswith("OK") and "ThreadSanitizer" not in out.stderr, out.stdout + out.stderr[-4000:]

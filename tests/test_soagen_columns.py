@@ -1,34 +1,25 @@
 """SURVEY.md §8 row a-8 against the reference's own container runtime (VERDICT r2 "what's missing" #4).
 
-`vendor/soagen.hpp` of the reference is std-only, so the build container can compile it where it lies under
-/root/reference: tests/native/soagen_columns.cpp builds `soagen::table`s with the column types, alignments and order of
+`vendor/soagen.hpp` of the reference is std-only, so the build compiles it where it lies in the reference tree (Makefile:
+oracle/_ref/soagen_columns, git-ignored): tests/native/soagen_columns.cpp builds `soagen::table`s with the column types, alignments and order of
 the reference's `src/soa.toml` / `src/soa.hpp`, fills them, and hands the pointers the accessors return — 32-byte aligned
 columns, capacity padded to 8-row strides, the padding rows poisoned — to the product's `rt_hip_scene_check` (pointer and
 index check, column fingerprint: pure host code of librt_hip.so) and to the oracle's renderer.  Nothing of the reference
-travels: the GPU box has no /root/reference and skips this test.
+itself is read by the tests: where the build had no reference tree, the program does not exist and both tests skip.
 """
-import shutil
 import subprocess
-from pathlib import Path
 
 import pytest
 
 from tests.conftest import ROOT
 
-SOAGEN = Path("/root/reference/vendor/soagen.hpp")
+SOAGEN_EXE = ROOT / "oracle" / "_ref" / "soagen_columns"
 
 
-@pytest.mark.skipif(not SOAGEN.exists() or shutil.which("g++") is None, reason="needs the reference tree and g++ (build container only)")
-def test_columns_of_a_real_soagen_table_are_read_up_to_size_and_no_further(tmp_path):
-    exe = tmp_path / "soagen_columns"
-    lib_dir, oracle_dir = ROOT / "rt_amd" / "lib", ROOT / "oracle"
-    build = subprocess.run(
-        ["g++", "-std=c++20", "-O1", "-Wall", "-Wextra", f"-I{SOAGEN.parent}", f"-I{ROOT / 'include'}", f"-I{oracle_dir}", str(ROOT / "tests" / "native" / "soagen_columns.cpp"), "-o", str(exe),
-         f"-L{lib_dir}", "-lrt_hip", f"-L{oracle_dir}", "-loracle", f"-Wl,-rpath,{lib_dir}", f"-Wl,-rpath,{oracle_dir}"],
-        capture_output=True, text=True, timeout=300,
-    )
-    assert build.returncode == 0, build.stderr[-3000:]
-    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+def test_columns_of_a_real_soagen_table_are_read_up_to_size_and_no_further():
+    if not SOAGEN_EXE.exists():
+        pytest.skip("oracle/_ref/soagen_columns was not built (the build makes it only where the reference tree is present)")
+    run = subprocess.run([str(SOAGEN_EXE)], capture_output=True, text=True, timeout=120)
     assert run.returncode == 0 and run.stdout.startswith("OK:"), run.stdout + run.stderr
     assert "11 spheres in capacity" in run.stdout  # padding rows existed (and were poisoned)
 

@@ -4,7 +4,7 @@ set -o pipefail
 mkdir -p gpurun_out
 out=gpurun_out/configs.jsonl
 : > $out
-run() { echo "== $*"; timeout -k 10 900 python bench.py --cpu-baseline-seconds 0 "$@" | tail -1 >> $out || exit 1; tail -1 $out | cut -c1-330; }
+run() { echo "== $*"; timeout -k 10 900 python bench.py --full --cpu-baseline-seconds 0 "$@" | tail -1 >> $out || exit 1; tail -1 $out | cut -c1-330; }
 run --steps 20 --warmup 3                                                     # headline: basic 1920x1080x256
 run --steps 20 --warmup 3 --spp 64                                            # config 2: basic 1920x1080x64
 run --steps 10 --warmup 2 --scene dielectric                                  # config 3: dielectric 1920x1080x256
