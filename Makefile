@@ -17,7 +17,7 @@ HIPFLAGS += -fvisibility=hidden
 # basic + plane 2.74 -> 2.62, tilted camera 2.80 -> 2.62 (profiles/r05/codegen_ab.txt).
 HIPFLAGS += -fno-slp-vectorize
 API_UNITS := context scene frame render multi group
-HIP_HDR  := rt_amd/csrc/kernels.hpp rt_amd/csrc/contract.hpp rt_amd/csrc/scan.hpp rt_amd/csrc/frame_group.hpp rt_amd/csrc/delivery.hpp rt_amd/csrc/internal.hpp include/rt_hip.h
+HIP_HDR  := rt_amd/csrc/kernels.hpp rt_amd/csrc/contract.hpp rt_amd/csrc/scan.hpp rt_amd/csrc/bvh_scan.hpp rt_amd/csrc/bvh.hpp rt_amd/csrc/frame_group.hpp rt_amd/csrc/delivery.hpp rt_amd/csrc/internal.hpp include/rt_hip.h
 HOST_SRC := rt_amd/host/host_capi.cpp rt_amd/host/scene.cpp rt_amd/host/toml_subset.cpp
 HOST_HDR := $(wildcard rt_amd/host/*.hpp) rt_amd/host/host_capi.h rt_amd/host/named_colours.inc include/rt_hip.h
 
@@ -27,7 +27,7 @@ all: $(LIBDIR)/librt_hip.so $(LIBDIR)/librt_hip_kat.so $(LIBDIR)/librt_host.so r
 # (-DRT_HIP_FAST_BUILD -ffp-contract=fast: only launch_render_fast comes out of that one)
 FASTFLAGS := $(filter-out -ffp-contract=off,$(HIPFLAGS)) -ffp-contract=fast -DRT_HIP_FAST_BUILD
 OBJDIR   := build/obj$(NAME)
-HIP_OBJS := $(OBJDIR)/kernels.o $(OBJDIR)/kernels_fast.o $(API_UNITS:%=$(OBJDIR)/%.o) $(OBJDIR)/delivery.o
+HIP_OBJS := $(OBJDIR)/kernels.o $(OBJDIR)/kernels_fast.o $(API_UNITS:%=$(OBJDIR)/%.o) $(OBJDIR)/delivery.o $(OBJDIR)/bvh.o
 
 $(OBJDIR)/kernels.o: rt_amd/csrc/kernels.hip $(HIP_HDR)
 	@mkdir -p $(OBJDIR)
@@ -42,6 +42,10 @@ $(OBJDIR)/%.o: rt_amd/csrc/%.hip $(HIP_HDR)
 $(OBJDIR)/delivery.o: rt_amd/csrc/delivery.cpp rt_amd/csrc/delivery.hpp
 	@mkdir -p $(OBJDIR)
 	$(CXX) -std=c++17 -O2 -fPIC -fvisibility=hidden -Wall -Wextra -c $< -o $@
+# the sphere hierarchy's builder (RT_HIP_FLAG_BVH): plain C++17, linked into the product and into the test-only library
+$(OBJDIR)/bvh.o: rt_amd/csrc/bvh.cpp rt_amd/csrc/bvh.hpp
+	@mkdir -p $(OBJDIR)
+	$(CXX) -std=c++17 -O2 -fPIC -fvisibility=hidden -Wall -Wextra -c $< -o $@
 
 # the product: exports the C entry points of include/rt_hip.h and nothing else
 $(LIBDIR)/librt_hip.so: $(HIP_OBJS)
@@ -50,8 +54,8 @@ $(LIBDIR)/librt_hip.so: $(HIP_OBJS)
 	python3 tools/kernel_sources_hash.py > $(LIBDIR)/librt_hip.kernels.sha16   # what THIS binary's kernels were compiled from (bench.py, profiles)
 
 # test-only: the known-answer entry points of include/rt_hip_kat.h (never shipped; loads next to librt_hip.so)
-$(LIBDIR)/librt_hip_kat.so: $(OBJDIR)/kat.o $(LIBDIR)/librt_hip.so
-	$(HIPCC) --offload-arch=gfx950 -fPIC -shared -o $@ $(OBJDIR)/kat.o -L$(LIBDIR) -lrt_hip -Wl,-rpath,'$$ORIGIN' -L/opt/rocm/lib -lrccl
+$(LIBDIR)/librt_hip_kat.so: $(OBJDIR)/kat.o $(OBJDIR)/bvh.o $(LIBDIR)/librt_hip.so
+	$(HIPCC) --offload-arch=gfx950 -fPIC -shared -o $@ $(OBJDIR)/kat.o $(OBJDIR)/bvh.o -L$(LIBDIR) -lrt_hip -Wl,-rpath,'$$ORIGIN' -L/opt/rocm/lib -lrccl
 $(OBJDIR)/kat.o: include/rt_hip_kat.h
 
 $(LIBDIR)/librt_host.so: $(HOST_SRC) $(HOST_HDR)

@@ -146,7 +146,7 @@ typedef struct rt_hip_stats
 {
 	uint64_t primary_samples; /* pixels rendered by this rank x samples_per_pixel */
 	uint64_t segments;		  /* calls of trace() that did not return at the bounce limit check, i.e. closest-hit queries */
-	uint64_t sphere_tests;	  /* segments x n_spheres */
+	uint64_t sphere_tests;	  /* segments x n_spheres (also under RT_HIP_FLAG_BVH: the linear scan's count, not the spheres the tree visited) */
 	uint64_t plane_tests;	  /* segments x n_planes */
 	float render_ms;		  /* device time of the render kernel(s), HIP events on the launch stream */
 	float upload_ms;		  /* host wall time of the last scene upload */
@@ -161,7 +161,8 @@ enum
 	RT_HIP_KERNEL_TILED		= 2, /* primitives streamed from the SoA columns through LDS in tiles (large scenes) */
 	RT_HIP_KERNEL_SMALL		= 3, /* <= 8 primitives (>= 1 sphere, <= 3 planes): scene in scalar registers, scan fully unrolled */
 	RT_HIP_KERNEL_PREVIEW	= 4, /* RT_HIP_FLAG_PREVIEW: one primary ray per pixel, N.L shading */
-	RT_HIP_KERNEL_STREAMED	= 5	 /* primitives read from the table in HBM/L2 with wave-uniform scalar loads: no staging, no barriers */
+	RT_HIP_KERNEL_STREAMED	= 5, /* primitives read from the table in HBM/L2 with wave-uniform scalar loads: no staging, no barriers */
+	RT_HIP_KERNEL_BVH		= 6	 /* RT_HIP_FLAG_BVH: a pixel tile per wave, spheres through the bounding volume hierarchy, one traversal per lane */
 };
 
 /* Render flags.  0 = the parity contract: arithmetic bit-identical to oracle/ (see DESIGN.md §3). */
@@ -215,7 +216,18 @@ enum
 	 * lane of the device — half chunks (HISTORY.md §5 "Half-chunk items"): the launch code decides by the size of the launch, and the frame is
 	 * the same bit for bit either way.  These two take the decision away from it (tests; never both). */
 	RT_HIP_FLAG_FORCE_HALF_CHUNKS = 1u << 8,
-	RT_HIP_FLAG_FORCE_WHOLE_CHUNKS = 1u << 9
+	RT_HIP_FLAG_FORCE_WHOLE_CHUNKS = 1u << 9,
+	/* OPT-IN: trace the spheres through a bounding volume hierarchy (binned-SAH binary tree, leaves of up to four spheres;
+	 * planes keep their linear scan) instead of testing every sphere on every path segment: O(log n) per query instead of
+	 * O(n), for scenes of thousands of spheres and more.  The PROMISE: the same frame, bit for bit, and the same `segments`
+	 * as without the flag — every sphere the tree reaches is tested with the linear scan's arithmetic, ties go to the lower
+	 * index, and no sphere is culled whose computed distance could win.  The tree is built on the host at the
+	 * first such frame after the scene's columns changed (counted in `upload_ms`), kept while they stay the same, and freed
+	 * with the context.  kernel_variant reports RT_HIP_KERNEL_BVH.  Refused (RT_HIP_UNSUPPORTED) with RT_HIP_FLAG_FORCE_TILED,
+	 * _FORCE_RESIDENT, _FORCE_STREAMED and RT_HIP_FLAG_FAST; ignored with RT_HIP_FLAG_PREVIEW (one ray per pixel: nothing to
+	 * gain).  Works with RT_HIP_FLAG_SM_MATERIALS and on every kind of context.  A library older than this flag refuses the
+	 * bit with RT_HIP_UNSUPPORTED (unknown flag bits): that is how a caller finds out whether it is there. */
+	RT_HIP_FLAG_BVH = 1u << 10
 };
 
 typedef struct rt_hip_ctx rt_hip_ctx;

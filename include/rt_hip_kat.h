@@ -33,6 +33,33 @@ RT_HIP_API rt_hip_status rt_hip_kat_closest_hit(rt_hip_ctx* ctx,
 									 uint32_t* out_index,
 									 float* out_normal);
 
+/* rt_hip_kat_closest_hit, answered by RT_HIP_FLAG_BVH's traversal (the render kernel's own code: bvh_scan.hpp) through a
+ * hierarchy built for the resident scene as the render path builds it.  Must equal rt_hip_kat_closest_hit bit for bit. */
+RT_HIP_API rt_hip_status rt_hip_kat_closest_hit_bvh(rt_hip_ctx* ctx,
+										 uint32_t n,
+										 const float* origins,
+										 const float* directions,
+										 float* out_distance,
+										 uint32_t* out_kind,
+										 uint32_t* out_index,
+										 float* out_normal);
+
+/* Host only (no context, no GPU): the sphere hierarchy RT_HIP_FLAG_BVH builds for `scene`.  out_counts[5] = { inner nodes,
+ * spheres in the tree, spheres in the always list, depth (inner-node levels of the deepest path), root link }.  Every other
+ * output may be NULL; each is sized for the worst case, n = scene->n_spheres:
+ *   out_nodes   16 floats per node (at most n): box A min xyz, link A (bits), box A max xyz, link B (bits), box B min xyz, 0,
+ *               box B max xyz, 0.  A link is a node index, or 0x80000000 | (count - 1) << 29 | first for a leaf of `count`
+ *               spheres at leaf slots first .. first + count - 1;
+ *   out_order   n: the scene index of each leaf slot;      out_spheres  4n: the (cx, cy, cz, r^2) of each leaf slot;
+ *   out_always  n: scene indices outside the tree;          out_bound    4: centre xyz and radius of the ball around the tree. */
+RT_HIP_API rt_hip_status rt_hip_kat_bvh_build(const rt_hip_scene* scene,
+								   uint32_t out_counts[5],
+								   float* out_nodes,
+								   uint32_t* out_order,
+								   float* out_spheres,
+								   uint32_t* out_always,
+								   float out_bound[4]);
+
 /* out_sqrt[i] = sqrtf(a[i]), out_div[i] = a[i] / b[i] as the device computes them (must be correctly rounded). */
 RT_HIP_API rt_hip_status rt_hip_kat_sqrt_div(rt_hip_ctx* ctx, uint32_t n, const float* a, const float* b, float* out_sqrt, float* out_div);
 

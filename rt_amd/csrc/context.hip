@@ -434,6 +434,7 @@ extern "C" void rt_hip_destroy(rt_hip_ctx* ctx)
 	unpin_frame(ctx); // a context never outlives its page-lock on the caller's memory
 	ctx->delivery.reset(); // (joins the delivery threads, frees the module's own frame)
 	ctx->scene_columns.release();
+	ctx->bvh_block.release();
 	ctx->scene_staging.release();
 	ctx->item_sums.release();
 	ctx->pixel_done.release();

@@ -11,8 +11,10 @@
 #include "../../include/rt_hip_kat.h"
 #include "internal.hpp"
 #include "scan.hpp"
+#include "bvh_scan.hpp"
 
 #include <algorithm>
+#include <vector>
 
 using namespace rt_hip;
 
@@ -82,6 +84,8 @@ namespace
 		}
 	}
 
+	// BVH: the spheres through RT_HIP_FLAG_BVH's traversal (`tree`) instead of the linear scan
+	template <bool BVH>
 	__global__ __launch_bounds__(block_threads) void kat_closest_hit(const device_scene s,
 																	 uint32_t n,
 																	 const float* __restrict__ origins,
@@ -89,7 +93,8 @@ namespace
 																	 float* __restrict__ out_distance,
 																	 uint32_t* __restrict__ out_kind,
 																	 uint32_t* __restrict__ out_index,
-																	 float* __restrict__ out_normal)
+																	 float* __restrict__ out_normal,
+																	 const device_bvh tree) // [BVH] the hierarchy of the scene
 	{
 		__shared__ float4 tile[tile_primitives];
 		const uint32_t i = blockIdx.x * block_threads + threadIdx.x;
@@ -111,15 +116,25 @@ namespace
 			if (alive)
 				scan_lds<false>(planes, o, d, tile, count, first);
 		}
-		for (uint32_t first = 0; first < s.n_spheres; first += tile_primitives)
+		if constexpr (BVH)
 		{
-			const uint32_t count = min(tile_primitives, s.n_spheres - first);
-			__syncthreads();
-			stage_spheres(tile, s, first, count);
-			__syncthreads();
-			if (alive)
-				scan_lds<true>(spheres, o, d, tile, count, first);
+			__shared__ uint32_t stacks[bvh_max_depth * block_threads];
+			if (alive && !bvh_spheres(spheres, o, d, tree, s.primitive_geometry, stacks + threadIdx.x))
+			{
+				spheres = { 0.0f, 0u, false }; // what the render kernel does too: the sequential rule decides
+				scan_lds<true>(spheres, o, d, s.primitive_geometry, s.n_spheres, 0);
+			}
 		}
+		else
+			for (uint32_t first = 0; first < s.n_spheres; first += tile_primitives)
+			{
+				const uint32_t count = min(tile_primitives, s.n_spheres - first);
+				__syncthreads();
+				stage_spheres(tile, s, first, count);
+				__syncthreads();
+				if (alive)
+					scan_lds<true>(spheres, o, d, tile, count, first);
+			}
 		if (alive)
 		{
 			float distance;
@@ -195,7 +210,9 @@ static void launch_kat_random(uint32_t frame_key_a, uint32_t frame_key_b, uint32
 	hipLaunchKernelGGL(kat_random, dim3(1), dim3(64), 0, stream, frame_keys{ frame_key_a, frame_key_b }, pixel, sample, n, d_out);
 }
 
-static void launch_kat_closest_hit(const device_scene& scene,
+static void launch_kat_closest_hit(bool bvh,
+							const device_scene& scene,
+							const device_bvh& tree,
 							uint32_t n,
 							const float* d_origins,
 							const float* d_directions,
@@ -206,7 +223,10 @@ static void launch_kat_closest_hit(const device_scene& scene,
 							hipStream_t stream)
 {
 	const dim3 grid((n + block_threads - 1) / block_threads);
-	hipLaunchKernelGGL(kat_closest_hit, grid, dim3(block_threads), 0, stream, scene, n, d_origins, d_directions, d_distance, d_kind, d_index, d_normal);
+	if (bvh)
+		hipLaunchKernelGGL(kat_closest_hit<true>, grid, dim3(block_threads), 0, stream, scene, n, d_origins, d_directions, d_distance, d_kind, d_index, d_normal, tree);
+	else
+		hipLaunchKernelGGL(kat_closest_hit<false>, grid, dim3(block_threads), 0, stream, scene, n, d_origins, d_directions, d_distance, d_kind, d_index, d_normal, tree);
 }
 
 static void launch_kat_sqrt_div(uint32_t n, const float* d_a, const float* d_b, float* d_sqrt, float* d_div, hipStream_t stream)
@@ -244,20 +264,55 @@ extern "C" rt_hip_status rt_hip_kat_random(rt_hip_ctx* ctx, uint64_t seed, uint3
 	return RT_HIP_OK;
 }
 
-extern "C" rt_hip_status rt_hip_kat_closest_hit(rt_hip_ctx* ctx,
-												uint32_t n,
-												const float* origins,
-												const float* directions,
-												float* out_distance,
-												uint32_t* out_kind,
-												uint32_t* out_index,
-												float* out_normal)
+static rt_hip_status closest_hit(bool bvh,
+								 rt_hip_ctx* ctx,
+								 uint32_t n,
+								 const float* origins,
+								 const float* directions,
+								 float* out_distance,
+								 uint32_t* out_kind,
+								 uint32_t* out_index,
+								 float* out_normal)
 {
+	const char* const name = bvh ? "rt_hip_kat_closest_hit_bvh" : "rt_hip_kat_closest_hit";
 	if (!ctx || !n || !origins || !directions || !out_distance || !out_kind || !out_index || !out_normal)
-		return kat_fail(RT_HIP_INVALID_ARGUMENT, "rt_hip_kat_closest_hit: invalid argument");
+		return kat_fail(RT_HIP_INVALID_ARGUMENT, "%s: invalid argument", name);
 	if (!ctx->have_scene)
-		return kat_fail(RT_HIP_NO_SCENE, "rt_hip_kat_closest_hit: no scene uploaded");
+		return kat_fail(RT_HIP_NO_SCENE, "%s: no scene uploaded", name);
 	RT_HIP_KAT_TRY(hipSetDevice(ctx->device));
+	const device_scene& scene = ctx->scene;
+	device_bvh tree_desc{};
+	scratch tree_block;
+	if (bvh)
+	{
+		// the hierarchy of the resident scene, built as the render path builds it (scene.hip, ensure_bvh): from the table on the device
+		const uint32_t spheres = scene.n_spheres;
+		std::vector<float> geometry(static_cast<size_t>(spheres) * 4);
+		if (spheres)
+			RT_HIP_KAT_TRY(hipMemcpy(geometry.data(), scene.primitive_geometry, static_cast<size_t>(spheres) * sizeof(float4), hipMemcpyDeviceToHost));
+		bvh_host tree;
+		std::string why;
+		if (!build_bvh(geometry.data(), spheres, tree, why))
+			return kat_fail(RT_HIP_UNSUPPORTED, "%s: %s", name, why.c_str());
+		const size_t nodes_bytes = tree.nodes.size() * 4, spheres_bytes = tree.spheres.size() * 4, order_bytes = tree.order.size() * 4, always_bytes = tree.always.size() * 4;
+		const size_t total = nodes_bytes + spheres_bytes + order_bytes + always_bytes + 16;
+		RT_HIP_KAT_TRY(tree_block.reserve(total));
+		unsigned char* const h = tree_block.host.as<unsigned char>();
+		std::memcpy(h, tree.nodes.data(), nodes_bytes);
+		std::memcpy(h + nodes_bytes, tree.spheres.data(), spheres_bytes);
+		std::memcpy(h + nodes_bytes + spheres_bytes, tree.order.data(), order_bytes);
+		std::memcpy(h + nodes_bytes + spheres_bytes + order_bytes, tree.always.data(), always_bytes);
+		RT_HIP_KAT_TRY(hipMemcpy(tree_block.device.ptr, h, total, hipMemcpyHostToDevice));
+		const unsigned char* const d = tree_block.device.as<unsigned char>();
+		tree_desc.nodes = reinterpret_cast<const float4*>(d);
+		tree_desc.spheres = reinterpret_cast<const float4*>(d + nodes_bytes);
+		tree_desc.order = reinterpret_cast<const uint32_t*>(d + nodes_bytes + spheres_bytes);
+		tree_desc.always = reinterpret_cast<const uint32_t*>(d + nodes_bytes + spheres_bytes + order_bytes);
+		tree_desc.root = tree.root;
+		tree_desc.n_tree = static_cast<uint32_t>(tree.order.size());
+		tree_desc.n_always = static_cast<uint32_t>(tree.always.size());
+		tree_desc.cx = tree.centre[0], tree_desc.cy = tree.centre[1], tree_desc.cz = tree.centre[2], tree_desc.radius = tree.radius;
+	}
 	const size_t vec_bytes = static_cast<size_t>(n) * 3 * sizeof(float);
 	const size_t scalar_bytes = static_cast<size_t>(n) * sizeof(float);
 	scratch in, out;
@@ -272,7 +327,7 @@ extern "C" rt_hip_status rt_hip_kat_closest_hit(rt_hip_ctx* ctx,
 	uint32_t* d_kind = reinterpret_cast<uint32_t*>(d_out + scalar_bytes);
 	uint32_t* d_index = reinterpret_cast<uint32_t*>(d_out + 2 * scalar_bytes);
 	float* d_normal = reinterpret_cast<float*>(d_out + 3 * scalar_bytes);
-	launch_kat_closest_hit(ctx->scene, n, reinterpret_cast<const float*>(d_in), reinterpret_cast<const float*>(d_in + vec_bytes), d_distance, d_kind, d_index, d_normal, nullptr);
+	launch_kat_closest_hit(bvh, scene, tree_desc, n, reinterpret_cast<const float*>(d_in), reinterpret_cast<const float*>(d_in + vec_bytes), d_distance, d_kind, d_index, d_normal, nullptr);
 	RT_HIP_KAT_TRY(hipGetLastError());
 	RT_HIP_KAT_TRY(hipMemcpy(out.host.ptr, out.device.ptr, vec_bytes + 3 * scalar_bytes, hipMemcpyDeviceToHost));
 	const unsigned char* const h_out = out.host.as<unsigned char>();
@@ -280,6 +335,78 @@ extern "C" rt_hip_status rt_hip_kat_closest_hit(rt_hip_ctx* ctx,
 	std::memcpy(out_kind, h_out + scalar_bytes, scalar_bytes);
 	std::memcpy(out_index, h_out + 2 * scalar_bytes, scalar_bytes);
 	std::memcpy(out_normal, h_out + 3 * scalar_bytes, vec_bytes);
+	return RT_HIP_OK;
+}
+
+extern "C" rt_hip_status rt_hip_kat_closest_hit(rt_hip_ctx* ctx,
+												uint32_t n,
+												const float* origins,
+												const float* directions,
+												float* out_distance,
+												uint32_t* out_kind,
+												uint32_t* out_index,
+												float* out_normal)
+{
+	return closest_hit(false, ctx, n, origins, directions, out_distance, out_kind, out_index, out_normal);
+}
+
+extern "C" rt_hip_status rt_hip_kat_closest_hit_bvh(rt_hip_ctx* ctx,
+													uint32_t n,
+													const float* origins,
+													const float* directions,
+													float* out_distance,
+													uint32_t* out_kind,
+													uint32_t* out_index,
+													float* out_normal)
+{
+	return closest_hit(true, ctx, n, origins, directions, out_distance, out_kind, out_index, out_normal);
+}
+
+extern "C" rt_hip_status rt_hip_kat_bvh_build(const rt_hip_scene* scene,
+											  uint32_t out_counts[5],
+											  float* out_nodes,
+											  uint32_t* out_order,
+											  float* out_spheres,
+											  uint32_t* out_always,
+											  float out_bound[4])
+{
+	if (!scene || !out_counts)
+		return kat_fail(RT_HIP_INVALID_ARGUMENT, "rt_hip_kat_bvh_build: NULL argument");
+	const uint32_t n = scene->n_spheres;
+	if (n && (!scene->sphere_center_x || !scene->sphere_center_y || !scene->sphere_center_z || !scene->sphere_radius))
+		return kat_fail(RT_HIP_INVALID_ARGUMENT, "rt_hip_kat_bvh_build: NULL sphere column");
+	// the sphere rows of the primitive table as the upload derives them (scene.hip, build_image)
+	std::vector<float> geometry(static_cast<size_t>(n) * 4);
+	for (uint32_t i = 0; i < n; i++)
+	{
+		const float radius = scene->sphere_radius[i];
+		geometry[i * 4 + 0] = scene->sphere_center_x[i];
+		geometry[i * 4 + 1] = scene->sphere_center_y[i];
+		geometry[i * 4 + 2] = scene->sphere_center_z[i];
+		geometry[i * 4 + 3] = radius * radius;
+	}
+	bvh_host tree;
+	std::string why;
+	if (!build_bvh(geometry.data(), n, tree, why))
+		return kat_fail(RT_HIP_UNSUPPORTED, "rt_hip_kat_bvh_build: %s", why.c_str());
+	out_counts[0] = static_cast<uint32_t>(tree.nodes.size() / 16);
+	out_counts[1] = static_cast<uint32_t>(tree.order.size());
+	out_counts[2] = static_cast<uint32_t>(tree.always.size());
+	out_counts[3] = tree.depth;
+	out_counts[4] = tree.root;
+	if (out_nodes)
+		std::memcpy(out_nodes, tree.nodes.data(), tree.nodes.size() * 4);
+	if (out_order)
+		std::memcpy(out_order, tree.order.data(), tree.order.size() * 4);
+	if (out_spheres)
+		std::memcpy(out_spheres, tree.spheres.data(), tree.spheres.size() * 4);
+	if (out_always)
+		std::memcpy(out_always, tree.always.data(), tree.always.size() * 4);
+	if (out_bound)
+	{
+		std::memcpy(out_bound, tree.centre, sizeof(tree.centre));
+		out_bound[3] = tree.radius;
+	}
 	return RT_HIP_OK;
 }
 

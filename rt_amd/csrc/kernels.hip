@@ -40,6 +40,7 @@
 #include "kernels.hpp"
 #include "contract.hpp"
 #include "scan.hpp"
+#include "bvh_scan.hpp"
 
 #ifdef RT_HIP_FAST_BUILD
 #define render_queue render_queue_fast
@@ -70,6 +71,11 @@
 #ifndef RT_HIP_WAVES_DENSE
 #define RT_HIP_WAVES_DENSE 6
 #endif
+// the BVH kernel (NS == -4, RT_HIP_FLAG_BVH): a pixel tile per wave with a traversal stack of bvh_max_depth words per lane in LDS
+// (24 KiB per workgroup)
+#ifndef RT_HIP_WAVES_BVH
+#define RT_HIP_WAVES_BVH 5
+#endif
 #ifndef RT_HIP_PERSISTENT_WAVES_CAP
 #define RT_HIP_PERSISTENT_WAVES_CAP 5 // workgroups per CU of the persistent (big-scene) launches: see launch_queue_sm
 #endif
@@ -90,6 +96,8 @@
 
 namespace rt_hip
 {
+	static_assert(bvh_stack_float4s * 4u == bvh_max_depth * block_threads, "the BVH kernel's LDS stacks hold bvh_max_depth words per thread");
+
 	namespace
 	{
 		// The streamed kernel's sphere scan: the (center, radius^2) table is read from HBM/L2 with wave-uniform scalar loads,
@@ -283,7 +291,9 @@ namespace rt_hip
 		// runs its own queue, but the workgroup advances in lock step, one path segment per trip, with barriers around
 		// each tile, until all four waves are done.  NS == -2: `streamed` kernel — the resident loop reading the primitive
 		// table from HBM/L2 with wave-uniform scalar loads.  NS == -3: the same without the cooperative scan of sparse waves, for frames
-		// that fill the device (6 waves per SIMD; RT_HIP_WAVES_DENSE above).
+		// that fill the device (6 waves per SIMD; RT_HIP_WAVES_DENSE above).  NS == -4: the BVH kernel (RT_HIP_FLAG_BVH) — the resident
+		// kernel's tile queue, planes scanned from the table in memory, spheres through the hierarchy, one traversal per lane
+		// (bvh_scan.hpp; the lanes of a wave hold unrelated rays, and a wave-wide walk would visit the union of their paths).
 		// SM: scatter table of sm_ray_tracer (RT_HIP_FLAG_SM_MATERIALS) instead of mg_ray_tracer's.
 		// launch bounds: compiled for 7 waves per SIMD.  That raises the compiler's budgets from 64 to 72 vector and from 72
 		// to 88 scalar registers.  With 5..8 spheres in SGPRs and in the resident kernel 64 VGPRs mean scratch
@@ -424,7 +434,7 @@ namespace rt_hip
 		// LDS-resident kernel (+35 % on basic.toml); now they keep the scalar-register kernel, in a build of it that carries
 		// the 18 scalars of the general form INSTEAD of the 18 of the affine one (both would not fit its scalar registers).
 		template <int NS, bool SM, bool HALF = false, int NP = 0, bool GC = false>
-		__global__ __launch_bounds__(block_threads, NS == -3 ? RT_HIP_WAVES_DENSE : (NS < 0 ? 5 : (NS == 0 ? RT_HIP_WAVES_RESIDENT : (NS >= 6 && NS + NP >= 7 ? RT_HIP_WAVES_MANY : RT_HIP_WAVES_FEW)))) void render_queue(const frame_params p,
+		__global__ __launch_bounds__(block_threads, NS == -4 ? RT_HIP_WAVES_BVH : NS == -3 ? RT_HIP_WAVES_DENSE : (NS < 0 ? 5 : (NS == 0 ? RT_HIP_WAVES_RESIDENT : (NS >= 6 && NS + NP >= 7 ? RT_HIP_WAVES_MANY : RT_HIP_WAVES_FEW)))) void render_queue(const frame_params p,
 																	  const queue_params q,
 																	  const small_scene small,
 																	  const device_scene s,
@@ -432,7 +442,8 @@ namespace rt_hip
 																	  uint32_t* __restrict__ out_rgba,
 																	  float* __restrict__ out_rgb,
 																	  device_counters* __restrict__ counters,
-																	  unsigned long long* item_sums, // [NS < 0] chunk sums in transit: 16 bytes per item
+																	  unsigned long long* item_sums, // [NS < 0] chunk sums in transit: 16 bytes per item; [NS == -4] the device_bvh
+																									 // descriptor (rolling_buffers::bvh)
 																	  uint32_t* pixel_done)			 // [NS < 0] items arrived per pixel (zeroed in front of every launch)
 		{
 			extern __shared__ float4 lds[];
@@ -446,7 +457,8 @@ namespace rt_hip
 			constexpr bool RESIDENT_SCALAR_SCAN = NS == 0 && NP == 1;
 			const bool spheres_in_lds = RESIDENT && !RESIDENT_SCALAR_SCAN;
 			const uint32_t lds_spheres = spheres_in_lds ? s.n_spheres : 0u;
-			const uint32_t table_float4s = NS > 0 ? small_table_float4s : (RESIDENT ? lds_spheres + s.n_planes : (NS == -1 ? tile_primitives : 0u));
+			constexpr bool BVH = NS == -4;
+			const uint32_t table_float4s = NS > 0 ? small_table_float4s : (RESIDENT ? lds_spheres + s.n_planes : (NS == -1 ? tile_primitives : (BVH ? bvh_stack_float4s : 0u)));
 			if (NS > 0)
 			{
 				if (threadIdx.x == 0)
@@ -471,7 +483,11 @@ namespace rt_hip
 #ifdef RT_HIP_REGION_COUNTERS
 			uint32_t region_runs[device_counters::regions] = {}, region_lanes[device_counters::regions] = {};
 #endif
-			constexpr bool ROLLING = NS < 0;
+			constexpr bool ROLLING = NS < 0 && !BVH;
+			// [BVH] the hierarchy, read once into scalar registers (its pointers and counts are the same for the whole launch)
+			device_bvh bvh{};
+			if constexpr (BVH)
+				bvh = *reinterpret_cast<const device_bvh*>(item_sums);
 			// the camera form a scalar-register kernel is built for: the pinhole form, or (GC) the eye form.  A matrix without a
 			// finite eye (an orthographic frustum: nothing rt's camera can produce) takes the LDS-resident kernel, which carries all
 			// three forms — together with seven spheres their scalars do not fit the scalar registers, and hipcc then reloads the
@@ -921,7 +937,24 @@ namespace rt_hip
 						// resident: the LDS copy; streamed: the table in HBM/L2 itself, read with wave-uniform (scalar) loads
 						const float4* const primitives = RESIDENT ? lds : geometry;
 						scan_lds<false>(planes, st.origin, st.dir, RESIDENT ? lds + lds_spheres : geometry + s.n_spheres, s.n_planes, 0);
-						if (NS == -2 || NS == -3)
+						if (BVH)
+						{
+							// the lane's traversal stack: word k at lds[k * block_threads + threadIdx.x] (consecutive lanes, consecutive banks)
+							if (!bvh_spheres(spheres, st.origin, st.dir, bvh, geometry, reinterpret_cast<uint32_t*>(lds) + threadIdx.x))
+							{
+								spheres = { 0.0f, 0u, false }; // a degenerate ray or a non-finite distance: the sequential rule decides
+								scan_streamed_spheres(spheres, st.origin, st.dir, geometry, s.n_spheres);
+							}
+#ifdef RT_HIP_BVH_CHECK
+							candidate linear = { 0.0f, 0u, false };
+							scan_streamed_spheres(linear, st.origin, st.dir, geometry, s.n_spheres);
+							const bool same = linear.have == spheres.have && (!linear.have || (__float_as_uint(linear.t) == __float_as_uint(spheres.t) && linear.index == spheres.index));
+							atomicAdd(&counters->bvh_checked, 1ull);
+							if (!same)
+								atomicAdd(&counters->bvh_disagreements, 1ull);
+#endif
+						}
+						else if (NS == -2 || NS == -3)
 						{
 							if (scanned_together)
 								spheres = together;
@@ -1519,7 +1552,7 @@ namespace rt_hip
 							 launch_cache& cache,
 							 hipStream_t stream)
 		{
-			if (NS < 0)
+			if (NS < 0 && NS != -4)
 			{
 				// persistent launch: exactly what the device keeps resident (surplus workgroups would only find the queue dry).
 				// The answer is remembered per context (= per device and host thread of use), per kernel and LDS size.
@@ -1552,15 +1585,17 @@ namespace rt_hip
 				}
 				grid = dim3(std::min(grid.x, compute_units * static_cast<uint32_t>(known.per_cu)));
 			}
+			// (the BVH kernel takes its hierarchy's descriptor in the item_sums argument's place)
+			unsigned long long* const item_sums = NS == -4 ? reinterpret_cast<unsigned long long*>(const_cast<device_bvh*>(rolling.bvh)) : rolling.item_sums;
 			if constexpr (!SM) // (the sm table keeps whole chunks: one set of kernels fewer to build)
 			{
 				if (queue.halves)
 				{
-					hipLaunchKernelGGL((render_queue<NS, SM, true, NP, GC>), grid, dim3(block_threads), lds_bytes, stream, frame, queue, small, scene, scene.primitive_geometry, d_rgba8, d_rgb_f32, d_counters, rolling.item_sums, rolling.pixel_done);
+					hipLaunchKernelGGL((render_queue<NS, SM, true, NP, GC>), grid, dim3(block_threads), lds_bytes, stream, frame, queue, small, scene, scene.primitive_geometry, d_rgba8, d_rgb_f32, d_counters, item_sums, rolling.pixel_done);
 					return;
 				}
 			}
-			hipLaunchKernelGGL((render_queue<NS, SM, false, NP, GC>), grid, dim3(block_threads), lds_bytes, stream, frame, queue, small, scene, scene.primitive_geometry, d_rgba8, d_rgb_f32, d_counters, rolling.item_sums, rolling.pixel_done);
+			hipLaunchKernelGGL((render_queue<NS, SM, false, NP, GC>), grid, dim3(block_threads), lds_bytes, stream, frame, queue, small, scene, scene.primitive_geometry, d_rgba8, d_rgb_f32, d_counters, item_sums, rolling.pixel_done);
 		}
 
 		template <int NS, int NP = 0, bool GC = false>
@@ -1592,6 +1627,8 @@ namespace rt_hip
 	uint32_t choose_kernel(const device_scene& scene, uint32_t flags, uint32_t samples_per_pixel, bool perspective, uint64_t pixels)
 	{
 		const uint32_t primitives = scene.n_spheres + scene.n_planes;
+		if (flags & RT_HIP_FLAG_BVH) // (render.hip refuses it with the FORCE_ flags, and builds the hierarchy first)
+			return RT_HIP_KERNEL_BVH;
 		if (flags & RT_HIP_FLAG_FORCE_STREAMED)
 			return RT_HIP_KERNEL_STREAMED;
 		if (flags & RT_HIP_FLAG_FORCE_TILED)
@@ -1827,6 +1864,13 @@ namespace rt_hip
 #undef RT_HIP_LAUNCH_SMALL
 			return variant;
 		}
+#ifndef RT_HIP_FAST_BUILD // (the API refuses RT_HIP_FLAG_FAST together with RT_HIP_FLAG_BVH)
+		if (variant == RT_HIP_KERNEL_BVH)
+		{
+			launch_queue<-4>(sm, frame, queue, small, scene, grid, bvh_stack_float4s * sizeof(float4) + slot_bytes, d_rgba8, d_rgb_f32, d_counters, rolling, compute_units, cache, stream);
+			return variant;
+		}
+#endif
 		if (variant == RT_HIP_KERNEL_RESIDENT)
 		{
 			const size_t lds_bytes = static_cast<size_t>((scene.n_spheres < resident_scalar_scan_from ? scene.n_spheres : 0u) + scene.n_planes) * sizeof(float4) + slot_bytes;

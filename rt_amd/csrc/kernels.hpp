@@ -14,6 +14,19 @@ namespace rt_hip
 	//     shading inputs of the primitive's material — (albedo.rgb * reflectivity, roughness) and a metal flag
 	//     (mg_ray_tracer.cpp:115,131,142-152) — so that a hit needs one indexed lookup instead of two dependent ones;
 	//   * the per-material shading table for kernels that only know the winning primitive's material index.
+	// RT_HIP_FLAG_BVH: the sphere hierarchy of the resident scene (bvh.hpp), built on the host at the first such frame of a scene.
+	// It lives in device memory (scene.hip, ensure_bvh) and reaches the BVH kernel through a pointer: device_scene, the other
+	// kernels' argument, stays as it is.
+	struct device_bvh
+	{
+		const float4* nodes;	// 4 per inner node
+		const float4* spheres;	// (c, r^2) of the tree's spheres in leaf order
+		const uint32_t* order;	// their indices in the scene
+		const uint32_t* always; // indices of the spheres outside the tree (scanned linearly by every query)
+		uint32_t root, n_tree, n_always;
+		float cx, cy, cz, radius; // a ball around every tree sphere: the cull margin's C and R (bvh_scan.hpp)
+	};
+
 	struct device_scene
 	{
 		uint32_t n_spheres, n_planes, n_materials;
@@ -166,6 +179,9 @@ namespace rt_hip
 	{
 		unsigned long long* item_sums = nullptr;
 		uint32_t* pixel_done = nullptr;
+		// RT_HIP_FLAG_BVH: the hierarchy's descriptor in device memory.  The BVH kernel keeps no sums in HBM; it is handed this in
+		// the item_sums argument's place (render_queue), so that no kernel's argument block changes.
+		const device_bvh* bvh = nullptr;
 	};
 	// bytes of the two buffers for a launch (0, 0 for the small-scene kernels)
 	void rolling_buffer_bytes(const queue_params& queue, uint32_t samples_per_pixel, uint32_t width, uint32_t local_rows, bool big_scene, size_t& item_sums_bytes, size_t& pixel_done_bytes);
@@ -180,6 +196,11 @@ namespace rt_hip
 #ifdef RT_HIP_REGION_COUNTERS
 		static constexpr unsigned regions = 13; // experiment variant only (kernels.hip, RT_HIP_REGION)
 		unsigned long long region_runs[regions], region_lanes[regions];
+#endif
+#ifdef RT_HIP_BVH_CHECK
+		// experiment variant only (tools/bvh_sweep.py --check): sphere queries of the BVH kernel answered again by the linear scan,
+		// and how many of them it answered differently (must stay 0)
+		unsigned long long bvh_checked, bvh_disagreements;
 #endif
 #ifdef RT_HIP_WAVE_CLOCKS
 		// experiment variant only (tools/gpu_wave_tail.py): when every wave of a persistent launch started, found the
@@ -202,6 +223,7 @@ namespace rt_hip
 	// 48.4, 1 500: 66.5 against 65.8, 2 000: 90.3 against 87.9, 3 000: 141.8 against 130.7 (profiles/r05/resident_vs_dense_streamed.txt;
 	// against the streamed kernel as it was before that build the lead lasted to 4 000 spheres: resident_beyond_1024_ab.txt).
 	constexpr uint32_t streamed_from_primitives = 1300;
+	constexpr uint32_t bvh_stack_float4s = 24u * 256u / 4u; // the BVH kernel's LDS traversal stacks: bvh_max_depth words per thread (bvh.hpp, kernels.hip)
 	constexpr uint32_t tile_primitives = 1024;		   // primitives per LDS tile in the tiled kernel
 
 	// what a context remembers between launches: workgroups per CU that stay resident, for the persistent (big-scene) kernels

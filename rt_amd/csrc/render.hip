@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <exception>
 
 using namespace rt_hip;
@@ -51,14 +52,24 @@ rt_hip_status render_device(rt_hip_ctx* ctx, uint32_t width, uint32_t height, ui
 		return fail(RT_HIP_INVALID_ARGUMENT, "rt_hip_render_device: empty frame %ux%u", width, height);
 	if (static_cast<uint64_t>(width) * height > 0xFFFFFFFFull)
 		return fail(RT_HIP_INVALID_ARGUMENT, "rt_hip_render_device: %ux%u exceeds the 32-bit pixel index of image_view", width, height);
-	if (flags & ~static_cast<uint32_t>(RT_HIP_FLAG_FORCE_TILED | RT_HIP_FLAG_FORCE_RESIDENT | RT_HIP_FLAG_PERSISTENT_FRAME | RT_HIP_FLAG_SM_MATERIALS | RT_HIP_FLAG_PREVIEW | RT_HIP_FLAG_FORCE_STREAMED | RT_HIP_FLAG_FAST | RT_HIP_FLAG_STATS | RT_HIP_FLAG_FORCE_HALF_CHUNKS | RT_HIP_FLAG_FORCE_WHOLE_CHUNKS))
+	if (flags & ~static_cast<uint32_t>(RT_HIP_FLAG_FORCE_TILED | RT_HIP_FLAG_FORCE_RESIDENT | RT_HIP_FLAG_PERSISTENT_FRAME | RT_HIP_FLAG_SM_MATERIALS | RT_HIP_FLAG_PREVIEW | RT_HIP_FLAG_FORCE_STREAMED | RT_HIP_FLAG_FAST | RT_HIP_FLAG_STATS | RT_HIP_FLAG_FORCE_HALF_CHUNKS | RT_HIP_FLAG_FORCE_WHOLE_CHUNKS | RT_HIP_FLAG_BVH))
 		return fail(RT_HIP_UNSUPPORTED, "rt_hip_render_device: unknown flag bits 0x%x", flags);
+	if ((flags & RT_HIP_FLAG_BVH) && (flags & (RT_HIP_FLAG_FORCE_TILED | RT_HIP_FLAG_FORCE_RESIDENT | RT_HIP_FLAG_FORCE_STREAMED)))
+		return fail(RT_HIP_UNSUPPORTED, "rt_hip_render_device: RT_HIP_FLAG_BVH chooses its own kernel (not with RT_HIP_FLAG_FORCE_TILED / _RESIDENT / _STREAMED)");
+	if ((flags & RT_HIP_FLAG_BVH) && (flags & RT_HIP_FLAG_FAST))
+		return fail(RT_HIP_UNSUPPORTED, "rt_hip_render_device: RT_HIP_FLAG_BVH is built for the parity contract's arithmetic only (not with RT_HIP_FLAG_FAST)");
+	if (flags & RT_HIP_FLAG_PREVIEW)
+		flags &= ~static_cast<uint32_t>(RT_HIP_FLAG_BVH); // one ray per pixel: the preview keeps its own scan
 	if ((flags & RT_HIP_FLAG_FORCE_HALF_CHUNKS) && (flags & RT_HIP_FLAG_FORCE_WHOLE_CHUNKS))
 		return fail(RT_HIP_INVALID_ARGUMENT, "rt_hip_render_device: RT_HIP_FLAG_FORCE_HALF_CHUNKS and RT_HIP_FLAG_FORCE_WHOLE_CHUNKS exclude each other");
 	if ((flags & RT_HIP_FLAG_FAST) && (flags & (RT_HIP_FLAG_SM_MATERIALS | RT_HIP_FLAG_PREVIEW)))
 		return fail(RT_HIP_UNSUPPORTED, "rt_hip_render_device: RT_HIP_FLAG_FAST applies to mg_ray_tracer's path only (not with RT_HIP_FLAG_SM_MATERIALS / RT_HIP_FLAG_PREVIEW)");
 	if (!ctx->have_scene)
 		return fail(RT_HIP_NO_SCENE, "rt_hip_render_device: no scene uploaded");
+	if (flags & RT_HIP_FLAG_BVH)
+		if (const rt_hip_status st = ensure_bvh(ctx))
+			return st;
+	const device_bvh* const bvh = (flags & RT_HIP_FLAG_BVH) ? ctx->bvh_descriptor : nullptr;
 	if (height > 65535u * 2u) // the launch grid's y dimension counts pixel tiles at least two rows high
 		return fail(RT_HIP_INVALID_ARGUMENT, "rt_hip_render_device: frame height %u exceeds the supported 131070 rows", height);
 	const rt_hip_partition whole = { 0, 1, RT_HIP_DEFAULT_STRIPE_ROWS };
@@ -192,6 +203,7 @@ rt_hip_status render_device(rt_hip_ctx* ctx, uint32_t width, uint32_t height, ui
 
 	bool rolling_items = false; // the persistent big-scene kernels draw items from a sequence whose head must start at 0
 	rolling_buffers rolling;
+	rolling.bvh = bvh;
 	if (!(flags & RT_HIP_FLAG_PREVIEW))
 	{
 		const uint32_t variant = choose_kernel(ctx->scene, flags, f.samples_per_pixel, f.pinhole != 0 || f.eye_form == 2u, static_cast<uint64_t>(width) * f.local_rows);
@@ -307,6 +319,9 @@ namespace rt_hip
 			ctx->stats.segments = segments;
 			ctx->stats.sphere_tests = segments * ctx->scene.n_spheres;
 			ctx->stats.plane_tests = segments * ctx->scene.n_planes;
+#ifdef RT_HIP_BVH_CHECK // (experiment builds: tools/bvh_sweep.py --check reads this line)
+			std::fprintf(stderr, "bvh_check: %llu queries, %llu disagreements\n", ctx->counters_host->bvh_checked, ctx->counters_host->bvh_disagreements);
+#endif
 		}
 		return ok();
 	}

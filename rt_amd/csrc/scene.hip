@@ -5,9 +5,11 @@
 // The columns are exactly the soagen columns the reference fills at load (src/scene.cpp:583,595; src/soa.toml:6-45) and
 // whose split float columns none of its renderers reads.
 #include "internal.hpp"
+#include "bvh.hpp"
 
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <exception>
 
 using namespace rt_hip;
@@ -290,6 +292,7 @@ namespace rt_hip
 			RT_HIP_TRY(hipMemcpy(ctx->scene_columns.ptr, r.image, L.total, hipMemcpyHostToDevice));
 			ctx->scene_fingerprint = r.print;
 			ctx->scene_bytes = L.total;
+			ctx->scene_uploads++; // (a sphere hierarchy built for the previous scene is stale from here on: ensure_bvh)
 			ctx->small = r.small;
 			ctx->small_sm = r.small_sm;
 
@@ -330,6 +333,54 @@ namespace rt_hip
 		ctx->have_scene = true;
 		ctx->phases.scene_resident = resident ? 1u : 0u;
 		ctx->stats.upload_ms = static_cast<float>(seconds_since(t0) * 1e3);
+		return ok();
+	}
+
+	// RT_HIP_FLAG_BVH: make ctx->scene.bvh describe a hierarchy of the resident scene.  Built on the host from the (c, r^2) table
+	// read back from the device — the very floats the linear kernels read — at the first such frame after an upload, and
+	// kept until the next one.  The build's time is added to upload_ms.
+	rt_hip_status ensure_bvh(rt_hip_ctx* ctx)
+	{
+		if (ctx->bvh_built_for == ctx->scene_uploads)
+			return ok();
+		const auto t0 = std::chrono::steady_clock::now();
+		const uint32_t n = ctx->scene.n_spheres;
+		RT_HIP_TRY(hipSetDevice(ctx->device));
+		RT_HIP_TRY(hipDeviceSynchronize()); // a previous frame may still be reading the old tree
+		std::vector<float> geometry(static_cast<size_t>(n) * 4);
+		if (n)
+			RT_HIP_TRY(hipMemcpy(geometry.data(), ctx->scene.primitive_geometry, static_cast<size_t>(n) * sizeof(float4), hipMemcpyDeviceToHost));
+		bvh_host tree;
+		std::string why;
+		if (!build_bvh(geometry.data(), n, tree, why))
+			return fail(RT_HIP_UNSUPPORTED, "RT_HIP_FLAG_BVH: %s", why.c_str());
+		// one block: the descriptor the kernel reads first, nodes, leaf-ordered spheres, their scene indices, the always list
+		// (256-byte aligned starts)
+		const auto aligned = [](size_t bytes) { return (bytes + 255u) & ~static_cast<size_t>(255u); };
+		const size_t nodes_at = aligned(sizeof(device_bvh)), spheres_at = nodes_at + aligned(tree.nodes.size() * 4), order_at = spheres_at + aligned(tree.spheres.size() * 4);
+		const size_t always_at = order_at + aligned(tree.order.size() * 4), total = always_at + aligned(tree.always.size() * 4);
+		std::vector<unsigned char> image(total, 0);
+		std::memcpy(image.data() + nodes_at, tree.nodes.data(), tree.nodes.size() * 4);
+		std::memcpy(image.data() + spheres_at, tree.spheres.data(), tree.spheres.size() * 4);
+		std::memcpy(image.data() + order_at, tree.order.data(), tree.order.size() * 4);
+		std::memcpy(image.data() + always_at, tree.always.data(), tree.always.size() * 4);
+		ctx->bvh_descriptor = nullptr;
+		RT_HIP_TRY(ctx->bvh_block.reserve(image.size()));
+		unsigned char* const base = ctx->bvh_block.as<unsigned char>();
+		device_bvh b{};
+		b.nodes = reinterpret_cast<const float4*>(base + nodes_at);
+		b.spheres = reinterpret_cast<const float4*>(base + spheres_at);
+		b.order = reinterpret_cast<const uint32_t*>(base + order_at);
+		b.always = reinterpret_cast<const uint32_t*>(base + always_at);
+		b.root = tree.root;
+		b.n_tree = static_cast<uint32_t>(tree.order.size());
+		b.n_always = static_cast<uint32_t>(tree.always.size());
+		b.cx = tree.centre[0], b.cy = tree.centre[1], b.cz = tree.centre[2], b.radius = tree.radius;
+		std::memcpy(image.data(), &b, sizeof(b));
+		RT_HIP_TRY(hipMemcpy(ctx->bvh_block.ptr, image.data(), image.size(), hipMemcpyHostToDevice));
+		ctx->bvh_descriptor = reinterpret_cast<const device_bvh*>(base);
+		ctx->bvh_built_for = ctx->scene_uploads;
+		ctx->stats.upload_ms += static_cast<float>(seconds_since(t0) * 1e3);
 		return ok();
 	}
 }

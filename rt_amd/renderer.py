@@ -53,6 +53,22 @@ def live_frame_locks() -> int:
     return int(capi.hip_lib().rt_hip_live_frame_locks())
 
 
+def bvh_build(scene: RtHipScene) -> dict:
+    """The sphere hierarchy RT_HIP_FLAG_BVH builds for `scene`, built on the host (rt_hip_kat_bvh_build; no GPU needed):
+    nodes float32[N, 16] (links as bits in words 3 and 7), order / always uint32, spheres float32[T, 4] (leaf order),
+    bound float32[4] (centre, radius), depth, root."""
+    n = max(int(scene.n_spheres), 1)
+    counts = np.zeros(5, dtype=np.uint32)
+    nodes = np.zeros((n, 16), dtype=np.float32)
+    order = np.zeros(n, dtype=np.uint32)
+    spheres = np.zeros((n, 4), dtype=np.float32)
+    always = np.zeros(n, dtype=np.uint32)
+    bound = np.zeros(4, dtype=np.float32)
+    capi.check_kat(capi.kat_lib().rt_hip_kat_bvh_build(C.byref(scene), counts.ctypes.data, nodes.ctypes.data, order.ctypes.data, spheres.ctypes.data, always.ctypes.data, bound.ctypes.data))
+    n_nodes, n_tree, n_always, depth, root = (int(c) for c in counts)
+    return {"nodes": nodes[:n_nodes], "order": order[:n_tree], "spheres": spheres[:n_tree], "always": always[:n_always], "bound": bound, "depth": depth, "root": root}
+
+
 def device_count() -> int:
     n = C.c_int()
     check(capi.hip_lib().rt_hip_device_count(C.byref(n)))
@@ -217,7 +233,9 @@ class HipRayTracer:
         capi.check_kat(capi.kat_lib().rt_hip_kat_random(self._ctx, seed, pixel, sample, n, out.ctypes.data))
         return out
 
-    def kat_closest_hit(self, origins: np.ndarray, directions: np.ndarray):
+    def kat_closest_hit(self, origins: np.ndarray, directions: np.ndarray, bvh: bool = False):
+        """Closest hit of each ray against the resident scene: (distance, kind, index, normal).  `bvh`: through the sphere
+        hierarchy of RT_HIP_FLAG_BVH (rt_hip_kat_closest_hit_bvh) instead of the linear scan."""
         o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
         d = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
         n = len(o)
@@ -225,7 +243,8 @@ class HipRayTracer:
         kind = np.empty(n, dtype=np.uint32)
         index = np.empty(n, dtype=np.uint32)
         normal = np.empty((n, 3), dtype=np.float32)
-        capi.check_kat(capi.kat_lib().rt_hip_kat_closest_hit(self._ctx, n, o.ctypes.data, d.ctypes.data, dist.ctypes.data, kind.ctypes.data, index.ctypes.data, normal.ctypes.data))
+        entry = capi.kat_lib().rt_hip_kat_closest_hit_bvh if bvh else capi.kat_lib().rt_hip_kat_closest_hit
+        capi.check_kat(entry(self._ctx, n, o.ctypes.data, d.ctypes.data, dist.ctypes.data, kind.ctypes.data, index.ctypes.data, normal.ctypes.data))
         return dist, kind, index, normal
 
     def kat_sqrt_div(self, a: np.ndarray, b: np.ndarray):

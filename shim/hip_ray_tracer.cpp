@@ -110,6 +110,18 @@ namespace
 		return flags;
 	}
 
+	// RT_HIP_ACCEL=bvh opts in to RT_HIP_FLAG_BVH: the spheres through a bounding volume hierarchy, the same frame bit for bit
+	// (for scenes of thousands of spheres; the preview ignores it)
+	uint32_t accel_flags()
+	{
+		static const uint32_t flags = []
+		{
+			const char* accel = std::getenv("RT_HIP_ACCEL");
+			return (accel && std::strcmp(accel, "bvh") == 0) ? static_cast<uint32_t>(RT_HIP_FLAG_BVH) : static_cast<uint32_t>(RT_HIP_FLAG_NONE);
+		}();
+		return flags;
+	}
+
 	// ModeFlags: 0 = mg_ray_tracer's scatter table; RT_HIP_FLAG_SM_MATERIALS = sm_ray_tracer's (dielectrics refract);
 	// RT_HIP_FLAG_PREVIEW = the one-ray-per-pixel preview of src/renderers/rasterizer.cpp
 	template <uint32_t ModeFlags>
@@ -179,7 +191,7 @@ namespace
 			const char* fixed	= std::getenv("RT_HIP_SEED");
 			const uint64_t seed = fixed ? std::strtoull(fixed, nullptr, 0) : ++frame_number;
 
-			if (rt_hip_render(ctx, &s, pixels.data(), pixels.size().x, pixels.size().y, seed, frame_flags() | ModeFlags, nullptr, nullptr)
+			if (rt_hip_render(ctx, &s, pixels.data(), pixels.size().x, pixels.size().y, seed, frame_flags() | accel_flags() | ModeFlags, nullptr, nullptr)
 				!= RT_HIP_OK)
 				std::cerr << "error: hip_ray_tracer: " << rt_hip_last_error() << "\n";
 		}
