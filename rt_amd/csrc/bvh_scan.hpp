@@ -24,7 +24,15 @@
 // most 5u (|o - C| + R + pad) on either side of a t that can be accepted — far inside that spare.  A sphere whose t could win
 // has t <= best.t, and fl(best.t + pad) >= best.t + 5uU wherever that matters (best.t <= 2.5 U; beyond, no tree sphere's t
 // comes near best.t anyway).  The adversarial rays of tests/test_gpu_bvh.py (tangents at +-1..64 ulp, origins on and inside
-// spheres, duplicates) and the RT_HIP_BVH_CHECK build over config 5's 300 M queries check it.
+// spheres, duplicates) and the RT_HIP_BVH_CHECK build over config 5's 300 M queries check it at one scale.  Across the scales
+// the builder admits (2^-60 .. 2^38, r^2 down to subnormal and zero), origins up to 1e6 scene widths away, scenes 1e6 widths
+// off the coordinate origin, and directions with zero, subnormal and tiny components from origins on box faces,
+// tests/test_bvh_cull_audit.py audits on the host that no box between the root and the oracle's answer is culled (with a pad
+// no larger than the one computed here), and test_closest_hit_in_every_regime_of_the_cull_bound of tests/test_gpu_bvh.py runs
+// the same scenes and rays through this code; test_directions_at_the_edges_of_the_length_gate sits on both sides of the
+// |d|^2 gate, test_a_ray_that_fills_the_stack and test_frames_of_a_tree_as_deep_as_the_stack use the last stack word, and
+// test_frames_whose_lanes_fall_back_to_the_linear_scan runs the render kernel's rescan.  Measured there, the margin has a factor
+// of 4 to 16 to spare, not more: the audit still passes at 2^-10 and fails at 2^-12 (profiles/r07/README.md).
 #pragma once
 
 #include "bvh.hpp"

@@ -14,76 +14,14 @@ import pytest
 import rt_amd
 from rt_amd import capi
 from rt_amd.renderer import bvh_build
+from tests.bvh_cases import STACK_DEPTH, check_tree, sphere_scene
 
 ROOT = __import__("pathlib").Path(__file__).resolve().parent.parent
-LEAF = 0x80000000
-STACK_DEPTH = 24  # bvh_max_depth (rt_amd/csrc/bvh.hpp)
 
 
 def header_constant(name):
     text = (ROOT / "rt_amd" / "csrc" / "bvh.hpp").read_text()
     return int(re.search(rf"constexpr uint32_t {name} = (\d+);", text).group(1))
-
-
-def sphere_scene(rows):
-    rows = np.asarray(rows, dtype=np.float64).reshape(-1, 5)
-    return rt_amd.scene_from_arrays(spheres=rows, materials=[(0, 0.5, 0.5, 0.5, 1, 0, 0)])
-
-
-def geometry_of(scene):
-    n = scene.n_spheres
-    c = [np.ctypeslib.as_array(p, (n,)).astype(np.float32) for p in (scene.sphere_center_x, scene.sphere_center_y, scene.sphere_center_z)]
-    r = np.ctypeslib.as_array(scene.sphere_radius, (n,)).astype(np.float32)
-    return np.stack(c + [r * r], axis=1).astype(np.float32)  # (cx, cy, cz, r^2) as the upload derives it
-
-
-def check_tree(scene, t):
-    n = scene.n_spheres
-    g = geometry_of(scene)
-    order, always, nodes = t["order"], t["always"], t["nodes"]
-    # every sphere exactly once across the leaves and the always list
-    assert np.array_equal(np.sort(np.concatenate([order, always])), np.arange(n, dtype=np.uint32))
-    assert np.array_equal(always, np.sort(always))
-    # the leaf table is a bit copy of the primitive table's rows
-    assert np.array_equal(t["spheres"].view(np.uint32), g[order].view(np.uint32))
-    assert t["depth"] <= STACK_DEPTH
-    if len(order) == 0:
-        return
-    half = np.sqrt(g[:, 3].astype(np.float64))
-    lo = g[:, :3].astype(np.float64) - half[:, None]
-    hi = g[:, :3].astype(np.float64) + half[:, None]
-    # the ball around the tree holds every tree sphere: |c - C| + sqrt(r^2) <= R
-    centre, radius = t["bound"][:3].astype(np.float64), float(t["bound"][3])
-    reach = np.linalg.norm(g[order, :3].astype(np.float64) - centre, axis=1) + half[order]
-    assert (reach <= radius).all()
-    links = nodes[:, [3, 7]].copy().view(np.uint32)
-    seen_slots = np.zeros(len(order), dtype=np.int32)
-
-    def leaf_range(link):
-        first, count = link & ((1 << 29) - 1), ((link >> 29) & 3) + 1
-        return first, count
-
-    def walk(link, box_lo, box_hi, level):
-        if link & LEAF:
-            first, count = leaf_range(link)
-            assert first + count <= len(order)
-            seen_slots[first : first + count] += 1
-            ids = order[first : first + count]
-            if box_lo is not None:
-                assert (lo[ids] >= box_lo).all() and (hi[ids] <= box_hi).all(), "a leaf box does not contain its spheres' boxes"
-            return 0
-        assert link < len(nodes)
-        node = nodes[link].astype(np.float64)
-        a_lo, a_hi, b_lo, b_hi = node[0:3], node[4:7], node[8:11], node[12:15]
-        if box_lo is not None:
-            assert (a_lo >= box_lo).all() and (a_hi <= box_hi).all() and (b_lo >= box_lo).all() and (b_hi <= box_hi).all(), "a node box does not contain its children's"
-        return 1 + max(walk(int(links[link, 0]), a_lo, a_hi, level + 1), walk(int(links[link, 1]), b_lo, b_hi, level + 1))
-
-    depth = walk(t["root"], None, None, 1)
-    assert depth == t["depth"]
-    assert (seen_slots == 1).all(), "every leaf slot belongs to exactly one leaf"
-    # leaves of at most four spheres is what the link encodes; inner nodes number at most (tree spheres - 1)
-    assert len(nodes) <= max(len(order) - 1, 0)
 
 
 def build_twice(scene):
