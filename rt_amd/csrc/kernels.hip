@@ -37,6 +37,9 @@
 // This file is compiled TWICE into librt_hip.so: as it stands (the parity contract: -ffp-contract=off, exactly rounded
 // square roots and quotients), and with -DRT_HIP_FAST_BUILD -ffp-contract=fast (RT_HIP_FLAG_FAST: contract.hpp's
 // hardware approximations), where it provides launch_render_fast() and nothing else.
+//
+// What is launched is decided elsewhere: launch_plan.cpp (plan_launch: which kernel, which build, queue shape, grid, LDS — host-only
+// policy, tested on the CPU).  This file holds the kernels and the dispatch from a plan's kernel_build to the instantiation.
 #include "kernels.hpp"
 #include "contract.hpp"
 #include "scan.hpp"
@@ -50,7 +53,6 @@
 #include "../../include/rt_hip.h"
 
 #include <algorithm>
-#include <cstdlib>
 
 // waves per SIMD the kernel variants are compiled for (register budget = 512 / waves): measured, see render_queue
 #ifndef RT_HIP_WAVES_FEW
@@ -65,19 +67,11 @@
 #ifndef RT_HIP_WAVES_RESIDENT
 #define RT_HIP_WAVES_RESIDENT 7
 #endif
-// the streamed kernel of frames that fill the device (NS == -3: no cooperative scan of sparse waves, whose four 16-byte loads in flight
-// per lane set the register count of the other build): 80 registers hold its loop, half-chunk items included — config 5 5.47 s at 5
-// waves WITH the cooperative scan, 5.09 without, 4.99 at 6 waves, 5.05 at 7 (profiles/r05/streamed_occupancy_ab.txt)
-#ifndef RT_HIP_WAVES_DENSE
-#define RT_HIP_WAVES_DENSE 6
-#endif
-// the BVH kernel (NS == -4, RT_HIP_FLAG_BVH): a pixel tile per wave with a traversal stack of bvh_max_depth words per lane in LDS
+// (RT_HIP_WAVES_DENSE — the streamed kernel of frames that fill the device — and RT_HIP_PERSISTENT_WAVES_CAP: launch_plan.hpp, whose plan reads them too)
+// the BVH kernel (scan_bvh, RT_HIP_FLAG_BVH): a pixel tile per wave with a traversal stack of bvh_max_depth words per lane in LDS
 // (24 KiB per workgroup)
 #ifndef RT_HIP_WAVES_BVH
 #define RT_HIP_WAVES_BVH 5
-#endif
-#ifndef RT_HIP_PERSISTENT_WAVES_CAP
-#define RT_HIP_PERSISTENT_WAVES_CAP 5 // workgroups per CU of the persistent (big-scene) launches: see launch_queue_sm
 #endif
 
 // Region counters (tools/region_profile.py; built only as an experiment variant, never in the product): how often each
@@ -156,7 +150,6 @@ namespace rt_hip
 		// The one thing a minimum cannot reproduce is a NaN distance (a degenerate ray), which the sequential rule lets
 		// in and then never displaces consistently: if any lane meets one, the ray is reported as not scanned and goes
 		// through the sequential scan.  The per-sphere arithmetic is finish_sphere's, bit for bit.
-		[[maybe_unused]] constexpr uint32_t sparse_wave_rays = 8;	 // a wave holding at most this many rays scans together
 		constexpr uint32_t sparse_min_spheres = sparse_launch_min_spheres; // (below that a sequential scan is a few microseconds anyway)
 
 		__device__ __forceinline__ void test_sphere_alone(candidate& best, bool& met_nan, vec3 o, vec3 d, float4 s, uint32_t index)
@@ -212,8 +205,6 @@ namespace rt_hip
 			found.index = found.have ? key_i : 0u;
 			return true;
 		}
-
-		constexpr uint32_t small_table_float4s = 2u * scalar_max_spheres; // LDS tables of the scalar-register kernels: geometry, shading
 
 		// everything a lane carries between loop trips
 		struct lane_state
@@ -285,13 +276,13 @@ namespace rt_hip
 		// keep waves short, so that a launch has tens of thousands of them to balance over the chip; which lane
 		// computes which chunk cannot change a result.
 		//
-		// NS > 0: `small` kernel, NS spheres in SGPRs (kernel argument).  NS == 0: `resident` kernel, all primitives in LDS.
-		// NS == -1: `tiled` kernel — the primitives stream from the SoA columns in HBM/L2 through one LDS tile shared by the
+		// NS > 0: `small` kernel, NS spheres in SGPRs (kernel argument).  NS == scan_resident: `resident` kernel, all primitives in LDS.
+		// NS == scan_tiled: `tiled` kernel — the primitives stream from the SoA columns in HBM/L2 through one LDS tile shared by the
 		// workgroup's four waves (coalesced dword per lane per column, radius squared on the way in); every wave still
 		// runs its own queue, but the workgroup advances in lock step, one path segment per trip, with barriers around
-		// each tile, until all four waves are done.  NS == -2: `streamed` kernel — the resident loop reading the primitive
-		// table from HBM/L2 with wave-uniform scalar loads.  NS == -3: the same without the cooperative scan of sparse waves, for frames
-		// that fill the device (6 waves per SIMD; RT_HIP_WAVES_DENSE above).  NS == -4: the BVH kernel (RT_HIP_FLAG_BVH) — the resident
+		// each tile, until all four waves are done.  NS == scan_streamed: `streamed` kernel — the resident loop reading the primitive
+		// table from HBM/L2 with wave-uniform scalar loads.  NS == scan_streamed_dense: the same without the cooperative scan of sparse waves, for frames
+		// that fill the device (6 waves per SIMD; RT_HIP_WAVES_DENSE, launch_plan.hpp).  NS == scan_bvh: the BVH kernel (RT_HIP_FLAG_BVH) — the resident
 		// kernel's tile queue, planes scanned from the table in memory, spheres through the hierarchy, one traversal per lane
 		// (bvh_scan.hpp; the lanes of a wave hold unrelated rays, and a wave-wide walk would visit the union of their paths).
 		// SM: scatter table of sm_ray_tracer (RT_HIP_FLAG_SM_MATERIALS) instead of mg_ray_tracer's.
@@ -415,6 +406,20 @@ namespace rt_hip
 #endif
 		}
 
+		// waves per SIMD a build is compiled for (the RT_HIP_WAVES_* above)
+		constexpr int waves_per_simd(int NS, int NP)
+		{
+			if (NS == scan_bvh)
+				return RT_HIP_WAVES_BVH;
+			if (NS == scan_streamed_dense)
+				return RT_HIP_WAVES_DENSE;
+			if (NS < 0) // scan_tiled, scan_streamed
+				return 5;
+			if (NS == scan_resident)
+				return RT_HIP_WAVES_RESIDENT;
+			return NS >= 6 && NS + NP >= 7 ? RT_HIP_WAVES_MANY : RT_HIP_WAVES_FEW;
+		}
+
 		// HALF (small and resident kernels, short launches; see choose_queue): the unit of work is HALF a chunk, 8 samples.
 		// The chunk sum stays what the contract says — sixteen samples added in sample order — so the lane that traces a
 		// chunk's second half cannot add anything up itself: it parks its (up to) eight sample values in the tile's LDS
@@ -434,7 +439,7 @@ namespace rt_hip
 		// LDS-resident kernel (+35 % on basic.toml); now they keep the scalar-register kernel, in a build of it that carries
 		// the 18 scalars of the general form INSTEAD of the 18 of the affine one (both would not fit its scalar registers).
 		template <int NS, bool SM, bool HALF = false, int NP = 0, bool GC = false>
-		__global__ __launch_bounds__(block_threads, NS == -4 ? RT_HIP_WAVES_BVH : NS == -3 ? RT_HIP_WAVES_DENSE : (NS < 0 ? 5 : (NS == 0 ? RT_HIP_WAVES_RESIDENT : (NS >= 6 && NS + NP >= 7 ? RT_HIP_WAVES_MANY : RT_HIP_WAVES_FEW)))) void render_queue(const frame_params p,
+		__global__ __launch_bounds__(block_threads, waves_per_simd(NS, NP)) void render_queue(const frame_params p,
 																	  const queue_params q,
 																	  const small_scene small,
 																	  const device_scene s,
@@ -442,23 +447,23 @@ namespace rt_hip
 																	  uint32_t* __restrict__ out_rgba,
 																	  float* __restrict__ out_rgb,
 																	  device_counters* __restrict__ counters,
-																	  unsigned long long* item_sums, // [NS < 0] chunk sums in transit: 16 bytes per item; [NS == -4] the device_bvh
+																	  unsigned long long* item_sums, // [NS < 0] chunk sums in transit: 16 bytes per item; [NS == scan_bvh] the device_bvh
 																									 // descriptor (rolling_buffers::bvh)
 																	  uint32_t* pixel_done)			 // [NS < 0] items arrived per pixel (zeroed in front of every launch)
 		{
 			extern __shared__ float4 lds[];
-			// [NS > 0] 8 geometry (with the scatter function) + 8 shading float4s | [NS == 0] all primitives; then the chunk slots
+			// [NS > 0] 8 geometry (with the scatter function) + 8 shading float4s | [NS == scan_resident] all primitives; then the chunk slots
 			float4* const lds_geometry = lds;
 			float4* const lds_shading = lds + scalar_max_spheres;
-			constexpr bool RESIDENT = NS == 0; // all primitives in LDS
-			// [NS == 0] from resident_scalar_scan_from spheres on the sphere scan reads the table in memory (scalar loads): only the planes are staged
+			constexpr bool RESIDENT = NS == scan_resident; // all primitives in LDS
+			// [NS == scan_resident] from resident_scalar_scan_from spheres on the sphere scan reads the table in memory (scalar loads): only the planes are staged
 			// (a build of its own, NP == 1: the scalar-load scan keeps two groups of four spheres in 32 scalar registers, which the
 			// LDS-scan build — scenes below the threshold — has for the frame's constants instead)
-			constexpr bool RESIDENT_SCALAR_SCAN = NS == 0 && NP == 1;
+			constexpr bool RESIDENT_SCALAR_SCAN = NS == scan_resident && NP == 1;
 			const bool spheres_in_lds = RESIDENT && !RESIDENT_SCALAR_SCAN;
 			const uint32_t lds_spheres = spheres_in_lds ? s.n_spheres : 0u;
-			constexpr bool BVH = NS == -4;
-			const uint32_t table_float4s = NS > 0 ? small_table_float4s : (RESIDENT ? lds_spheres + s.n_planes : (NS == -1 ? tile_primitives : (BVH ? bvh_stack_float4s : 0u)));
+			constexpr bool BVH = NS == scan_bvh;
+			const uint32_t table_float4s = NS > 0 ? small_table_float4s : (RESIDENT ? lds_spheres + s.n_planes : (NS == scan_tiled ? tile_primitives : (BVH ? bvh_stack_float4s : 0u)));
 			if (NS > 0)
 			{
 				if (threadIdx.x == 0)
@@ -498,7 +503,7 @@ namespace rt_hip
 			// below resident_scalar_scan_from spheres), GC = "the frame is not a pinhole's" (eye or homogeneous form, chosen at run time);
 			// NP == 1: the scalar-load scan, all forms at run time as before (split by form it gained nothing and lost 4 % through a tilted
 			// camera).  12 spheres 1.23 -> 1.15 ms, 32: 2.06 -> 2.01, basic.toml forced here 2.89 -> 2.72 (profiles/r05/resident_forms_ab.txt).
-			constexpr bool RESIDENT_LDS_SCAN = NS == 0 && NP == 0;
+			constexpr bool RESIDENT_LDS_SCAN = NS == scan_resident && NP == 0;
 			constexpr bool PINHOLE_ONLY = (NS > 0 || RESIDENT_LDS_SCAN) && !GC, EYE_ONLY = NS > 0 && GC, NEVER_PINHOLE = RESIDENT_LDS_SCAN && GC;
 			const uint32_t lane = threadIdx.x & 63u;
 			const uint32_t wave = threadIdx.x >> 6;
@@ -775,7 +780,7 @@ namespace rt_hip
 					wave_segments += static_cast<unsigned>(__builtin_popcountll(__builtin_amdgcn_ballot_w64(tracing)));
 				candidate tiled_planes = { 0.0f, 0u, false };
 				candidate tiled_spheres = { 0.0f, 0u, false };
-				if (NS == -1 && __syncthreads_or(tracing)) // nothing to stream on the very first trip: no lane holds a ray yet
+				if (NS == scan_tiled && __syncthreads_or(tracing)) // nothing to stream on the very first trip: no lane holds a ray yet
 				{
 					// all 256 threads stage, lanes without a ray just do not scan
 					for (uint32_t first = 0; first < s.n_planes; first += tile_primitives)
@@ -810,7 +815,7 @@ namespace rt_hip
 #else
 				constexpr bool sparse_waves = true;
 #endif
-				if (sparse_waves && NS == -2 && s.n_spheres >= sparse_min_spheres)
+				if (sparse_waves && NS == scan_streamed && s.n_spheres >= sparse_min_spheres)
 				{
 					unsigned long long holders = __builtin_amdgcn_ballot_w64(tracing);
 					if (holders != 0 && static_cast<uint32_t>(__builtin_popcountll(holders)) <= q.sparse_rays)
@@ -846,7 +851,7 @@ namespace rt_hip
 					uint32_t kind;
 					float distance;
 					uint32_t small_index = 0;
-					if (NS == -1)
+					if (NS == scan_tiled)
 					{
 						uint32_t index;
 						kind = select_hit(tiled_spheres, tiled_planes, distance, index);
@@ -954,7 +959,7 @@ namespace rt_hip
 								atomicAdd(&counters->bvh_disagreements, 1ull);
 #endif
 						}
-						else if (NS == -2 || NS == -3)
+						else if (NS == scan_streamed || NS == scan_streamed_dense)
 						{
 							if (scanned_together)
 								spheres = together;
@@ -1134,7 +1139,7 @@ namespace rt_hip
 						RT_HIP_BECOME(lane_retired);
 				}
 				const bool queue_empty = __builtin_amdgcn_ballot_w64(!RT_HIP_IS(lane_retired)) == 0;
-				if (NS == -1)
+				if (NS == scan_tiled)
 				{
 					if (__syncthreads_and(queue_empty)) // the four waves leave together
 						break;
@@ -1537,281 +1542,84 @@ namespace rt_hip
 
 #endif // !RT_HIP_FAST_BUILD
 
-		template <int NS, bool SM, int NP = 0, bool GC = false>
-		void launch_queue_sm(const frame_params& frame,
-							 const queue_params& queue,
-							 const small_scene& small,
-							 const device_scene& scene,
-							 dim3 grid, // small scenes: the grid of tiles; big scenes: x = the most workgroups the tiles can occupy
-							 size_t lds_bytes,
-							 uint32_t* d_rgba8,
-							 float* d_rgb_f32,
-							 device_counters* d_counters,
-							 const rolling_buffers& rolling,
-							 uint32_t compute_units,
-							 launch_cache& cache,
-							 hipStream_t stream)
+		// what launch_render was called with, on its way to the instantiation the plan names
+		struct launch_arguments
 		{
-			if (NS < 0 && NS != -4)
+			const frame_params& frame;
+			const device_scene& scene;
+			const small_scene& small;
+			const launch_plan& plan;
+			uint32_t* d_rgba8;
+			float* d_rgb_f32;
+			device_counters* d_counters;
+			const rolling_buffers& rolling;
+			uint32_t compute_units;
+			launch_cache& cache;
+			hipStream_t stream;
+		};
+
+		template <int NS, bool SM, int NP = 0, bool GC = false>
+		void launch_queue_sm(const launch_arguments& a)
+		{
+			const launch_plan& plan = a.plan;
+			dim3 grid(plan.grid_x, plan.grid_y); // small scenes: the grid of tiles; big scenes: x = the most workgroups the items can occupy
+			if (scan_is_persistent(NS))
 			{
 				// persistent launch: exactly what the device keeps resident (surplus workgroups would only find the queue dry).
 				// The answer is remembered per context (= per device and host thread of use), per kernel and LDS size.
-#ifdef RT_HIP_FAST_BUILD
-				constexpr bool fast_arithmetic = true;
-#else
-				constexpr bool fast_arithmetic = false;
-#endif
-				const bool sub_chunk_items = !SM && queue.halves;
-				launch_cache::entry& known = cache.persistent[launch_cache::slot(NS == -1 ? 0u : (NS == -2 ? 1u : 2u), SM, fast_arithmetic, sub_chunk_items)];
-				if (known.lds_bytes != lds_bytes || known.per_cu < 1)
+				launch_cache::entry& known = a.cache.persistent[plan.persistent_slot];
+				if (known.lds_bytes != plan.lds_bytes || known.per_cu < 1)
 				{
 					int per_cu = 0;
 					hipError_t asked;
 					if constexpr (!SM)
-						asked = sub_chunk_items ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, render_queue<NS, SM, true>, static_cast<int>(block_threads), lds_bytes)
-												: hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, render_queue<NS, SM, false>, static_cast<int>(block_threads), lds_bytes); // (persistent kernels: never with scalar-register planes)
+						asked = plan.build.sub_chunk_items ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, render_queue<NS, SM, true>, static_cast<int>(block_threads), plan.lds_bytes)
+														   : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, render_queue<NS, SM, false>, static_cast<int>(block_threads), plan.lds_bytes); // (persistent kernels: never with scalar-register planes)
 					else
-						asked = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, render_queue<NS, SM>, static_cast<int>(block_threads), lds_bytes);
+						asked = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, render_queue<NS, SM>, static_cast<int>(block_threads), plan.lds_bytes);
 					if (asked != hipSuccess || per_cu < 1)
 						per_cu = 4;
 					// Not more workgroups than the kernels were compiled for (5 waves per SIMD = 5 workgroups per CU), even when the
 					// register allocation of a build happens to leave room for a sixth (round 4 saw 6 144 waves instead of 5 120
 					// on one build): the launch's shape should not depend on that.  Measured, it makes no difference either way
 					// (config 5: 5.479 against 5.476 s, profiles/r04/persistent_waves_ab.txt).
-					per_cu = std::min(per_cu, NS == -3 ? RT_HIP_WAVES_DENSE : RT_HIP_PERSISTENT_WAVES_CAP);
+					per_cu = std::min(per_cu, plan.per_cu_cap);
 					(void)hipGetLastError();
-					known.lds_bytes = lds_bytes;
+					known.lds_bytes = plan.lds_bytes;
 					known.per_cu = per_cu;
 				}
-				grid = dim3(std::min(grid.x, compute_units * static_cast<uint32_t>(known.per_cu)));
+				grid = dim3(std::min(grid.x, a.compute_units * static_cast<uint32_t>(known.per_cu)));
 			}
 			// (the BVH kernel takes its hierarchy's descriptor in the item_sums argument's place)
-			unsigned long long* const item_sums = NS == -4 ? reinterpret_cast<unsigned long long*>(const_cast<device_bvh*>(rolling.bvh)) : rolling.item_sums;
+			unsigned long long* const item_sums = NS == scan_bvh ? reinterpret_cast<unsigned long long*>(const_cast<device_bvh*>(a.rolling.bvh)) : a.rolling.item_sums;
 			if constexpr (!SM) // (the sm table keeps whole chunks: one set of kernels fewer to build)
 			{
-				if (queue.halves)
+				if (plan.build.sub_chunk_items)
 				{
-					hipLaunchKernelGGL((render_queue<NS, SM, true, NP, GC>), grid, dim3(block_threads), lds_bytes, stream, frame, queue, small, scene, scene.primitive_geometry, d_rgba8, d_rgb_f32, d_counters, item_sums, rolling.pixel_done);
+					hipLaunchKernelGGL((render_queue<NS, SM, true, NP, GC>), grid, dim3(block_threads), plan.lds_bytes, a.stream, a.frame, plan.queue, a.small, a.scene, a.scene.primitive_geometry, a.d_rgba8, a.d_rgb_f32, a.d_counters, item_sums, a.rolling.pixel_done);
 					return;
 				}
 			}
-			hipLaunchKernelGGL((render_queue<NS, SM, false, NP, GC>), grid, dim3(block_threads), lds_bytes, stream, frame, queue, small, scene, scene.primitive_geometry, d_rgba8, d_rgb_f32, d_counters, item_sums, rolling.pixel_done);
+			hipLaunchKernelGGL((render_queue<NS, SM, false, NP, GC>), grid, dim3(block_threads), plan.lds_bytes, a.stream, a.frame, plan.queue, a.small, a.scene, a.scene.primitive_geometry, a.d_rgba8, a.d_rgb_f32, a.d_counters, item_sums, a.rolling.pixel_done);
 		}
 
 		template <int NS, int NP = 0, bool GC = false>
-		void launch_queue(bool sm,
-						  const frame_params& frame,
-						  const queue_params& queue,
-						  const small_scene& small,
-						  const device_scene& scene,
-						  dim3 grid,
-						  size_t lds_bytes,
-						  uint32_t* d_rgba8,
-						  float* d_rgb_f32,
-						  device_counters* d_counters,
-						  const rolling_buffers& rolling,
-						  uint32_t compute_units,
-						  launch_cache& cache,
-						  hipStream_t stream)
+		void launch_queue(const launch_arguments& a)
 		{
 #ifndef RT_HIP_FAST_BUILD // (the API refuses RT_HIP_FLAG_FAST together with RT_HIP_FLAG_SM_MATERIALS)
-			if (sm)
-				launch_queue_sm<NS, true, NP, GC>(frame, queue, small, scene, grid, lds_bytes, d_rgba8, d_rgb_f32, d_counters, rolling, compute_units, cache, stream);
+			if (a.plan.build.sm_table)
+				launch_queue_sm<NS, true, NP, GC>(a);
 			else
 #endif
-				launch_queue_sm<NS, false, NP, GC>(frame, queue, small, scene, grid, lds_bytes, d_rgba8, d_rgb_f32, d_counters, rolling, compute_units, cache, stream);
+				launch_queue_sm<NS, false, NP, GC>(a);
 		}
 	}
 
-#ifndef RT_HIP_FAST_BUILD
-	uint32_t choose_kernel(const device_scene& scene, uint32_t flags, uint32_t samples_per_pixel, bool perspective, uint64_t pixels)
-	{
-		const uint32_t primitives = scene.n_spheres + scene.n_planes;
-		if (flags & RT_HIP_FLAG_BVH) // (render.hip refuses it with the FORCE_ flags, and builds the hierarchy first)
-			return RT_HIP_KERNEL_BVH;
-		if (flags & RT_HIP_FLAG_FORCE_STREAMED)
-			return RT_HIP_KERNEL_STREAMED;
-		if (flags & RT_HIP_FLAG_FORCE_TILED)
-			return RT_HIP_KERNEL_TILED;
-		// up to 8 primitives: at least one sphere, at most three planes (round 4: neither a plane nor a camera whose w varies
-		// over the frame pushes a scene off this kernel any more)
-		// ... through a camera with an eye (`perspective`: the pinhole or the plain eye form; the scalar-register kernels are built for those)
-		// ... and planes whose normals are of ordinary size (device_scene::planes_tame)
-		if (!(flags & RT_HIP_FLAG_FORCE_RESIDENT) && perspective && scene.n_spheres >= 1 && scene.n_planes <= scalar_max_planes && primitives <= scalar_max_spheres && (scene.n_planes == 0 || scene.planes_tame))
-			return RT_HIP_KERNEL_SMALL;
-		// The LDS-resident kernel (one tile per wave) up to streamed_from_primitives (kernels.hpp has the measurements), or whatever
-		// its LDS can hold when forced; beyond that a trip is a long scan and the rolling hand-out of the big-scene kernels wins.
-		const uint32_t staged = (scene.n_spheres < resident_scalar_scan_from ? scene.n_spheres : 0u) + scene.n_planes; // what the resident kernel keeps in LDS
-		// (Scenes beyond its LDS capacity only in frames that fill the device — 4M samples, 64 for every lane it holds: in a small
-		// frame of a big scene every wave is a sparse one, and the streamed kernel scans those with all 64 lanes per ray.)
-		const bool fits = primitives <= resident_max_primitives || (primitives <= streamed_from_primitives && pixels * samples_per_pixel >= (1ull << 22));
-		if (staged <= resident_max_primitives && ((flags & RT_HIP_FLAG_FORCE_RESIDENT) || fits))
-			return RT_HIP_KERNEL_RESIDENT;
-		// Big scenes: the scalar-streamed kernel (no staging, no barriers).  Rounds 1-2 chose the LDS-tiled kernel below
-		// 32 samples per pixel, where it was 2 % ahead; since the group prefetch, the cooperative scan of sparse waves and
-		// the one-sample items the streamed kernel is 10-30 % ahead at every sample count from 1 to 24 and every size from
-		// 1 100 to 100 000 spheres (profiles/r03/tiled_vs_streamed.txt).  The tiled kernel stays behind its flag.
-		(void)samples_per_pixel;
-		return RT_HIP_KERNEL_STREAMED;
-	}
-
-	queue_params choose_queue(uint32_t samples_per_pixel, uint32_t width, uint32_t local_rows, bool big_scene, bool host_frame, int half_chunks, uint32_t primitives, bool sparse_launch)
-	{
-		queue_params q{};
-		q.chunks = (samples_per_pixel + sample_chunk - 1u) / sample_chunk; // K chunks per pixel
-		uint32_t pixels_log2;
-		if (big_scene)
-		{
-			// rolling items: no tiles at all (the fields below describe the frame as 1 x 1 tiles and are not used); a wave
-			// draws 8 items at a time, one block ahead — small enough that a wave sits on at most 15 reserved items when
-			// the sequence runs dry, large enough that the counter sees one atomic per wave every few trips
-			pixels_log2 = 0;
-			q.block_items = 8u;
-			q.lane_cap = 64u;
-			q.sparse_rays = sparse_wave_rays;
-			// Sub-chunk items.  A trip of a big-scene wave costs the same with one lane holding a ray as with 64, and from the
-			// moment the launch-wide sequence runs dry every lane still owes the rest of its item: with whole chunks the
-			// last 10 % of config 5's launch ran on thinning waves (4.9 % of all wave-time after the waves' retirement alone,
-			// profiles/r03/config5_streamed/wave_tail_items_sparse.txt), and its 8-way share — 2.6 chunks per lane — took
-			// twice its share of the time.  Items may be ANY run of consecutive samples if every sample's VALUE is handed
-			// over instead of a chunk's sum (16 bytes per sample through HBM: nothing next to a scan of the scene per path
-			// segment) and the lane that brings a pixel's last item adds them up as the contract says.  How small: every item
-			// costs an arrival (an atomic in HBM: the device does ~0.66 G of them per second, profiles/r03/item_sweep.txt),
-			// which stays in the shadow of the tracing while samples-per-item x primitives >= 8192 — one sample per item from
-			// 8192 primitives upwards, eight at 1025.  Measured: config 5 5.55 -> 5.10 s, its 1/8 share 1203 -> 636 ms;
-			// 30 000 x 64 spp 1756 -> 1616; 10 000 x 32 spp 276 -> 244; 2 000 x 64 spp 96.4 -> 90.5; 1 025 x 64 spp 49.7 -> 47.1.
-			q.item_samples = sample_chunk;
-			if (half_chunks && samples_per_pixel > 1u && primitives)
-			{
-				uint32_t smallest = 1u;
-				while (smallest < sample_chunk && static_cast<uint64_t>(smallest) * primitives < 8192u)
-					smallest *= 2u;
-				// (a sample's slot is 16 bytes: frames whose samples would need more than 8 GiB keep whole chunks)
-				if (static_cast<uint64_t>(width) * local_rows * samples_per_pixel * 16u <= (8ull << 30))
-					q.item_samples = smallest;
-				if (half_chunks == 2 && q.item_samples == sample_chunk)
-					q.item_samples = sample_chunk / 2u;
-#ifdef RT_HIP_QUEUE_KNOBS
-				if (const char* knob = std::getenv("RT_HIP_ITEM_SAMPLES")) // experiment builds only (tools/gpu_item_sweep.py)
-					q.item_samples = static_cast<uint32_t>(std::atoi(knob));
-#endif
-				q.halves = q.item_samples < sample_chunk ? 1u : 0u;
-#ifdef RT_HIP_QUEUE_KNOBS
-				if (const char* knob = std::getenv("RT_HIP_BLOCK_ITEMS"))
-					q.block_items = static_cast<uint32_t>(std::atoi(knob));
-#endif
-			}
-			// Sparse launches of the streamed kernel.  A trip costs one sequential scan of the scene whether the wave holds 64
-			// rays or one; the cooperative scan (scan_spheres_together) costs a wave about 1/40 of that PER RAY.  At the end of a
-			// full launch, where the device is busy, it pays up to 8 rays (sparse_wave_rays: an A/B of round 3); in a launch
-			// that cannot fill the device at all — fewer work items than 32 per wave it can hold — it pays all the way:
-			// the launch is spread THIN, every wave taking at most ceil(items / waves) rays at a time, and scans
-			// cooperatively throughout (profiles/r03/sparse_launch.txt).
-			if (sparse_launch)
-			{
-				constexpr uint64_t launch_waves = 256ull * 4ull * 5ull;
-				const uint64_t items = static_cast<uint64_t>(width) * local_rows * (q.halves ? (samples_per_pixel + q.item_samples - 1u) / q.item_samples : q.chunks);
-				const uint64_t per_wave = (items + launch_waves - 1u) / launch_waves;
-				if (per_wave <= 32u)
-				{
-					q.lane_cap = static_cast<uint32_t>(std::max<uint64_t>(per_wave, 1u));
-					q.block_items = std::min(q.block_items, q.lane_cap);
-					q.sparse_rays = std::max(q.sparse_rays, q.lane_cap);
-				}
-			}
-		}
-		else
-		{
-			// one tile per wave.  A wave lives as long as its longest lane and the launch ends with about one wave lifetime
-			// of tail, so waves should be short — but with fewer than two items per lane the lanes of a wave end at very
-			// different times.  Measured on the headline frame and on its 1/2, 1/4, 1/8 shares at 256, 64 and 16 spp
-			// (profiles/r01/queue_shape_sweep.txt): 128 items per wave, and 64 when that would give fewer than 6 x 8192
-			// waves (8192 = what the device holds at a time), win or tie every case.
-			pixels_log2 = 7; // 128 pixels = 16 x 8
-			while (pixels_log2 > 2 && (q.chunks << pixels_log2) > 128u)
-				pixels_log2--;
-			const uint64_t pixels = static_cast<uint64_t>(width) * local_rows;
-			if (pixels_log2 > 2 && (pixels >> pixels_log2) < 49152u)
-				pixels_log2--;
-		}
-		// Half-chunks (render_queue<.., HALF>): a launch that has only a few chunks per lane of the device ends unevenly —
-		// a rank's 1/8 share of a 64-spp frame holds two per lane and took 0.21 ms for 0.09 ms of work; with 8-sample items
-		// 0.13-0.14 (profiles/r03/chunk_probe.txt: 1/4 share -11 %, nothing from eight chunks per lane upwards, where the
-		// parking would only cost).  64 half-chunks per wave, one per lane; tiles of at least four pixels.
-		// (Not for pixels of ONE chunk, forced aside: their tiles would hold half as many pixels and the wave's fold — a
-		// division and three square roots per pixel — runs on half its lanes: 1080p x 16 spp 0.345 against 0.323 ms.  Between
-		// four and seven chunks per lane the gain fades: 800 x 600 x 64 spp -16 %, 1280 x 720 x 64 spp +16 %;
-		// profiles/r03/half_threshold.txt.)
-		if (half_chunks && !big_scene && samples_per_pixel > sample_chunk / 2u && q.chunks <= 16u)
-		{
-			constexpr uint64_t resident_lanes = 256ull * 4ull * 8ull * 64ull; // an MI355X at 8 waves per SIMD
-			if (half_chunks == 2 || (q.chunks >= 2u && static_cast<uint64_t>(width) * local_rows * q.chunks < 5ull * resident_lanes))
-			{
-				q.halves = 1u;
-				pixels_log2 = 2u;
-				while (pixels_log2 < 7u && ((2u * q.chunks) << (pixels_log2 + 1u)) <= 64u)
-					pixels_log2++;
-			}
-		}
-		// frames of headline size and beyond at 256 spp: 16 pixels (256 items) per wave beat 8 — half as many waves to start
-		// and to fold (HBM: 2.62 against 2.63 ms at 1080p, 10.4 against 10.6 at 4K; profiles/r03/tile_shapes.txt) — while a
-		// half frame still prefers 8 (1.39 against 1.34)
-		if (!big_scene && !q.halves && pixels_log2 == 3u && (q.chunks << 4u) <= 256u && ((static_cast<uint64_t>(width) * local_rows) >> 4u) >= 98304u)
-			pixels_log2 = 4u;
-		q.pixels_log2 = pixels_log2;
-		q.tile_w_log2 = (pixels_log2 + 1u) / 2u; // 16x8, 8x8, 8x4, 4x4, 4x2, 2x2, 2x1, 1x1
-		if (host_frame && !big_scene && q.halves)
-			q.tile_w_log2 = std::min(pixels_log2, 4u); // (rows as wide as the tile allows: see below)
-		else if (host_frame && !big_scene)
-		{
-			// The finished pixels of a tile leave the wave as one store per tile, a row fragment of tile_w pixels per tile
-			// row; into page-locked host memory every fragment is a PCIe write.  Fragments of 8 and 16 bytes (2 x 2, 4 x 4,
-			// 4 x 2 tiles) cost nothing in HBM and a lot over PCIe as soon as there are many of them per microsecond — a 1/8
-			// share of the headline frame took 0.60 ms as 2 x 2 tiles against 0.35 ms into HBM, 0.37 ms as 4 x 1; config 2's
-			// whole frame 1.36 ms into memory of the other socket as 8 x 4, 0.86 ms as 16 x 2 — and so does memory on the far
-			// socket (profiles/r03/tile_shapes.txt).  So: rows as wide as the tile allows, up to 64 bytes.  One exception,
-			// where the launch has waves to spare: 256-spp frames of headline size take 16 pixels as 8 x 2 instead of 8 as
-			// 8 x 1 (half as many store instructions: as fast as the frame left in HBM whichever socket the memory is on).
-			const uint64_t pixels = static_cast<uint64_t>(width) * local_rows;
-			if (pixels_log2 == 3u && (q.chunks << 4u) <= 256u && (pixels >> 4u) >= 49152u)
-				q.pixels_log2 = pixels_log2 = 4u;
-			// (16 pixels at 256 spp: 8 x 2 for the 1..4-sphere kernels — basic.toml 2.639 against 2.664 ms as 16 x 1 — and 16 x 1
-			// for the 5..8-sphere and the resident ones — dielectric.toml 3.011 against 3.040 as 8 x 2; tile_sweep_drop_in.txt)
-			q.tile_w_log2 = (pixels_log2 == 4u && q.chunks == 16u && primitives < 5u) ? 3u : std::min(pixels_log2, 4u);
-		}
-#ifdef RT_HIP_QUEUE_KNOBS
-		// experiment builds only (tools/gpu_tile_shapes.py): tile size and width from the environment, per launch
-		if (!big_scene)
-		{
-			if (const char* knob = std::getenv("RT_HIP_TILE_LOG2"))
-				q.pixels_log2 = pixels_log2 = static_cast<uint32_t>(std::atoi(knob));
-			q.tile_w_log2 = (pixels_log2 + 1u) / 2u;
-			if (const char* knob = std::getenv("RT_HIP_TILE_W_LOG2"))
-				q.tile_w_log2 = std::min<uint32_t>(static_cast<uint32_t>(std::atoi(knob)), pixels_log2);
-		}
-#endif
-		const uint32_t tile_w = 1u << q.tile_w_log2, tile_h = (1u << pixels_log2) >> q.tile_w_log2;
-		q.tiles_x = (width + tile_w - 1u) / tile_w;
-		q.tiles_y = (local_rows + tile_h - 1u) / tile_h;
-		return q;
-	}
-
-	void rolling_buffer_bytes(const queue_params& queue, uint32_t samples_per_pixel, uint32_t width, uint32_t local_rows, bool big_scene, size_t& item_sums_bytes, size_t& pixel_done_bytes)
-	{
-		item_sums_bytes = pixel_done_bytes = 0;
-		if (!big_scene || (queue.chunks <= 1u && !queue.halves)) // one chunk per pixel: the lane that traced it writes the pixel
-			return;
-		const size_t pixels = static_cast<size_t>(width) * local_rows;
-		item_sums_bytes = queue.halves ? pixels * samples_per_pixel * 16u : pixels * queue.chunks * 16u;
-		pixel_done_bytes = pixels * sizeof(uint32_t);
-	}
-
-#endif // !RT_HIP_FAST_BUILD
-
+	// picks the instantiation plan.build names and launches it: every decision is the plan's (launch_plan.hpp)
 	uint32_t launch_render(const frame_params& frame,
 						   const device_scene& scene,
 						   const small_scene& small,
-						   uint32_t flags,
+						   const launch_plan& plan,
 						   uint32_t* d_rgba8,
 						   float* d_rgb_f32,
 						   device_counters* d_counters,
@@ -1820,29 +1628,15 @@ namespace rt_hip
 						   launch_cache& cache,
 						   hipStream_t stream)
 	{
-		if (!frame.width || !frame.local_rows)
+		if (plan.variant == RT_HIP_KERNEL_NONE)
 			return RT_HIP_KERNEL_NONE;
-		const uint32_t variant = choose_kernel(scene, flags, frame.samples_per_pixel, frame.pinhole != 0 || frame.eye_form == 2u, static_cast<uint64_t>(frame.width) * frame.local_rows);
-		const bool sm = (flags & RT_HIP_FLAG_SM_MATERIALS) != 0;
-		const bool big_scene = variant == RT_HIP_KERNEL_TILED || variant == RT_HIP_KERNEL_STREAMED;
-		const queue_params queue = choose_queue(frame.samples_per_pixel, frame.width, frame.local_rows, big_scene, (flags & launch_flag_host_frame) != 0u, half_chunk_choice(flags), scene.n_spheres + scene.n_planes,
-												variant == RT_HIP_KERNEL_STREAMED && scene.n_spheres >= sparse_launch_min_spheres);
-
-		// small scenes: one wave per tile, four tiles side by side per workgroup.  Big scenes: a persistent launch — what
-		// the device keeps resident, and no more lanes than items
-		const uint64_t total_items = static_cast<uint64_t>(frame.width) * frame.local_rows * ((big_scene && queue.halves) ? (frame.samples_per_pixel + queue.item_samples - 1u) / queue.item_samples : queue.chunks);
-		const uint64_t items_per_workgroup = big_scene ? static_cast<uint64_t>(block_threads / 64u) * queue.lane_cap : block_threads; // (a sparse launch: lane_cap rays per wave)
-		const dim3 grid = big_scene ? dim3(static_cast<uint32_t>(std::min<uint64_t>(0x7FFFFFFFull, (total_items + items_per_workgroup - 1u) / items_per_workgroup))) // capped to the resident count at launch
-									: dim3((queue.tiles_x + 3u) / 4u, queue.tiles_y);
-		const size_t slot_bytes = big_scene ? 0u : static_cast<size_t>(block_threads / 64u) * tile_slot_bytes(queue);
-		if (variant == RT_HIP_KERNEL_SMALL)
+		const launch_arguments a = { frame, scene, small, plan, d_rgba8, d_rgb_f32, d_counters, rolling, compute_units, cache, stream };
+		const kernel_build& build = plan.build;
+		if (build.scan > 0) // the scalar-register kernels: build.scan spheres, then build.planes planes
 		{
-			const size_t lds_bytes = small_table_float4s * sizeof(float4) + slot_bytes;
-#define RT_HIP_LAUNCH_SMALL(N, P)                                                                                                    \
-	(frame.pinhole ? launch_queue<N, P, false>(sm, frame, queue, small, scene, grid, lds_bytes, d_rgba8, d_rgb_f32, d_counters, rolling, compute_units, cache, stream)  \
-					 : launch_queue<N, P, true>(sm, frame, queue, small, scene, grid, lds_bytes, d_rgba8, d_rgb_f32, d_counters, rolling, compute_units, cache, stream))
+#define RT_HIP_LAUNCH_SMALL(N, P) (build.general_camera ? launch_queue<N, P, true>(a) : launch_queue<N, P, false>(a))
 #define RT_HIP_LAUNCH_SMALL_SPHERES(P, N_MAX)                                                                                        \
-	switch (scene.n_spheres)                                                                                                         \
+	switch (build.scan)                                                                                                              \
 	{                                                                                                                                \
 		case 1: RT_HIP_LAUNCH_SMALL(1, P); break;                                                                                    \
 		case 2: RT_HIP_LAUNCH_SMALL(2, P); break;                                                                                    \
@@ -1853,7 +1647,7 @@ namespace rt_hip
 		case 7: if constexpr (N_MAX >= 7) RT_HIP_LAUNCH_SMALL(7, P); break;                                                          \
 		default: if constexpr (N_MAX >= 8) RT_HIP_LAUNCH_SMALL(8, P); break;                                                         \
 	}
-			switch (scene.n_planes) // (choose_kernel admits n_spheres + n_planes <= 8 only)
+			switch (build.planes) // (choose_kernel admits n_spheres + n_planes <= 8 only)
 			{
 				case 0: RT_HIP_LAUNCH_SMALL_SPHERES(0, 8); break;
 				case 1: RT_HIP_LAUNCH_SMALL_SPHERES(1, 7); break;
@@ -1862,39 +1656,26 @@ namespace rt_hip
 			}
 #undef RT_HIP_LAUNCH_SMALL_SPHERES
 #undef RT_HIP_LAUNCH_SMALL
-			return variant;
+			return plan.variant;
 		}
+		switch (build.scan)
+		{
 #ifndef RT_HIP_FAST_BUILD // (the API refuses RT_HIP_FLAG_FAST together with RT_HIP_FLAG_BVH)
-		if (variant == RT_HIP_KERNEL_BVH)
-		{
-			launch_queue<-4>(sm, frame, queue, small, scene, grid, bvh_stack_float4s * sizeof(float4) + slot_bytes, d_rgba8, d_rgb_f32, d_counters, rolling, compute_units, cache, stream);
-			return variant;
-		}
+			case scan_bvh: launch_queue<scan_bvh>(a); break;
 #endif
-		if (variant == RT_HIP_KERNEL_RESIDENT)
-		{
-			const size_t lds_bytes = static_cast<size_t>((scene.n_spheres < resident_scalar_scan_from ? scene.n_spheres : 0u) + scene.n_planes) * sizeof(float4) + slot_bytes;
-			if (scene.n_spheres >= resident_scalar_scan_from) // (the scalar-load scan: one build for every camera form)
-				launch_queue<0, 1, false>(sm, frame, queue, small, scene, grid, lds_bytes, d_rgba8, d_rgb_f32, d_counters, rolling, compute_units, cache, stream);
-			else if (frame.pinhole)
-				launch_queue<0, 0, false>(sm, frame, queue, small, scene, grid, lds_bytes, d_rgba8, d_rgb_f32, d_counters, rolling, compute_units, cache, stream);
-			else
-				launch_queue<0, 0, true>(sm, frame, queue, small, scene, grid, lds_bytes, d_rgba8, d_rgb_f32, d_counters, rolling, compute_units, cache, stream);
-			return variant;
+			case scan_resident:
+				if (build.planes) // (the scalar-load scan: one build for every camera form)
+					launch_queue<scan_resident, 1, false>(a);
+				else if (build.general_camera)
+					launch_queue<scan_resident, 0, true>(a);
+				else
+					launch_queue<scan_resident, 0, false>(a);
+				break;
+			case scan_streamed_dense: launch_queue<scan_streamed_dense>(a); break;
+			case scan_streamed: launch_queue<scan_streamed>(a); break;
+			default: launch_queue<scan_tiled>(a); break;
 		}
-		if (variant == RT_HIP_KERNEL_STREAMED)
-		{
-			// A frame that fills the device — not a thin launch, and at least 4M samples — takes the build without the cooperative scan of
-			// sparse waves: only its last waves run sparse, and the registers that scan costs every other trip are worth 9 % (config 5).
-			const bool dense = queue.lane_cap == 64u && static_cast<uint64_t>(frame.width) * frame.local_rows * frame.samples_per_pixel >= (1ull << 22);
-			if (dense)
-				launch_queue<-3>(sm, frame, queue, small, scene, grid, 0, d_rgba8, d_rgb_f32, d_counters, rolling, compute_units, cache, stream);
-			else
-				launch_queue<-2>(sm, frame, queue, small, scene, grid, 0, d_rgba8, d_rgb_f32, d_counters, rolling, compute_units, cache, stream);
-			return variant;
-		}
-		launch_queue<-1>(sm, frame, queue, small, scene, grid, tile_primitives * sizeof(float4), d_rgba8, d_rgb_f32, d_counters, rolling, compute_units, cache, stream);
-		return variant;
+		return plan.variant;
 	}
 
 #ifndef RT_HIP_FAST_BUILD

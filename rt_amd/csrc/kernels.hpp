@@ -3,7 +3,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "../../include/rt_hip.h" // (the render flags: half_chunk_choice)
+#include "launch_plan.hpp" // (the launch policy: queue_params, the thresholds, launch_plan)
 
 namespace rt_hip
 {
@@ -117,59 +117,13 @@ namespace rt_hip
 	};
 
 	// the whole scene of the `small` kernel, passed by value as a kernel argument (-> SGPRs); host copy kept by the context
-	constexpr uint32_t scalar_max_spheres = 8; // scenes of up to this many primitives (spheres + planes) run with the scene in SGPRs
-	constexpr uint32_t scalar_max_planes = 3;  // ... of which at most this many planes (and at least one sphere)
+	// (scalar_max_spheres: launch_plan.hpp)
 	struct small_scene
 	{
 		float4 geometry[scalar_max_spheres]; // spheres (center, radius^2), then planes (normal, d)
 		float4 shading[scalar_max_spheres];	 // (attenuation.rgb, roughness or index of refraction) of the primitive's material
 		uint32_t scatter[scalar_max_spheres]; // scatter_*
 	};
-
-	// pixel sums are taken in chunks of this many consecutive samples (arithmetic contract; see oracle/cpu_ref.cpp)
-#ifdef RT_HIP_SAMPLE_CHUNK // (timing experiments only: frames of such a build are not the contract's)
-	constexpr uint32_t sample_chunk = RT_HIP_SAMPLE_CHUNK;
-#else
-	constexpr uint32_t sample_chunk = 16;
-#endif
-
-	// Work distribution.  The unit of work is one ITEM = one chunk of 16 consecutive samples of one pixel (K = chunks per
-	// pixel).  Small scenes: the frame is cut into pixel tiles of P = 2^pixels_log2 pixels, one tile (P x K items) per wave,
-	// launched as a grid of tiles.  Big scenes (tiled / streamed kernels): a persistent launch whose waves draw single
-	// items, in blocks of `block_items`, from one launch-wide sequence (device_counters::next_item), pixel-major, bottom
-	// row first; a pixel's chunk sums meet in HBM (rolling_buffers).
-	struct queue_params
-	{
-		uint32_t chunks;		   // K = ceil(spp / sample_chunk)
-		uint32_t pixels_log2;	   // P (small scenes)
-		uint32_t tile_w_log2;	   // a tile is 2^tile_w_log2 columns wide
-		uint32_t tiles_x, tiles_y; // tiles across / down this rank's rows
-		uint32_t block_items;	   // big scenes: items a wave draws from the launch-wide sequence at a time
-		uint32_t lane_cap;		   // big scenes: rays a wave holds at most (64 = all lanes; less in sparse launches of the streamed kernel)
-		uint32_t sparse_rays;	   // streamed kernel: a wave holding at most this many rays scans cooperatively
-		uint32_t halves;		   // short launches: 1 = the work items are smaller than a chunk (render_queue<.., HALF>): small scenes
-								   // half chunks; big scenes item_samples consecutive samples, every sample's value parked
-		uint32_t item_samples;	   // big scenes with halves: samples per work item (8, 4, 2 or 1)
-	};
-	// LDS floats per chunk of a tile: its sum — or, with half-chunks, the first half's partial sum and the second half's 8 x 3 sample values
-	constexpr uint32_t half_chunk_slot_floats = 3u + 3u * (sample_chunk / 2u);
-	inline size_t tile_slot_bytes(const queue_params& q) // of ONE wave's tile
-	{
-		return static_cast<size_t>(q.chunks << q.pixels_log2) * (q.halves ? half_chunk_slot_floats : 3u) * sizeof(float);
-	}
-	// `host_frame`: the packed pixels go to page-locked HOST memory (every row fragment of a tile is a PCIe write)
-	// `half_chunks`: 0 = whole chunks (the sm table's kernels have no half-chunk build; RT_HIP_FLAG_FORCE_WHOLE_CHUNKS),
-	// 1 = by the size of the launch, 2 = half chunks wherever the samples allow (RT_HIP_FLAG_FORCE_HALF_CHUNKS)
-	queue_params choose_queue(uint32_t samples_per_pixel, uint32_t width, uint32_t local_rows, bool big_scene, bool host_frame, int half_chunks, uint32_t primitives, bool sparse_launch);
-	constexpr uint32_t sparse_launch_min_spheres = 1024; // the streamed kernel's cooperative scan (a wave with a handful of rays) exists from here
-	inline int half_chunk_choice(uint32_t flags)
-	{
-		if (flags & (RT_HIP_FLAG_SM_MATERIALS | RT_HIP_FLAG_FORCE_WHOLE_CHUNKS))
-			return 0;
-		return (flags & RT_HIP_FLAG_FORCE_HALF_CHUNKS) ? 2 : 1;
-	}
-	// internal launch flag, or-ed into the render flags by the callers of launch_render / launch_render_fast: see choose_queue
-	constexpr uint32_t launch_flag_host_frame = 1u << 31;
 
 	// What the big-scene kernels exchange chunk sums through (owned by the context, grown on demand):
 	//   item_sums   16 bytes per item of this rank's rows (a chunk sum on its way to the lane that folds the pixel);
@@ -183,8 +137,6 @@ namespace rt_hip
 		// the item_sums argument's place (render_queue), so that no kernel's argument block changes.
 		const device_bvh* bvh = nullptr;
 	};
-	// bytes of the two buffers for a launch (0, 0 for the small-scene kernels)
-	void rolling_buffer_bytes(const queue_params& queue, uint32_t samples_per_pixel, uint32_t width, uint32_t local_rows, bool big_scene, size_t& item_sums_bytes, size_t& pixel_done_bytes);
 
 	struct device_counters
 	{
@@ -210,22 +162,6 @@ namespace rt_hip
 #endif
 	};
 
-#ifndef RT_HIP_RESIDENT_SCALAR_FROM
-#define RT_HIP_RESIDENT_SCALAR_FROM 40
-#endif
-	constexpr uint32_t resident_scalar_scan_from = RT_HIP_RESIDENT_SCALAR_FROM; // spheres from which the resident kernel scans through the scalar cache (kernels.hip)
-	constexpr uint32_t resident_max_primitives = 1024; // what the resident kernel keeps in LDS at most: the planes, and the spheres of a scene below resident_scalar_scan_from
-	// The launch code prefers the resident kernel (a pixel tile per wave) up to this many primitives, the streamed kernel's rolling
-	// items beyond.  From resident_scalar_scan_from spheres on the resident kernel reads the sphere table in memory, as the streamed
-	// kernel does, and its LDS holds planes only — so its capacity is no limit to the spheres; what ends its lead is that a tile's
-	// lanes run dry one by one while a trip costs the wave a whole scan.  Against the streamed kernel's build for dense frames
-	// (1080p x 64 spp, kernel ms): 400 spheres 16.8 against 18.4, 700: 29.7 against 31.0, 1 000: 42.9 against 44.9, 1 100: 47.8 against
-	// 48.4, 1 500: 66.5 against 65.8, 2 000: 90.3 against 87.9, 3 000: 141.8 against 130.7 (profiles/r05/resident_vs_dense_streamed.txt;
-	// against the streamed kernel as it was before that build the lead lasted to 4 000 spheres: resident_beyond_1024_ab.txt).
-	constexpr uint32_t streamed_from_primitives = 1300;
-	constexpr uint32_t bvh_stack_float4s = 24u * 256u / 4u; // the BVH kernel's LDS traversal stacks: bvh_max_depth words per thread (bvh.hpp, kernels.hip)
-	constexpr uint32_t tile_primitives = 1024;		   // primitives per LDS tile in the tiled kernel
-
 	// what a context remembers between launches: workgroups per CU that stay resident, for the persistent (big-scene) kernels
 	struct launch_cache
 	{
@@ -234,28 +170,19 @@ namespace rt_hip
 			size_t lds_bytes = 0;
 			int per_cu = 0;
 		};
-		entry persistent[18]; // { tiled, streamed, streamed for dense frames } x { mg, sm scatter table, fast arithmetic } x { whole chunks, sub-chunk items }
-		// one definition for both builds of kernels.hip (the parity contract and RT_HIP_FAST_BUILD), which are linked into
-		// one library: the build says which arithmetic it is through the argument (the fast build has no sm scatter table)
-		static constexpr unsigned slot(unsigned kernel /* 0 tiled, 1 streamed, 2 streamed for dense frames */, bool sm, bool fast_arithmetic, bool sub_chunk_items)
-		{
-			return (sub_chunk_items ? 9u : 0u) + 3u * kernel + (fast_arithmetic ? 2u : (sm ? 1u : 0u));
-		}
+		entry persistent[persistent_cache_slots]; // indexed by launch_plan::persistent_slot
 	};
 
-	// which kernel launch_render would pick (RT_HIP_KERNEL_*)
-	uint32_t choose_kernel(const device_scene& scene, uint32_t flags, uint32_t samples_per_pixel, bool perspective /* the frame's camera is a pinhole or a plain eye-form one: frame_params::pinhole or eye_form == 2 */,
-						   uint64_t pixels /* of this rank's rows */);
-
-	// returns the kernel variant launched (RT_HIP_KERNEL_*)
+	// launches what `plan` says (plan_launch, made by the caller, who has prepared the buffers from the same plan); returns the
+	// kernel variant launched (RT_HIP_KERNEL_*)
 	uint32_t launch_render(const frame_params& frame,
 						   const device_scene& scene,
-						   const small_scene& small, // valid when choose_kernel() says RT_HIP_KERNEL_SMALL; tables already chosen by flag
-						   uint32_t flags,
+						   const small_scene& small, // valid when the plan's variant is RT_HIP_KERNEL_SMALL; tables already chosen by flag
+						   const launch_plan& plan,
 						   uint32_t* d_rgba8,
 						   float* d_rgb_f32,
 						   device_counters* d_counters,
-						   const rolling_buffers& rolling, // big scenes: sized by rolling_buffer_bytes(), pixel_done zeroed in front of the launch
+						   const rolling_buffers& rolling, // big scenes: sized as the plan says, pixel_done zeroed in front of the launch
 						   uint32_t compute_units, // of the device: the big-scene kernels are launched persistent
 						   launch_cache& cache,
 						   hipStream_t stream);
@@ -264,7 +191,7 @@ namespace rt_hip
 	uint32_t launch_render_fast(const frame_params& frame,
 								const device_scene& scene,
 								const small_scene& small,
-								uint32_t flags,
+								const launch_plan& plan,
 								uint32_t* d_rgba8,
 								float* d_rgb_f32,
 								device_counters* d_counters,

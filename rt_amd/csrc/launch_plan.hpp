@@ -1,0 +1,160 @@
+// rt_amd/csrc/launch_plan.hpp — every host decision of one render launch, made ONCE (plan_launch): which kernel, which build of
+// it, the shape of its work, its grid and LDS, the HBM buffers it needs.  render.hip plans a launch, prepares what the plan asks
+// for and hands the same plan to launch_render (kernels.hip), which only picks the instantiation and launches it.
+// Host-only integer policy with the measurements that justify it: plain C++17, no HIP header, built with the host compiler into
+// librt_hip.so and, on the CPU, into tests/native/launch_plan_dump (tests/test_launch_plan.py pins every decision).
+#pragma once
+
+#include <stdint.h>
+#include <stddef.h>
+#include "../../include/rt_hip.h" // (the render flags and RT_HIP_KERNEL_*)
+
+// waves per SIMD the streamed kernel of frames that fill the device is compiled for (scan_streamed_dense: no cooperative scan of sparse
+// waves, whose four 16-byte loads in flight per lane set the register count of the other build): 80 registers hold its loop, half-chunk
+// items included — config 5 5.47 s at 5 waves WITH the cooperative scan, 5.09 without, 4.99 at 6 waves, 5.05 at 7
+// (profiles/r05/streamed_occupancy_ab.txt)
+#ifndef RT_HIP_WAVES_DENSE
+#define RT_HIP_WAVES_DENSE 6
+#endif
+#ifndef RT_HIP_PERSISTENT_WAVES_CAP
+#define RT_HIP_PERSISTENT_WAVES_CAP 5 // workgroups per CU of the persistent (big-scene) launches: see launch_queue_sm
+#endif
+
+namespace rt_hip
+{
+	constexpr uint32_t block_threads = 256; // a workgroup of the render kernels: 4 waves
+
+	// the whole scene of the `small` kernel is passed by value as a kernel argument (-> SGPRs): small_scene, kernels.hpp
+	constexpr uint32_t scalar_max_spheres = 8; // scenes of up to this many primitives (spheres + planes) run with the scene in SGPRs
+	constexpr uint32_t scalar_max_planes = 3;  // ... of which at most this many planes (and at least one sphere)
+	constexpr uint32_t small_table_float4s = 2u * scalar_max_spheres; // LDS tables of the scalar-register kernels: geometry, shading
+
+	// pixel sums are taken in chunks of this many consecutive samples (arithmetic contract; see oracle/cpu_ref.cpp)
+#ifdef RT_HIP_SAMPLE_CHUNK // (timing experiments only: frames of such a build are not the contract's)
+	constexpr uint32_t sample_chunk = RT_HIP_SAMPLE_CHUNK;
+#else
+	constexpr uint32_t sample_chunk = 16;
+#endif
+
+	// Work distribution.  The unit of work is one ITEM = one chunk of 16 consecutive samples of one pixel (K = chunks per
+	// pixel).  Small scenes: the frame is cut into pixel tiles of P = 2^pixels_log2 pixels, one tile (P x K items) per wave,
+	// launched as a grid of tiles.  Big scenes (tiled / streamed kernels): a persistent launch whose waves draw single
+	// items, in blocks of `block_items`, from one launch-wide sequence (device_counters::next_item), pixel-major, bottom
+	// row first; a pixel's chunk sums meet in HBM (rolling_buffers).
+	struct queue_params
+	{
+		uint32_t chunks;		   // K = ceil(spp / sample_chunk)
+		uint32_t pixels_log2;	   // P (small scenes)
+		uint32_t tile_w_log2;	   // a tile is 2^tile_w_log2 columns wide
+		uint32_t tiles_x, tiles_y; // tiles across / down this rank's rows
+		uint32_t block_items;	   // big scenes: items a wave draws from the launch-wide sequence at a time
+		uint32_t lane_cap;		   // big scenes: rays a wave holds at most (64 = all lanes; less in sparse launches of the streamed kernel)
+		uint32_t sparse_rays;	   // streamed kernel: a wave holding at most this many rays scans cooperatively
+		uint32_t halves;		   // short launches: 1 = the work items are smaller than a chunk (render_queue<.., HALF>): small scenes
+								   // half chunks; big scenes item_samples consecutive samples, every sample's value parked
+		uint32_t item_samples;	   // big scenes with halves: samples per work item (8, 4, 2 or 1)
+	};
+	// LDS floats per chunk of a tile: its sum — or, with half-chunks, the first half's partial sum and the second half's 8 x 3 sample values
+	constexpr uint32_t half_chunk_slot_floats = 3u + 3u * (sample_chunk / 2u);
+	inline size_t tile_slot_bytes(const queue_params& q) // of ONE wave's tile
+	{
+		return static_cast<size_t>(q.chunks << q.pixels_log2) * (q.halves ? half_chunk_slot_floats : 3u) * sizeof(float);
+	}
+	// `host_frame`: the packed pixels go to page-locked HOST memory (every row fragment of a tile is a PCIe write)
+	// `half_chunks`: 0 = whole chunks (the sm table's kernels have no half-chunk build; RT_HIP_FLAG_FORCE_WHOLE_CHUNKS),
+	// 1 = by the size of the launch, 2 = half chunks wherever the samples allow (RT_HIP_FLAG_FORCE_HALF_CHUNKS)
+	queue_params choose_queue(uint32_t samples_per_pixel, uint32_t width, uint32_t local_rows, bool big_scene, bool host_frame, int half_chunks, uint32_t primitives, bool sparse_launch);
+	constexpr uint32_t sparse_wave_rays = 8;			 // (streamed kernel) a wave holding at most this many rays scans together
+	constexpr uint32_t sparse_launch_min_spheres = 1024; // the streamed kernel's cooperative scan (a wave with a handful of rays) exists from here
+	inline int half_chunk_choice(uint32_t flags)
+	{
+		if (flags & (RT_HIP_FLAG_SM_MATERIALS | RT_HIP_FLAG_FORCE_WHOLE_CHUNKS))
+			return 0;
+		return (flags & RT_HIP_FLAG_FORCE_HALF_CHUNKS) ? 2 : 1;
+	}
+
+	// bytes of the two buffers the big-scene kernels exchange chunk sums through (rolling_buffers, kernels.hpp) for a launch
+	// (0, 0 for the small-scene kernels)
+	void rolling_buffer_bytes(const queue_params& queue, uint32_t samples_per_pixel, uint32_t width, uint32_t local_rows, bool big_scene, size_t& item_sums_bytes, size_t& pixel_done_bytes);
+
+#ifndef RT_HIP_RESIDENT_SCALAR_FROM
+#define RT_HIP_RESIDENT_SCALAR_FROM 40
+#endif
+	constexpr uint32_t resident_scalar_scan_from = RT_HIP_RESIDENT_SCALAR_FROM; // spheres from which the resident kernel scans through the scalar cache (kernels.hip)
+	constexpr uint32_t resident_max_primitives = 1024; // what the resident kernel keeps in LDS at most: the planes, and the spheres of a scene below resident_scalar_scan_from
+	// The launch code prefers the resident kernel (a pixel tile per wave) up to this many primitives, the streamed kernel's rolling
+	// items beyond.  From resident_scalar_scan_from spheres on the resident kernel reads the sphere table in memory, as the streamed
+	// kernel does, and its LDS holds planes only — so its capacity is no limit to the spheres; what ends its lead is that a tile's
+	// lanes run dry one by one while a trip costs the wave a whole scan.  Against the streamed kernel's build for dense frames
+	// (1080p x 64 spp, kernel ms): 400 spheres 16.8 against 18.4, 700: 29.7 against 31.0, 1 000: 42.9 against 44.9, 1 100: 47.8 against
+	// 48.4, 1 500: 66.5 against 65.8, 2 000: 90.3 against 87.9, 3 000: 141.8 against 130.7 (profiles/r05/resident_vs_dense_streamed.txt;
+	// against the streamed kernel as it was before that build the lead lasted to 4 000 spheres: resident_beyond_1024_ab.txt).
+	constexpr uint32_t streamed_from_primitives = 1300;
+	constexpr uint32_t bvh_stack_float4s = 24u * 256u / 4u; // the BVH kernel's LDS traversal stacks: bvh_max_depth words per thread (bvh.hpp, kernels.hip)
+	constexpr uint32_t tile_primitives = 1024;		   // primitives per LDS tile in the tiled kernel
+
+	// which kernel a launch takes (RT_HIP_KERNEL_*)
+	uint32_t choose_kernel(uint32_t n_spheres, uint32_t n_planes, bool planes_tame /* device_scene::planes_tame */, uint32_t flags, uint32_t samples_per_pixel,
+						   bool perspective /* the frame's camera is a pinhole or a plain eye-form one: frame_params::pinhole or eye_form == 2 */, uint64_t pixels /* of this rank's rows */);
+
+	// The scan a build of render_queue<NS, ..> is compiled for, as its first template argument says it: NS > 0 is the `small`
+	// kernel with NS spheres in scalar registers; the other kernels have these codes (kernels.hip, render_queue).
+	enum : int
+	{
+		scan_resident = 0,		  // all primitives in LDS — or, NP == 1, the planes in LDS and the spheres through scalar loads
+		scan_tiled = -1,		  // rolling items; the primitives stream through one LDS tile per workgroup
+		scan_streamed = -2,		  // rolling items; wave-uniform scalar loads, sparse waves scan cooperatively
+		scan_streamed_dense = -3, // ... without the cooperative scan: frames that fill the device
+		scan_bvh = -4			  // RT_HIP_FLAG_BVH: a pixel tile per wave, spheres through the hierarchy
+	};
+	// the rolling kernels are launched persistent: as many workgroups as the device keeps resident (launch_cache, kernels.hpp)
+	constexpr bool scan_is_persistent(int scan) { return scan == scan_tiled || scan == scan_streamed || scan == scan_streamed_dense; }
+	constexpr unsigned persistent_cache_slots = 18; // { tiled, streamed, streamed for dense frames } x { mg, sm scatter table, fast arithmetic } x { whole chunks, sub-chunk items }
+
+	enum class camera_form : uint32_t
+	{
+		pinhole,   // frame_params::pinhole
+		plain_eye, // frame_params::eye_form == 2
+		other	   // an eye form that needs its guards, or the homogeneous form
+	};
+
+	// what a launch is planned from
+	struct launch_request
+	{
+		uint32_t n_spheres, n_planes;
+		bool planes_tame; // device_scene::planes_tame
+		uint32_t width, local_rows, samples_per_pixel; // this rank's rows of the frame
+		camera_form camera;
+		uint32_t flags;		  // RT_HIP_FLAG_*
+		bool host_frame;	  // the packed pixels go to page-locked host memory (choose_queue)
+		bool fast_arithmetic; // RT_HIP_FLAG_FAST's build of the kernels (launch_render_fast)
+	};
+
+	// the instantiation render_queue<scan, sm_table, sub_chunk_items, planes, general_camera>
+	struct kernel_build
+	{
+		int scan;			  // NS: the spheres of a scalar-register kernel, or scan_*
+		int planes;			  // NP: the planes of a scalar-register kernel; scan_resident: 1 = the scalar-load scan
+		bool general_camera;  // GC: the frame is not a pinhole's (scalar-register kernels and the resident LDS scan)
+		bool sub_chunk_items; // HALF
+		bool sm_table;		  // SM: RT_HIP_FLAG_SM_MATERIALS
+	};
+
+	struct launch_plan
+	{
+		uint32_t variant; // RT_HIP_KERNEL_*; RT_HIP_KERNEL_NONE for a frame without pixels: nothing is launched (the other fields
+						  // are still those of the kernel the scene would take)
+		bool big_scene;	  // a rolling kernel (tiled / streamed): items drawn from device_counters::next_item, which must start at 0
+		queue_params queue;
+		kernel_build build;
+		uint32_t grid_x, grid_y; // workgroups; a persistent launch is capped to what the device keeps resident at launch (launch_queue_sm)
+		size_t table_bytes;		 // LDS: the primitive tables / the tiled kernel's tile / the BVH kernel's stacks ...
+		size_t slot_bytes;		 // ... and the chunk-sum slots of the workgroup's four tiles (small scenes)
+		size_t lds_bytes;		 // = table_bytes + slot_bytes
+		uint64_t total_items;
+		size_t item_sums_bytes, pixel_done_bytes; // rolling_buffer_bytes
+		int persistent_slot; // index into launch_cache::persistent, or -1: not a persistent launch
+		int per_cu_cap;		 // persistent launches: workgroups per CU at most
+	};
+	launch_plan plan_launch(const launch_request& request);
+}

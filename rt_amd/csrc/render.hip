@@ -201,42 +201,40 @@ rt_hip_status render_device(rt_hip_ctx* ctx, uint32_t width, uint32_t height, ui
 		}
 	}
 
-	bool rolling_items = false; // the persistent big-scene kernels draw items from a sequence whose head must start at 0
+	// every decision of the launch is made here, once: the buffers below are prepared from the plan the launch code then follows
+	launch_plan plan{}; // (the preview: nothing to plan)
 	rolling_buffers rolling;
 	rolling.bvh = bvh;
 	if (!(flags & RT_HIP_FLAG_PREVIEW))
 	{
-		const uint32_t variant = choose_kernel(ctx->scene, flags, f.samples_per_pixel, f.pinhole != 0 || f.eye_form == 2u, static_cast<uint64_t>(width) * f.local_rows);
-		const bool big_scene = variant == RT_HIP_KERNEL_TILED || variant == RT_HIP_KERNEL_STREAMED;
-		rolling_items = big_scene;
-		queue_params queue = choose_queue(f.samples_per_pixel, width, f.local_rows, big_scene, host_frame, half_chunk_choice(flags), ctx->scene.n_spheres + ctx->scene.n_planes, variant == RT_HIP_KERNEL_STREAMED && ctx->scene.n_spheres >= sparse_launch_min_spheres);
+		launch_request request{};
+		request.n_spheres = ctx->scene.n_spheres, request.n_planes = ctx->scene.n_planes, request.planes_tame = ctx->scene.planes_tame != 0;
+		request.width = width, request.local_rows = f.local_rows, request.samples_per_pixel = f.samples_per_pixel;
+		request.camera = f.pinhole ? camera_form::pinhole : (f.eye_form == 2u ? camera_form::plain_eye : camera_form::other);
+		request.flags = flags, request.host_frame = host_frame, request.fast_arithmetic = (flags & RT_HIP_FLAG_FAST) != 0;
+		plan = plan_launch(request);
 		// small scenes: a pixel's chunk sums (one per 16 samples) are parked in LDS until the pixel is complete
-		const uint64_t slot_bytes = big_scene ? 0u : 4ull * tile_slot_bytes(queue);
-		if (slot_bytes > 48u * 1024u)
+		if (plan.slot_bytes > 48u * 1024u)
 			return fail(RT_HIP_UNSUPPORTED, "rt_hip_render_device: %u samples per pixel are more than the kernels hold chunk sums for (4096; the reference clamps to 1000, src/scene.cpp:544)", f.samples_per_pixel);
 		// big scenes: they meet in HBM, 16 bytes per chunk (or per sample) of this rank's rows
-		size_t sums_bytes = 0, done_bytes = 0;
-		rolling_buffer_bytes(queue, f.samples_per_pixel, width, f.local_rows, big_scene, sums_bytes, done_bytes);
-		if (sums_bytes > ctx->item_sums.bytes && queue.halves && big_scene && ctx->item_sums.reserve(sums_bytes) != hipSuccess)
+		if (plan.item_sums_bytes > ctx->item_sums.bytes && plan.queue.halves && plan.big_scene && ctx->item_sums.reserve(plan.item_sums_bytes) != hipSuccess)
 		{
-			// no room for a slot per SAMPLE (up to 8 GiB): whole chunks need a sixteenth of it.  The launch code makes the
-			// same choice from the same flag.
+			// no room for a slot per SAMPLE (up to 8 GiB): whole chunks need a sixteenth of it — the one launch that is planned twice
 			(void)hipGetLastError();
-			flags |= RT_HIP_FLAG_FORCE_WHOLE_CHUNKS;
-			flags &= ~static_cast<uint32_t>(RT_HIP_FLAG_FORCE_HALF_CHUNKS);
-			queue = choose_queue(f.samples_per_pixel, width, f.local_rows, big_scene, host_frame, half_chunk_choice(flags), ctx->scene.n_spheres + ctx->scene.n_planes, variant == RT_HIP_KERNEL_STREAMED && ctx->scene.n_spheres >= sparse_launch_min_spheres);
-			rolling_buffer_bytes(queue, f.samples_per_pixel, width, f.local_rows, big_scene, sums_bytes, done_bytes);
+			request.flags |= RT_HIP_FLAG_FORCE_WHOLE_CHUNKS;
+			request.flags &= ~static_cast<uint32_t>(RT_HIP_FLAG_FORCE_HALF_CHUNKS);
+			plan = plan_launch(request);
 		}
-		if (sums_bytes > (64ull << 30))
-			return fail(RT_HIP_UNSUPPORTED, "rt_hip_render_device: %ux%u at %u samples per pixel needs %zu GiB for the chunk sums of a scene of this size", width, height, f.samples_per_pixel, sums_bytes >> 30);
-		if (sums_bytes)
+		if (plan.item_sums_bytes > (64ull << 30))
+			return fail(RT_HIP_UNSUPPORTED, "rt_hip_render_device: %ux%u at %u samples per pixel needs %zu GiB for the chunk sums of a scene of this size", width, height, f.samples_per_pixel, plan.item_sums_bytes >> 30);
+		if (plan.item_sums_bytes)
 		{
-			RT_HIP_TRY(ctx->item_sums.reserve(sums_bytes));
-			RT_HIP_TRY(ctx->pixel_done.reserve(done_bytes));
+			RT_HIP_TRY(ctx->item_sums.reserve(plan.item_sums_bytes));
+			RT_HIP_TRY(ctx->pixel_done.reserve(plan.pixel_done_bytes));
 			// The arrival counters start every launch at zero — set here, on the launch's own stream, not left behind by the
 			// previous launch: a launch that did not run to its end (a failed or aborted one) must not cost later frames
 			// their pixels.  (8 MB at 1080p in front of a launch of milliseconds to seconds.)
-			RT_HIP_TRY(hipMemsetAsync(ctx->pixel_done.ptr, 0, done_bytes, s));
+			RT_HIP_TRY(hipMemsetAsync(ctx->pixel_done.ptr, 0, plan.pixel_done_bytes, s));
 			rolling.item_sums = ctx->item_sums.as<unsigned long long>();
 			rolling.pixel_done = ctx->pixel_done.as<uint32_t>();
 		}
@@ -247,15 +245,15 @@ rt_hip_status render_device(rt_hip_ctx* ctx, uint32_t width, uint32_t height, ui
 		RT_HIP_TRY(hipMemsetAsync(counters, 0, sizeof(device_counters), s));
 		RT_HIP_TRY(hipEventRecord(ctx->render_begin, s));
 	}
-	else if (rolling_items)
+	else if (plan.big_scene) // the persistent big-scene kernels draw items from a sequence whose head must start at 0
 		RT_HIP_TRY(hipMemsetAsync(&counters->next_item, 0, sizeof(counters->next_item), s)); // (seconds-long launches: not launch-bound)
 	uint32_t variant = RT_HIP_KERNEL_PREVIEW;
 	if (flags & RT_HIP_FLAG_PREVIEW)
 		launch_preview(f, ctx->scene, d_rgba8, d_rgb_f32, counters, s);
 	else if (flags & RT_HIP_FLAG_FAST)
-		variant = launch_render_fast(f, ctx->scene, ctx->small, flags | (host_frame ? launch_flag_host_frame : 0u), d_rgba8, d_rgb_f32, counters, rolling, ctx->compute_units, ctx->cache, s);
+		variant = launch_render_fast(f, ctx->scene, ctx->small, plan, d_rgba8, d_rgb_f32, counters, rolling, ctx->compute_units, ctx->cache, s);
 	else
-		variant = launch_render(f, ctx->scene, (flags & RT_HIP_FLAG_SM_MATERIALS) ? ctx->small_sm : ctx->small, flags | (host_frame ? launch_flag_host_frame : 0u), d_rgba8, d_rgb_f32, counters, rolling, ctx->compute_units, ctx->cache, s);
+		variant = launch_render(f, ctx->scene, (flags & RT_HIP_FLAG_SM_MATERIALS) ? ctx->small_sm : ctx->small, plan, d_rgba8, d_rgb_f32, counters, rolling, ctx->compute_units, ctx->cache, s);
 	RT_HIP_TRY(hipGetLastError());
 	ctx->launched = true;
 	ctx->last_stream = s;

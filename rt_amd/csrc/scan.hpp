@@ -9,8 +9,6 @@
 
 namespace rt_hip
 {
-	constexpr uint32_t block_threads = 256;
-
 	// best candidate of one linear scan (test_planes / test_spheres, mg_ray_tracer.cpp:36-87)
 	struct candidate
 	{

@@ -91,7 +91,7 @@ def test_empty_scene():
 
 def test_stack_capacity_matches_the_kernels():
     assert header_constant("bvh_max_depth") == STACK_DEPTH
-    kernels = (ROOT / "rt_amd" / "csrc" / "kernels.hpp").read_text()
+    kernels = (ROOT / "rt_amd" / "csrc" / "launch_plan.hpp").read_text()  # (the kernels' LDS sizes live with the launch policy)
     assert re.search(r"bvh_stack_float4s = 24u \* 256u / 4u", kernels)
 
 
