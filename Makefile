@@ -17,17 +17,17 @@ HIPFLAGS += -fvisibility=hidden
 # basic + plane 2.74 -> 2.62, tilted camera 2.80 -> 2.62 (profiles/r05/codegen_ab.txt).
 HIPFLAGS += -fno-slp-vectorize
 API_UNITS := context scene frame render multi group
-HIP_HDR  := rt_amd/csrc/kernels.hpp rt_amd/csrc/launch_plan.hpp rt_amd/csrc/contract.hpp rt_amd/csrc/scan.hpp rt_amd/csrc/bvh_scan.hpp rt_amd/csrc/bvh.hpp rt_amd/csrc/frame_group.hpp rt_amd/csrc/delivery.hpp rt_amd/csrc/internal.hpp include/rt_hip.h
+HIP_HDR  := rt_amd/csrc/kernels.hpp rt_amd/csrc/launch_plan.hpp rt_amd/csrc/contract.hpp rt_amd/csrc/scan.hpp rt_amd/csrc/bvh_scan.hpp rt_amd/csrc/bvh.hpp rt_amd/csrc/bvh_build.hpp rt_amd/csrc/bvh_build_device.hpp rt_amd/csrc/frame_group.hpp rt_amd/csrc/delivery.hpp rt_amd/csrc/internal.hpp include/rt_hip.h
 HOST_SRC := rt_amd/host/host_capi.cpp rt_amd/host/scene.cpp rt_amd/host/toml_subset.cpp
 HOST_HDR := $(wildcard rt_amd/host/*.hpp) rt_amd/host/host_capi.h rt_amd/host/named_colours.inc include/rt_hip.h
 
-all: $(LIBDIR)/librt_hip.so $(LIBDIR)/librt_hip_kat.so $(LIBDIR)/librt_host.so rt_amd/bin/rt_headless oracle
+all: $(LIBDIR)/librt_hip.so $(LIBDIR)/librt_hip_kat.so $(LIBDIR)/librt_host.so rt_amd/bin/rt_headless tests/native/lbvh_reference oracle
 
 # kernels.hip is compiled twice: the parity contract (contraction off), and RT_HIP_FLAG_FAST's arithmetic
 # (-DRT_HIP_FAST_BUILD -ffp-contract=fast: only launch_render_fast comes out of that one)
 FASTFLAGS := $(filter-out -ffp-contract=off,$(HIPFLAGS)) -ffp-contract=fast -DRT_HIP_FAST_BUILD
 OBJDIR   := build/obj$(NAME)
-HIP_OBJS := $(OBJDIR)/kernels.o $(OBJDIR)/kernels_fast.o $(API_UNITS:%=$(OBJDIR)/%.o) $(OBJDIR)/delivery.o $(OBJDIR)/bvh.o $(OBJDIR)/launch_plan.o
+HIP_OBJS := $(OBJDIR)/kernels.o $(OBJDIR)/kernels_fast.o $(API_UNITS:%=$(OBJDIR)/%.o) $(OBJDIR)/delivery.o $(OBJDIR)/bvh.o $(OBJDIR)/bvh_build.o $(OBJDIR)/launch_plan.o
 
 $(OBJDIR)/kernels.o: rt_amd/csrc/kernels.hip $(HIP_HDR)
 	@mkdir -p $(OBJDIR)
@@ -60,8 +60,9 @@ $(LIBDIR)/librt_hip.so: $(HIP_OBJS)
 	python3 tools/kernel_sources_hash.py > $(LIBDIR)/librt_hip.kernels.sha16   # what THIS binary's kernels were compiled from (bench.py, profiles)
 
 # test-only: the known-answer entry points of include/rt_hip_kat.h (never shipped; loads next to librt_hip.so)
-$(LIBDIR)/librt_hip_kat.so: $(OBJDIR)/kat.o $(OBJDIR)/bvh.o $(LIBDIR)/librt_hip.so
-	$(HIPCC) --offload-arch=gfx950 -fPIC -shared -o $@ $(OBJDIR)/kat.o $(OBJDIR)/bvh.o -L$(LIBDIR) -lrt_hip -Wl,-rpath,'$$ORIGIN' -L/opt/rocm/lib -lrccl
+# (with its own copies of both builders of the sphere hierarchy: librt_hip.so exports neither)
+$(LIBDIR)/librt_hip_kat.so: $(OBJDIR)/kat.o $(OBJDIR)/bvh.o $(OBJDIR)/bvh_build.o $(LIBDIR)/librt_hip.so
+	$(HIPCC) --offload-arch=gfx950 -fPIC -shared -o $@ $(OBJDIR)/kat.o $(OBJDIR)/bvh.o $(OBJDIR)/bvh_build.o -L$(LIBDIR) -lrt_hip -Wl,-rpath,'$$ORIGIN' -L/opt/rocm/lib -lrccl
 $(OBJDIR)/kat.o: include/rt_hip_kat.h
 
 $(LIBDIR)/librt_host.so: $(HOST_SRC) $(HOST_HDR)
@@ -80,6 +81,11 @@ rt_amd/bin/rt_headless: $(HEADLESS_SRC) $(HOST_HDR) $(LIBDIR)/librt_hip.so
 	@mkdir -p rt_amd/bin
 	$(CXX) $(HOSTFLAGS) -o $@ $(HEADLESS_SRC) -L$(LIBDIR) -lrt_hip -Wl,-rpath,'$$ORIGIN/../lib'
 
+# the device builder of the sphere hierarchy restated serially over its own per-element header, g++ alone (tests/test_bvh_lbvh_reference.py
+# builds its own copy; this one is for the command line)
+tests/native/lbvh_reference: tests/native/lbvh_reference.cpp rt_amd/csrc/bvh_build.hpp
+	$(CXX) -std=c++20 -O2 -ffp-contract=off -Wall -Wextra $< -o $@
+
 oracle:
 	$(MAKE) -C oracle
 
@@ -95,7 +101,7 @@ oracle/_ref/soagen_columns: tests/native/soagen_columns.cpp $(LIBDIR)/librt_hip.
 endif
 
 clean:
-	rm -f $(LIBDIR)/*.so rt_amd/bin/rt_headless
+	rm -f $(LIBDIR)/*.so rt_amd/bin/rt_headless tests/native/lbvh_reference
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean variant

@@ -227,7 +227,17 @@ enum
 	 * _FORCE_RESIDENT, _FORCE_STREAMED and RT_HIP_FLAG_FAST; ignored with RT_HIP_FLAG_PREVIEW (one ray per pixel: nothing to
 	 * gain).  Works with RT_HIP_FLAG_SM_MATERIALS and on every kind of context.  A library older than this flag refuses the
 	 * bit with RT_HIP_UNSUPPORTED (unknown flag bits): that is how a caller finds out whether it is there. */
-	RT_HIP_FLAG_BVH = 1u << 10
+	RT_HIP_FLAG_BVH = 1u << 10,
+	/* OPT-IN, modifies RT_HIP_FLAG_BVH: build the hierarchy on the GPU from the resident (c, r^2) table — a Morton-ordered
+	 * binary tree (radix sort, one launch per level, bottom-up boxes) instead of the host's binned SAH — on the frame's stream,
+	 * with no read-back of the table and no host build.  The PROMISE is RT_HIP_FLAG_BVH's: the same frame bit for bit, the same
+	 * `segments`, kernel_variant RT_HIP_KERNEL_BVH; the traversal does not depend on the tree's shape.  What changes is where
+	 * the time goes: the build leaves the host, and the Morton tree is not the SAH tree, so a cached frame may render slower
+	 * through it (DESIGN.md §9 has the measured table; nothing here promises a net gain).  The cached tree remembers its
+	 * builder: asking for the other one after the same upload rebuilds it.  `upload_ms` includes the build on frames that keep
+	 * stats (the call then waits for it).  Takes scenes of up to 2^26 spheres.  Refused (RT_HIP_UNSUPPORTED) without
+	 * RT_HIP_FLAG_BVH and wherever RT_HIP_FLAG_BVH is refused; ignored with RT_HIP_FLAG_PREVIEW. */
+	RT_HIP_FLAG_BVH_DEVICE_BUILD = 1u << 11
 };
 
 typedef struct rt_hip_ctx rt_hip_ctx;

@@ -60,6 +60,28 @@ RT_HIP_API rt_hip_status rt_hip_kat_bvh_build(const rt_hip_scene* scene,
 								   uint32_t* out_always,
 								   float out_bound[4]);
 
+/* The tree that the product's device builder (RT_HIP_FLAG_BVH_DEVICE_BUILD, rt_amd/csrc/bvh_build.hip) makes for the scene resident
+ * on `ctx`, read back.  The outputs mean what rt_hip_kat_bvh_build's mean, with one difference: node k is the node that cuts the
+ * leaf order between slots k and k + 1, so out_counts[0] counts node SLOTS (tree spheres - 1, or 0 for a tree of one leaf) and
+ * the slots no cut uses are all zero.  Must equal tests/native/lbvh_reference.cpp byte for byte. */
+RT_HIP_API rt_hip_status rt_hip_kat_bvh_build_device(rt_hip_ctx* ctx,
+											  uint32_t out_counts[5],
+											  float* out_nodes,
+											  uint32_t* out_order,
+											  float* out_spheres,
+											  uint32_t* out_always,
+											  float out_bound[4]);
+
+/* rt_hip_kat_closest_hit_bvh through the device builder's tree.  Must equal rt_hip_kat_closest_hit bit for bit. */
+RT_HIP_API rt_hip_status rt_hip_kat_closest_hit_bvh_device(rt_hip_ctx* ctx,
+													uint32_t n,
+													const float* origins,
+													const float* directions,
+													float* out_distance,
+													uint32_t* out_kind,
+													uint32_t* out_index,
+													float* out_normal);
+
 /* out_sqrt[i] = sqrtf(a[i]), out_div[i] = a[i] / b[i] as the device computes them (must be correctly rounded). */
 RT_HIP_API rt_hip_status rt_hip_kat_sqrt_div(rt_hip_ctx* ctx, uint32_t n, const float* a, const float* b, float* out_sqrt, float* out_div);
 

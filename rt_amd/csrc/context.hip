@@ -435,6 +435,7 @@ extern "C" void rt_hip_destroy(rt_hip_ctx* ctx)
 	ctx->delivery.reset(); // (joins the delivery threads, frees the module's own frame)
 	ctx->scene_columns.release();
 	ctx->bvh_block.release();
+	ctx->bvh_scratch.release();
 	ctx->scene_staging.release();
 	ctx->item_sums.release();
 	ctx->pixel_done.release();

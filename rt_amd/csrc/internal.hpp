@@ -168,7 +168,7 @@ namespace rt_hip
 	struct frame_delivery; // below: the module-owned frame and the threads that carry it to the caller's buffer
 
 	// (RT_HIP_FLAG_PERSISTENT_FRAME and RT_HIP_FLAG_STATS are rt_hip_render's own: they do not travel to the launch)
-	constexpr uint32_t render_flag_mask = RT_HIP_FLAG_FORCE_TILED | RT_HIP_FLAG_FORCE_RESIDENT | RT_HIP_FLAG_SM_MATERIALS | RT_HIP_FLAG_PREVIEW | RT_HIP_FLAG_FORCE_STREAMED | RT_HIP_FLAG_FAST | RT_HIP_FLAG_FORCE_HALF_CHUNKS | RT_HIP_FLAG_FORCE_WHOLE_CHUNKS | RT_HIP_FLAG_BVH;
+	constexpr uint32_t render_flag_mask = RT_HIP_FLAG_FORCE_TILED | RT_HIP_FLAG_FORCE_RESIDENT | RT_HIP_FLAG_SM_MATERIALS | RT_HIP_FLAG_PREVIEW | RT_HIP_FLAG_FORCE_STREAMED | RT_HIP_FLAG_FAST | RT_HIP_FLAG_FORCE_HALF_CHUNKS | RT_HIP_FLAG_FORCE_WHOLE_CHUNKS | RT_HIP_FLAG_BVH | RT_HIP_FLAG_BVH_DEVICE_BUILD;
 
 }
 
@@ -231,6 +231,8 @@ struct rt_hip_ctx
 	uint64_t bvh_built_for = 0;			 // ... its scene_uploads when built (0 = none)
 	rt_hip::device_buffer bvh_block;	 // RT_HIP_FLAG_BVH: descriptor, nodes, leaf-ordered spheres, their indices, the always list
 	const rt_hip::device_bvh* bvh_descriptor = nullptr; // ... its first bytes: what the BVH kernel is handed (rolling_buffers::bvh)
+	bool bvh_device_built = false;		 // ... and which builder made it: bvh_build.hip (RT_HIP_FLAG_BVH_DEVICE_BUILD) or bvh.cpp
+	rt_hip::device_buffer bvh_scratch;	 // the device builder's keys, ping-pong buffers and level queues
 	size_t scene_bytes = 0;				 // size of the resident block
 	// Opt-in (RT_HIP_FLAG_PERSISTENT_FRAME, frame groups): the CALLER's buffer, page-locked and mapped into the GPU's address
 	// space while it keeps arriving at the same address: the kernel renders straight into it.  The caller then owes the
@@ -282,7 +284,9 @@ namespace rt_hip
 	rt_hip_status open_request(scene_request& r, const rt_hip_scene* scene);
 	// Make `ctx` hold the request's scene (leaves ctx->device current)
 	rt_hip_status make_resident(rt_hip_ctx* ctx, scene_request& r);
-	rt_hip_status ensure_bvh(rt_hip_ctx* ctx); // RT_HIP_FLAG_BVH: the resident scene's sphere hierarchy (scene.hip)
+	// RT_HIP_FLAG_BVH: the resident scene's sphere hierarchy (scene.hip).  device_build: RT_HIP_FLAG_BVH_DEVICE_BUILD — built by
+	// bvh_build.hip on `stream`, the stream the frame is about to be launched on; wait: the frame keeps stats, upload_ms is to hold the build
+	rt_hip_status ensure_bvh(rt_hip_ctx* ctx, bool device_build, hipStream_t stream, bool wait);
 
 	// ---- render.hip ----
 	// whole_frame_buffers: d_rgba8 / d_rgb_f32 are the whole width x height frame and every pixel goes to its image row

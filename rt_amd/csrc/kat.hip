@@ -12,6 +12,8 @@
 #include "internal.hpp"
 #include "scan.hpp"
 #include "bvh_scan.hpp"
+#include "bvh_build.hpp"
+#include "bvh_build_device.hpp"
 
 #include <algorithm>
 #include <vector>
@@ -264,7 +266,8 @@ extern "C" rt_hip_status rt_hip_kat_random(rt_hip_ctx* ctx, uint64_t seed, uint3
 	return RT_HIP_OK;
 }
 
-static rt_hip_status closest_hit(bool bvh,
+// bvh: 0 = the linear scan, 1 = the host builder's hierarchy, 2 = the device builder's
+static rt_hip_status closest_hit(int bvh,
 								 rt_hip_ctx* ctx,
 								 uint32_t n,
 								 const float* origins,
@@ -274,7 +277,7 @@ static rt_hip_status closest_hit(bool bvh,
 								 uint32_t* out_index,
 								 float* out_normal)
 {
-	const char* const name = bvh ? "rt_hip_kat_closest_hit_bvh" : "rt_hip_kat_closest_hit";
+	const char* const name = bvh == 2 ? "rt_hip_kat_closest_hit_bvh_device" : (bvh ? "rt_hip_kat_closest_hit_bvh" : "rt_hip_kat_closest_hit");
 	if (!ctx || !n || !origins || !directions || !out_distance || !out_kind || !out_index || !out_normal)
 		return kat_fail(RT_HIP_INVALID_ARGUMENT, "%s: invalid argument", name);
 	if (!ctx->have_scene)
@@ -283,7 +286,26 @@ static rt_hip_status closest_hit(bool bvh,
 	const device_scene& scene = ctx->scene;
 	device_bvh tree_desc{};
 	scratch tree_block;
-	if (bvh)
+	device_buffer device_tree, device_tree_scratch;
+	struct release_device_tree
+	{
+		device_buffer &a, &b;
+		~release_device_tree() { a.release(), b.release(); }
+	} release_tree{ device_tree, device_tree_scratch };
+	if (bvh == 2)
+	{
+		// the device builder's tree of the resident scene, used where it lies (the descriptor is read back for the kernel's argument)
+		if (scene.n_spheres > lbvh::max_spheres)
+			return kat_fail(RT_HIP_UNSUPPORTED, "%s: more than 2^26 spheres", name);
+		const bvh_build_sizes sizes = bvh_build_sizes_for(scene.n_spheres);
+		RT_HIP_KAT_TRY(device_tree.reserve(sizes.block_bytes));
+		RT_HIP_KAT_TRY(device_tree_scratch.reserve(sizes.scratch_bytes));
+		RT_HIP_KAT_TRY(tree_block.host.reserve(sizeof(device_bvh)));
+		RT_HIP_KAT_TRY(build_bvh_device(scene.primitive_geometry, scene.n_spheres, device_tree.ptr, device_tree_scratch.ptr, nullptr));
+		RT_HIP_KAT_TRY(hipMemcpy(tree_block.host.ptr, device_tree.ptr, sizeof(device_bvh), hipMemcpyDeviceToHost));
+		std::memcpy(&tree_desc, tree_block.host.ptr, sizeof(device_bvh));
+	}
+	else if (bvh)
 	{
 		// the hierarchy of the resident scene, built as the render path builds it (scene.hip, ensure_bvh): from the table on the device
 		const uint32_t spheres = scene.n_spheres;
@@ -327,7 +349,7 @@ static rt_hip_status closest_hit(bool bvh,
 	uint32_t* d_kind = reinterpret_cast<uint32_t*>(d_out + scalar_bytes);
 	uint32_t* d_index = reinterpret_cast<uint32_t*>(d_out + 2 * scalar_bytes);
 	float* d_normal = reinterpret_cast<float*>(d_out + 3 * scalar_bytes);
-	launch_kat_closest_hit(bvh, scene, tree_desc, n, reinterpret_cast<const float*>(d_in), reinterpret_cast<const float*>(d_in + vec_bytes), d_distance, d_kind, d_index, d_normal, nullptr);
+	launch_kat_closest_hit(bvh != 0, scene, tree_desc, n, reinterpret_cast<const float*>(d_in), reinterpret_cast<const float*>(d_in + vec_bytes), d_distance, d_kind, d_index, d_normal, nullptr);
 	RT_HIP_KAT_TRY(hipGetLastError());
 	RT_HIP_KAT_TRY(hipMemcpy(out.host.ptr, out.device.ptr, vec_bytes + 3 * scalar_bytes, hipMemcpyDeviceToHost));
 	const unsigned char* const h_out = out.host.as<unsigned char>();
@@ -347,7 +369,7 @@ extern "C" rt_hip_status rt_hip_kat_closest_hit(rt_hip_ctx* ctx,
 												uint32_t* out_index,
 												float* out_normal)
 {
-	return closest_hit(false, ctx, n, origins, directions, out_distance, out_kind, out_index, out_normal);
+	return closest_hit(0, ctx, n, origins, directions, out_distance, out_kind, out_index, out_normal);
 }
 
 extern "C" rt_hip_status rt_hip_kat_closest_hit_bvh(rt_hip_ctx* ctx,
@@ -359,7 +381,70 @@ extern "C" rt_hip_status rt_hip_kat_closest_hit_bvh(rt_hip_ctx* ctx,
 													uint32_t* out_index,
 													float* out_normal)
 {
-	return closest_hit(true, ctx, n, origins, directions, out_distance, out_kind, out_index, out_normal);
+	return closest_hit(1, ctx, n, origins, directions, out_distance, out_kind, out_index, out_normal);
+}
+
+extern "C" rt_hip_status rt_hip_kat_closest_hit_bvh_device(rt_hip_ctx* ctx,
+														   uint32_t n,
+														   const float* origins,
+														   const float* directions,
+														   float* out_distance,
+														   uint32_t* out_kind,
+														   uint32_t* out_index,
+														   float* out_normal)
+{
+	return closest_hit(2, ctx, n, origins, directions, out_distance, out_kind, out_index, out_normal);
+}
+
+extern "C" rt_hip_status rt_hip_kat_bvh_build_device(rt_hip_ctx* ctx,
+													 uint32_t out_counts[5],
+													 float* out_nodes,
+													 uint32_t* out_order,
+													 float* out_spheres,
+													 uint32_t* out_always,
+													 float out_bound[4])
+{
+	if (!ctx || !out_counts)
+		return kat_fail(RT_HIP_INVALID_ARGUMENT, "rt_hip_kat_bvh_build_device: NULL argument");
+	if (!ctx->have_scene)
+		return kat_fail(RT_HIP_NO_SCENE, "rt_hip_kat_bvh_build_device: no scene uploaded");
+	const uint32_t n = ctx->scene.n_spheres;
+	if (n > lbvh::max_spheres)
+		return kat_fail(RT_HIP_UNSUPPORTED, "rt_hip_kat_bvh_build_device: more than 2^26 spheres");
+	RT_HIP_KAT_TRY(hipSetDevice(ctx->device));
+	const bvh_build_sizes sizes = bvh_build_sizes_for(n);
+	scratch tree, work; // (the host halves: the tree read back, and the build's header)
+	RT_HIP_KAT_TRY(tree.reserve(sizes.block_bytes));
+	RT_HIP_KAT_TRY(work.device.reserve(sizes.scratch_bytes));
+	RT_HIP_KAT_TRY(work.host.reserve(sizeof(bvh_build_header)));
+	RT_HIP_KAT_TRY(build_bvh_device(ctx->scene.primitive_geometry, n, tree.device.ptr, work.device.ptr, nullptr));
+	RT_HIP_KAT_TRY(hipMemcpy(tree.host.ptr, tree.device.ptr, sizes.block_bytes, hipMemcpyDeviceToHost));
+	RT_HIP_KAT_TRY(hipMemcpy(work.host.ptr, work.device.ptr, sizeof(bvh_build_header), hipMemcpyDeviceToHost));
+	const unsigned char* const h = tree.host.as<unsigned char>();
+	device_bvh d;
+	std::memcpy(&d, h, sizeof(d));
+	const bvh_build_header& header = *work.host.as<bvh_build_header>();
+	uint32_t depth = 0;
+	for (uint32_t level = 1; level <= lbvh::max_depth; level++)
+		if (header.level_count[level])
+			depth = level;
+	const uint32_t node_slots = d.n_tree > lbvh::leaf_spheres ? d.n_tree - 1u : 0u;
+	out_counts[0] = node_slots;
+	out_counts[1] = d.n_tree;
+	out_counts[2] = d.n_always;
+	out_counts[3] = depth;
+	out_counts[4] = d.root;
+	if (out_nodes)
+		std::memcpy(out_nodes, h + sizes.nodes_at, static_cast<size_t>(node_slots) * 64u);
+	if (out_order)
+		std::memcpy(out_order, h + sizes.order_at, static_cast<size_t>(d.n_tree) * 4u);
+	if (out_spheres)
+		std::memcpy(out_spheres, h + sizes.spheres_at, static_cast<size_t>(d.n_tree) * 16u);
+	if (out_always)
+		std::memcpy(out_always, h + sizes.order_at + static_cast<size_t>(d.n_tree) * 4u, static_cast<size_t>(d.n_always) * 4u);
+	if (out_bound)
+		out_bound[0] = d.cx, out_bound[1] = d.cy, out_bound[2] = d.cz, out_bound[3] = d.radius;
+	return RT_HIP_OK;
 }
 
 extern "C" rt_hip_status rt_hip_kat_bvh_build(const rt_hip_scene* scene,

@@ -52,14 +52,16 @@ rt_hip_status render_device(rt_hip_ctx* ctx, uint32_t width, uint32_t height, ui
 		return fail(RT_HIP_INVALID_ARGUMENT, "rt_hip_render_device: empty frame %ux%u", width, height);
 	if (static_cast<uint64_t>(width) * height > 0xFFFFFFFFull)
 		return fail(RT_HIP_INVALID_ARGUMENT, "rt_hip_render_device: %ux%u exceeds the 32-bit pixel index of image_view", width, height);
-	if (flags & ~static_cast<uint32_t>(RT_HIP_FLAG_FORCE_TILED | RT_HIP_FLAG_FORCE_RESIDENT | RT_HIP_FLAG_PERSISTENT_FRAME | RT_HIP_FLAG_SM_MATERIALS | RT_HIP_FLAG_PREVIEW | RT_HIP_FLAG_FORCE_STREAMED | RT_HIP_FLAG_FAST | RT_HIP_FLAG_STATS | RT_HIP_FLAG_FORCE_HALF_CHUNKS | RT_HIP_FLAG_FORCE_WHOLE_CHUNKS | RT_HIP_FLAG_BVH))
+	if (flags & ~static_cast<uint32_t>(RT_HIP_FLAG_FORCE_TILED | RT_HIP_FLAG_FORCE_RESIDENT | RT_HIP_FLAG_PERSISTENT_FRAME | RT_HIP_FLAG_SM_MATERIALS | RT_HIP_FLAG_PREVIEW | RT_HIP_FLAG_FORCE_STREAMED | RT_HIP_FLAG_FAST | RT_HIP_FLAG_STATS | RT_HIP_FLAG_FORCE_HALF_CHUNKS | RT_HIP_FLAG_FORCE_WHOLE_CHUNKS | RT_HIP_FLAG_BVH | RT_HIP_FLAG_BVH_DEVICE_BUILD))
 		return fail(RT_HIP_UNSUPPORTED, "rt_hip_render_device: unknown flag bits 0x%x", flags);
 	if ((flags & RT_HIP_FLAG_BVH) && (flags & (RT_HIP_FLAG_FORCE_TILED | RT_HIP_FLAG_FORCE_RESIDENT | RT_HIP_FLAG_FORCE_STREAMED)))
 		return fail(RT_HIP_UNSUPPORTED, "rt_hip_render_device: RT_HIP_FLAG_BVH chooses its own kernel (not with RT_HIP_FLAG_FORCE_TILED / _RESIDENT / _STREAMED)");
 	if ((flags & RT_HIP_FLAG_BVH) && (flags & RT_HIP_FLAG_FAST))
 		return fail(RT_HIP_UNSUPPORTED, "rt_hip_render_device: RT_HIP_FLAG_BVH is built for the parity contract's arithmetic only (not with RT_HIP_FLAG_FAST)");
 	if (flags & RT_HIP_FLAG_PREVIEW)
-		flags &= ~static_cast<uint32_t>(RT_HIP_FLAG_BVH); // one ray per pixel: the preview keeps its own scan
+		flags &= ~static_cast<uint32_t>(RT_HIP_FLAG_BVH | RT_HIP_FLAG_BVH_DEVICE_BUILD); // one ray per pixel: the preview keeps its own scan
+	if ((flags & RT_HIP_FLAG_BVH_DEVICE_BUILD) && !(flags & RT_HIP_FLAG_BVH))
+		return fail(RT_HIP_UNSUPPORTED, "rt_hip_render_device: RT_HIP_FLAG_BVH_DEVICE_BUILD says how RT_HIP_FLAG_BVH's hierarchy is built (not without it)");
 	if ((flags & RT_HIP_FLAG_FORCE_HALF_CHUNKS) && (flags & RT_HIP_FLAG_FORCE_WHOLE_CHUNKS))
 		return fail(RT_HIP_INVALID_ARGUMENT, "rt_hip_render_device: RT_HIP_FLAG_FORCE_HALF_CHUNKS and RT_HIP_FLAG_FORCE_WHOLE_CHUNKS exclude each other");
 	if ((flags & RT_HIP_FLAG_FAST) && (flags & (RT_HIP_FLAG_SM_MATERIALS | RT_HIP_FLAG_PREVIEW)))
@@ -67,8 +69,9 @@ rt_hip_status render_device(rt_hip_ctx* ctx, uint32_t width, uint32_t height, ui
 	if (!ctx->have_scene)
 		return fail(RT_HIP_NO_SCENE, "rt_hip_render_device: no scene uploaded");
 	if (flags & RT_HIP_FLAG_BVH)
-		if (const rt_hip_status st = ensure_bvh(ctx))
+		if (const rt_hip_status st = ensure_bvh(ctx, (flags & RT_HIP_FLAG_BVH_DEVICE_BUILD) != 0u, static_cast<hipStream_t>(stream), keep_stats))
 			return st;
+	flags &= ~static_cast<uint32_t>(RT_HIP_FLAG_BVH_DEVICE_BUILD); // (the builder's business: the launch is RT_HIP_FLAG_BVH's either way)
 	const device_bvh* const bvh = (flags & RT_HIP_FLAG_BVH) ? ctx->bvh_descriptor : nullptr;
 	if (height > 65535u * 2u) // the launch grid's y dimension counts pixel tiles at least two rows high
 		return fail(RT_HIP_INVALID_ARGUMENT, "rt_hip_render_device: frame height %u exceeds the supported 131070 rows", height);

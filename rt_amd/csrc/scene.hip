@@ -6,6 +6,8 @@
 // whose split float columns none of its renderers reads.
 #include "internal.hpp"
 #include "bvh.hpp"
+#include "bvh_build.hpp"
+#include "bvh_build_device.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -336,17 +338,55 @@ namespace rt_hip
 		return ok();
 	}
 
-	// RT_HIP_FLAG_BVH: make ctx->scene.bvh describe a hierarchy of the resident scene.  Built on the host from the (c, r^2) table
-	// read back from the device — the very floats the linear kernels read — at the first such frame after an upload, and
-	// kept until the next one.  The build's time is added to upload_ms.
-	rt_hip_status ensure_bvh(rt_hip_ctx* ctx)
+	// RT_HIP_FLAG_BVH_DEVICE_BUILD: the hierarchy built by bvh_build.hip from the table where it lies, enqueued on the frame's
+	// stream.  Nothing is read back.  The call waits in two cases only: a block has to grow (what it held may still be read), and
+	// `wait` (the frame keeps stats: upload_ms is to hold the build, as it holds the host's).
+	static rt_hip_status build_bvh_on_device(rt_hip_ctx* ctx, hipStream_t stream, bool wait)
 	{
-		if (ctx->bvh_built_for == ctx->scene_uploads)
+		const auto t0 = std::chrono::steady_clock::now();
+		const uint32_t n = ctx->scene.n_spheres;
+		if (n > lbvh::max_spheres)
+			return fail(RT_HIP_UNSUPPORTED, "RT_HIP_FLAG_BVH_DEVICE_BUILD: more than 2^26 spheres");
+		RT_HIP_TRY(hipSetDevice(ctx->device));
+		const bvh_build_sizes sizes = bvh_build_sizes_for(n);
+		ctx->bvh_descriptor = nullptr;
+		ctx->bvh_built_for = 0;
+		if (sizes.block_bytes > ctx->bvh_block.bytes || sizes.scratch_bytes > ctx->bvh_scratch.bytes)
+			RT_HIP_TRY(hipDeviceSynchronize()); // a previous frame may still be reading the tree that is about to be freed
+		else if (ctx->launched && ctx->last_stream != stream)
+			RT_HIP_TRY(hipStreamSynchronize(ctx->last_stream)); // ... or, on another stream, the tree that is about to be overwritten
+		if (ctx->bvh_block.reserve(sizes.block_bytes) != hipSuccess || ctx->bvh_scratch.reserve(sizes.scratch_bytes) != hipSuccess)
+		{
+			(void)hipGetLastError();
+			return fail(RT_HIP_RUNTIME_ERROR, "RT_HIP_FLAG_BVH_DEVICE_BUILD: no device memory for a hierarchy of %u spheres (%zu + %zu bytes)", n, sizes.block_bytes, sizes.scratch_bytes);
+		}
+		RT_HIP_TRY(build_bvh_device(ctx->scene.primitive_geometry, n, ctx->bvh_block.ptr, ctx->bvh_scratch.ptr, stream));
+		ctx->launched = true;
+		ctx->last_stream = stream;
+		if (wait)
+			RT_HIP_TRY(hipStreamSynchronize(stream));
+		ctx->bvh_descriptor = ctx->bvh_block.as<const device_bvh>();
+		ctx->bvh_built_for = ctx->scene_uploads;
+		ctx->bvh_device_built = true;
+		ctx->stats.upload_ms += static_cast<float>(seconds_since(t0) * 1e3);
+		return ok();
+	}
+
+	// RT_HIP_FLAG_BVH: make ctx->bvh_descriptor describe a hierarchy of the resident scene, built at the first such frame after an
+	// upload — or after a frame that asked for the other builder — and kept until the next one.  The host builder (bvh.cpp) works
+	// from the (c, r^2) table read back from the device, the very floats the linear kernels read.  The build's time is added to
+	// upload_ms.
+	rt_hip_status ensure_bvh(rt_hip_ctx* ctx, bool device_build, hipStream_t stream, bool wait)
+	{
+		if (ctx->bvh_built_for == ctx->scene_uploads && ctx->bvh_device_built == device_build)
 			return ok();
+		if (device_build)
+			return build_bvh_on_device(ctx, stream, wait);
 		const auto t0 = std::chrono::steady_clock::now();
 		const uint32_t n = ctx->scene.n_spheres;
 		RT_HIP_TRY(hipSetDevice(ctx->device));
 		RT_HIP_TRY(hipDeviceSynchronize()); // a previous frame may still be reading the old tree
+		ctx->bvh_built_for = 0;
 		std::vector<float> geometry(static_cast<size_t>(n) * 4);
 		if (n)
 			RT_HIP_TRY(hipMemcpy(geometry.data(), ctx->scene.primitive_geometry, static_cast<size_t>(n) * sizeof(float4), hipMemcpyDeviceToHost));
@@ -380,6 +420,7 @@ namespace rt_hip
 		RT_HIP_TRY(hipMemcpy(ctx->bvh_block.ptr, image.data(), image.size(), hipMemcpyHostToDevice));
 		ctx->bvh_descriptor = reinterpret_cast<const device_bvh*>(base);
 		ctx->bvh_built_for = ctx->scene_uploads;
+		ctx->bvh_device_built = false;
 		ctx->stats.upload_ms += static_cast<float>(seconds_since(t0) * 1e3);
 		return ok();
 	}

@@ -116,6 +116,8 @@ namespace
 		static const uint32_t flags = []
 		{
 			const char* accel = std::getenv("RT_HIP_ACCEL");
+			if (accel && std::strcmp(accel, "bvh-device") == 0) // ... and builds the hierarchy on the GPU (RT_HIP_FLAG_BVH_DEVICE_BUILD)
+				return static_cast<uint32_t>(RT_HIP_FLAG_BVH | RT_HIP_FLAG_BVH_DEVICE_BUILD);
 			return (accel && std::strcmp(accel, "bvh") == 0) ? static_cast<uint32_t>(RT_HIP_FLAG_BVH) : static_cast<uint32_t>(RT_HIP_FLAG_NONE);
 		}();
 		return flags;

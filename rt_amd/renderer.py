@@ -233,9 +233,25 @@ class HipRayTracer:
         capi.check_kat(capi.kat_lib().rt_hip_kat_random(self._ctx, seed, pixel, sample, n, out.ctypes.data))
         return out
 
-    def kat_closest_hit(self, origins: np.ndarray, directions: np.ndarray, bvh: bool = False):
+    def kat_bvh_build_device(self) -> dict:
+        """The sphere hierarchy RT_HIP_FLAG_BVH_DEVICE_BUILD builds for the resident scene, read back
+        (rt_hip_kat_bvh_build_device): the dictionary of `bvh_build`, with one row of `nodes` per node SLOT."""
+        counts = np.zeros(5, dtype=np.uint32)
+        capi.check_kat(capi.kat_lib().rt_hip_kat_bvh_build_device(self._ctx, counts.ctypes.data, None, None, None, None, None))  # the sizes first
+        n = max(int(counts[1]) + int(counts[2]), 1)
+        nodes = np.zeros((n, 16), dtype=np.float32)
+        order = np.zeros(n, dtype=np.uint32)
+        spheres = np.zeros((n, 4), dtype=np.float32)
+        always = np.zeros(n, dtype=np.uint32)
+        bound = np.zeros(4, dtype=np.float32)
+        capi.check_kat(capi.kat_lib().rt_hip_kat_bvh_build_device(self._ctx, counts.ctypes.data, nodes.ctypes.data, order.ctypes.data, spheres.ctypes.data, always.ctypes.data, bound.ctypes.data))
+        n_nodes, n_tree, n_always, depth, root = (int(c) for c in counts)
+        return {"nodes": nodes[:n_nodes], "order": order[:n_tree], "spheres": spheres[:n_tree], "always": always[:n_always], "bound": bound, "depth": depth, "root": root}
+
+    def kat_closest_hit(self, origins: np.ndarray, directions: np.ndarray, bvh: bool = False, device_build: bool = False):
         """Closest hit of each ray against the resident scene: (distance, kind, index, normal).  `bvh`: through the sphere
-        hierarchy of RT_HIP_FLAG_BVH (rt_hip_kat_closest_hit_bvh) instead of the linear scan."""
+        hierarchy of RT_HIP_FLAG_BVH (rt_hip_kat_closest_hit_bvh) instead of the linear scan; `device_build`: through the
+        hierarchy the device builder makes (rt_hip_kat_closest_hit_bvh_device)."""
         o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
         d = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
         n = len(o)
@@ -243,7 +259,8 @@ class HipRayTracer:
         kind = np.empty(n, dtype=np.uint32)
         index = np.empty(n, dtype=np.uint32)
         normal = np.empty((n, 3), dtype=np.float32)
-        entry = capi.kat_lib().rt_hip_kat_closest_hit_bvh if bvh else capi.kat_lib().rt_hip_kat_closest_hit
+        kat = capi.kat_lib()
+        entry = kat.rt_hip_kat_closest_hit_bvh_device if device_build else (kat.rt_hip_kat_closest_hit_bvh if bvh else kat.rt_hip_kat_closest_hit)
         capi.check_kat(entry(self._ctx, n, o.ctypes.data, d.ctypes.data, dist.ctypes.data, kind.ctypes.data, index.ctypes.data, normal.ctypes.data))
         return dist, kind, index, normal
 

@@ -9,7 +9,10 @@ the loop cost a 7-sphere frame a factor (round 5: dielectric.toml 2.7 -> 9.4 ms 
 every change of the source.  Run this after any change to the kernels; `--fail-on-scratch N` exits non-zero if a scalar-register
 kernel without the sm table contains more than N scratch loads / stores.  (`scratch` = bytes of private segment the build
 reserves, `ops` = scratch_load / scratch_store instructions in its text: a build can reserve a segment for stack objects
-it never touches — that costs nothing; spills in the loop are what to look for.)"""
+it never touches — that costs nothing; spills in the loop are what to look for.)
+
+Given a listing of rt_amd/csrc/bvh_build.hip instead, it lists the device builder's kernels (build_*, sort_*) in a second table:
+they are expected to reserve no scratch at all."""
 import re
 import sys
 
@@ -25,6 +28,11 @@ for line in open(path):
         name = (m.group(1), int(ns.replace("n", "-")), int(m.group(3)), int(m.group(4)), int(m.group(5)), int(m.group(6)))
         cur = {}
         continue
+    m = re.match(r"^_ZN6rt_hip12_GLOBAL__N_1\d+((?:build|sort)_[a-z]+)E\w*:", line)
+    if m:
+        name = (m.group(1),)
+        cur = {}
+        continue
     if name:
         if re.match(r"^\s*scratch_(load|store)", line):
             cur["scratch_ops"] = cur.get("scratch_ops", 0) + 1
@@ -37,9 +45,15 @@ for line in open(path):
                 cur = {}
 bad = 0
 print(f"{'kernel':14s} {'NS':>3s} {'SM':>2s} {'HALF':>4s} {'NP':>2s} {'GC':>2s} {'VGPR':>5s} {'SGPR':>5s} {'scratch':>7s} {'ops':>4s} {'waves':>5s}")
+builder = [(name[0], c) for name, c in rows if len(name) == 1]
+rows = [row for row in rows if len(row[0]) > 1]
 for (kernel, ns, sm, half, np_, gc), c in sorted(rows):
     flag = ""
     if limit is not None and ns > 0 and not sm and c.get("scratch_ops", 0) > limit:
         flag, bad = "  <-- scratch", bad + 1
     print(f"{kernel:14s} {ns:3d} {sm:2d} {half:4d} {np_:2d} {gc:2d} {c.get('NumVgprs', -1):5d} {c.get('TotalNumSgprs', -1):5d} {c.get('ScratchSize', -1):7d} {c.get('scratch_ops', 0):4d} {c.get('Occupancy', -1):5d}{flag}")
+if builder:
+    print(f"{'builder kernel':16s} {'VGPR':>5s} {'SGPR':>5s} {'scratch':>7s} {'ops':>4s} {'waves':>5s}")
+    for kernel, c in builder:
+        print(f"{kernel:16s} {c.get('NumVgprs', -1):5d} {c.get('TotalNumSgprs', -1):5d} {c.get('ScratchSize', -1):7d} {c.get('scratch_ops', 0):4d} {c.get('Occupancy', -1):5d}")
 sys.exit(1 if bad else 0)
