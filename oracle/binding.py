@@ -70,6 +70,8 @@ def lib() -> C.CDLL:
         l.oracle_sky.argtypes = [C.c_float, C.c_void_p]
         l.oracle_primary_ray.restype = C.c_int
         l.oracle_primary_ray.argtypes = [C.POINTER(RtHipScene), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_void_p, C.c_void_p]
+        l.oracle_frame_constants.restype = None
+        l.oracle_frame_constants.argtypes = [C.POINTER(RtHipScene), C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p]
         l.oracle_hits_box.restype = C.c_int
         l.oracle_hits_box.argtypes = [C.c_void_p] * 5
         l.oracle_dielectric_direction.restype = None
@@ -209,6 +211,24 @@ def primary_ray(scene: RtHipScene, width: int, height: int, x: int, y: int, ka: 
     d = np.empty(3, dtype=np.float32)
     pinhole = lib().oracle_primary_ray(C.byref(scene), width, height, x, y, ka, kb, o.ctypes.data, d.ctypes.data)
     return (o, d, {1: "pinhole", 2: "eye", 0: "general"}[pinhole]) if want_form else (o, d)
+
+
+# (name, length) of what oracle_frame_constants writes, in order; 1-element entries are scalars
+FRAME_CONSTANTS = [("pinhole_rays", 1), ("eye_rays", 1), ("ray_d0", 3), ("ray_d1", 3), ("ray_d2", 3), ("ray_j1", 3), ("ray_j2", 3), ("ray_eye", 3),
+                   ("eye_q0", 3), ("eye_q1", 3), ("eye_q2", 3), ("eye_jq1", 3), ("eye_jq2", 3), ("eye_w0", 1), ("eye_w1", 1), ("eye_w2", 1), ("eye_jw1", 1),
+                   ("eye_jw2", 1), ("eye_e", 3), ("eye_zws", 1), ("mx", 4), ("my", 4), ("k_near", 4), ("k_far", 4), ("sx", 1), ("frame_key_a", 1), ("frame_key_b", 1)]
+
+
+def frame_constants(scene: RtHipScene, width: int, height: int, seed: int = 0) -> dict:
+    """make_frame's constants (camera form flags, the forms' scalars, the split matrix, 2/W, the mixed seed) as BIT PATTERNS: name ->
+    tuple of uint32."""
+    out = np.zeros(sum(n for _, n in FRAME_CONSTANTS), dtype=np.uint32)
+    lib().oracle_frame_constants(C.byref(scene), width, height, seed, out.ctypes.data)
+    at, named = 0, {}
+    for name, n in FRAME_CONSTANTS:
+        named[name] = tuple(int(v) for v in out[at : at + n])
+        at += n
+    return named
 
 
 def dielectric_direction(direction, normal, reflectivity: float, u: float):

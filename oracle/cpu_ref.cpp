@@ -286,7 +286,7 @@ namespace
 			// the depth alone: near(px, py) = (M0 X + M1 Y + k_near) / w_near is affine in the pixel position, and so is
 			// far - near.  Its frustum is a pinhole's: every near-to-far line passes through the eye, so that
 			// near = eye + kappa * (far - near) with ONE kappa = n / (f - n) for the whole frame.  The constants are worked out
-			// here in binary64, in this order of operations, and rounded to binary32 once (rt_amd/csrc/render.hip has the same
+			// here in binary64, in this order of operations, and rounded to binary32 once (rt_amd/csrc/frame_setup.cpp has the same
 			// lines).  Whether a matrix IS a pinhole's is decided from the same numbers: w constant over the frame, and the
 			// near point's motion per pixel within 1e-5 (relative) of kappa times the near-to-far vector's — a slack of
 			// 1e-10 of a pixel step, far below what binary32 resolves; an orthographic or sheared frustum fails it and takes the
@@ -1024,6 +1024,26 @@ extern "C" int oracle_primary_ray(const rt_hip_scene* scene, uint32_t width, uin
 	out_dir[1] = r.dir.y;
 	out_dir[2] = r.dir.z;
 	return f.pinhole_rays ? 1 : (f.eye_rays ? 2 : 0);
+}
+
+extern "C" void oracle_frame_constants(const rt_hip_scene* scene, uint32_t width, uint32_t height, uint64_t seed, uint32_t* out)
+{
+	const frame f = make_frame(scene, width, height, seed, ORACLE_TRACE_ITERATIVE);
+	uint32_t n = 0;
+	const auto put = [&](const float* values, int count) {
+		std::memcpy(out + n, values, sizeof(float) * static_cast<size_t>(count));
+		n += static_cast<uint32_t>(count);
+	};
+	out[n++] = f.pinhole_rays ? 1u : 0u;
+	out[n++] = f.eye_rays ? 1u : 0u;
+	put(f.ray_d0, 3), put(f.ray_d1, 3), put(f.ray_d2, 3), put(f.ray_j1, 3), put(f.ray_j2, 3), put(f.ray_eye, 3);
+	put(f.eye_q0, 3), put(f.eye_q1, 3), put(f.eye_q2, 3), put(f.eye_jq1, 3), put(f.eye_jq2, 3);
+	put(&f.eye_w0, 1), put(&f.eye_w1, 1), put(&f.eye_w2, 1), put(&f.eye_jw1, 1), put(&f.eye_jw2, 1);
+	put(f.eye_e, 3), put(&f.eye_zws, 1);
+	put(f.mx, 4), put(f.my, 4), put(f.k_near, 4), put(f.k_far, 4);
+	put(&f.sx, 1);
+	out[n++] = f.keys.a;
+	out[n++] = f.keys.b;
 }
 
 extern "C" void oracle_dielectric_direction(const float* dir, const float* normal, float reflectivity, float u, float* out_dir, float* out_reflect_prob)

@@ -93,6 +93,11 @@ int oracle_hits_box(const float* origin, const float* dir, const float* center, 
  * returns 1 if the matrix was taken as a pinhole camera's, 2 as a perspective matrix with a finite eye (the eye form),
  * 0 if it went through the general homogeneous form */
 int oracle_primary_ray(const rt_hip_scene* scene, uint32_t width, uint32_t height, uint32_t x, uint32_t y, float ka, float kb, float* out_origin, float* out_dir);
+/* make_frame's constants for a frame of this size and seed, as 63 bit patterns: pinhole_rays, eye_rays (0 / 1); ray_d0[3], ray_d1[3],
+ * ray_d2[3], ray_j1[3], ray_j2[3], ray_eye[3]; eye_q0[3], eye_q1[3], eye_q2[3], eye_jq1[3], eye_jq2[3], eye_w0, eye_w1, eye_w2, eye_jw1,
+ * eye_jw2, eye_e[3], eye_zws; mx[4], my[4], k_near[4], k_far[4]; sx; the two halves of the mixed seed */
+#define ORACLE_FRAME_CONSTANTS 63
+void oracle_frame_constants(const rt_hip_scene* scene, uint32_t width, uint32_t height, uint64_t seed, uint32_t* out);
 
 #ifdef __cplusplus
 }

@@ -15,6 +15,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "frame_setup.hpp" // (frame_keys: the mixed seed, made on the host)
 
 namespace rt_hip
 {
@@ -246,20 +247,7 @@ namespace rt_hip
 		return x;
 	}
 
-	struct frame_keys
-	{
-		uint32_t a, b;
-	};
-
-	__host__ inline frame_keys make_frame_keys(uint64_t seed) // the splitmix64 finaliser: a bijection of 64-bit words
-	{
-		uint64_t z = seed + 0x9E3779B97F4A7C15ull;
-		z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-		z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-		z ^= z >> 31;
-		return { static_cast<uint32_t>(z), static_cast<uint32_t>(z >> 32) };
-	}
-
+	// (frame_keys and make_frame_keys, the host's half of this: frame_setup.hpp)
 	__device__ __forceinline__ uint32_t pixel_function_key(uint32_t frame_a, uint32_t pixel_index) { return hash32(pixel_index ^ frame_a); }
 	__device__ __forceinline__ uint32_t pixel_stride(uint32_t frame_b, uint32_t function_key) { return hash32(function_key ^ frame_b) | 1u; }
 	// stream position before the first draw of sample `sample_index`: 4096 draws are reserved per sample

@@ -6,6 +6,7 @@
 //   frame.hip     the caller's frame buffer: the module-owned page-locked frame and its delivery threads (the default),
 //                 the opt-in page-lock of the caller's own buffer, NUMA placement
 //   render.hip    one launch (rt_hip_render_device), the work counters, the single-GPU drop-in rt_hip_render
+//   frame_setup.cpp, launch_plan.cpp   (host compiler, no HIP) what a launch is refused for, its per-frame constants, its plan
 //   multi.hip     rt_hip_render on several GPUs: stripes, one gather, assemble
 //   group.hip     rt_hip_render as one rank of a frame group (rank processes storing into one shared back buffer)
 //   kernels.hip   the gfx950 kernels (compiled twice: parity contract and RT_HIP_FLAG_FAST arithmetic)
@@ -135,23 +136,6 @@ namespace rt_hip
 	inline double seconds_since(std::chrono::steady_clock::time_point t0)
 	{
 		return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-	}
-
-	inline bool valid_partition(const rt_hip_partition& p)
-	{
-		return p.world && p.rank < p.world && p.stripe_rows;
-	}
-
-	inline uint32_t local_rows_of(uint32_t height, uint32_t rank, uint32_t world, uint32_t stripe_rows)
-	{
-		const uint32_t stripes = (height + stripe_rows - 1) / stripe_rows;
-		uint32_t rows = 0;
-		for (uint32_t b = rank; b < stripes; b += world)
-		{
-			const uint32_t y0 = b * stripe_rows;
-			rows += (height - y0 < stripe_rows) ? height - y0 : stripe_rows;
-		}
-		return rows;
 	}
 
 	inline float elapsed_or_zero(hipEvent_t from, hipEvent_t to)

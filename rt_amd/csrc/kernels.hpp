@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "launch_plan.hpp" // (the launch policy: queue_params, the thresholds, launch_plan)
+#include "frame_setup.hpp" // (frame_params, the kernels' per-frame uniforms, and the host code that fills them)
 
 namespace rt_hip
 {
@@ -66,54 +67,6 @@ namespace rt_hip
 		scatter_lambert = 0,	// mg_ray_tracer.cpp:110-123
 		scatter_metal = 1,		// mg_ray_tracer.cpp:126-140
 		scatter_dielectric = 2	// sm_ray_tracer.cpp:181-219 (opt-in)
-	};
-
-	// Per-frame uniforms (kernel arguments -> SGPRs).
-	struct frame_params
-	{
-		uint32_t width, height;			   // full frame
-		uint32_t local_rows;			   // rows this rank renders (compact buffer height in use)
-		uint32_t rank, world, stripe_rows; // rt_hip_partition
-		uint32_t stripe_shift;			   // log2(stripe_rows) if that is a power of two, else 0xFFFFFFFF (general division)
-		uint32_t frame_rows;			   // != 0: the output buffers are the WHOLE frame, a pixel goes to its image row (several
-										   // GPUs storing straight into one host frame); 0: this rank's compact stripe buffer
-		uint32_t samples_per_pixel, max_bounces;
-		uint32_t frame_key_a, frame_key_b;  // the two halves of the mixed 64-bit seed (contract.hpp, random streams)
-		float sx, neg_sy;				   // 2/W and -(2/H): ndc = (fma(px, sx, -1), fma(py, neg_sy, 1))
-		// inverse view-projection, pre-split for depth 0 / depth 1 (camera.hpp:42-48):
-		// row_r(depth) = fma(mx[r], ndc.x, fma(my[r], ndc.y, k[r])),  k_near[r] = fma(M[r][2], 0, M[r][3]),
-		// k_far[r] = fma(M[r][2], 1, M[r][3])
-		float mx[4], my[4], k_near[4], k_far[4];
-		// Contract v4, primary rays.  For a camera built as in camera.hpp:122-137 the last row of the inverse view-projection
-		// does not depend on x and y, so w is a per-frame constant, the un-projected near and far points are AFFINE in the
-		// pixel position, and every near-to-far line passes through the eye: a PINHOLE.  pinhole != 0 says the matrix is one
-		// (decided on the host from binary64 constants, render.hip; the oracle has the same lines) and the kernels then use
-		//   base_c   = fma(ray_d1[c], x, fma(ray_d2[c], y, ray_d0[c]))          once per pixel (x, y: its column and row)
-		//   toward_c = fma(ray_j1[c], ka, fma(ray_j2[c], kb, base_c))           per sample; (ka, kb) = the jitter's numerators,
-		//                                                                        ray_j = ray_d * 2^-24
-		//   origin_c = ray_eye[c] + toward_c                                    the near point (ray_d holds kappa * (far - near)
-		//                                                                        = near - eye, kappa = near / (far - near))
-		// The scalar-register kernels are built for ONE form; mx .. k_far above serve the preview and any other matrix (an
-		// orthographic or sheared frustum, a w that varies over the frame: the homogeneous form with one division per sample).
-		uint32_t pinhole;
-		float ray_d0[3], ray_d1[3], ray_d2[3];
-		float ray_j1[3], ray_j2[3];
-		float ray_eye[3];
-		// eye_form != 0: the matrix is a PERSPECTIVE one (its depth column Z has a finite point E = Z.xyz / Z.w: the eye every
-		// near-to-far line passes through) — what the general-camera kernels use for a camera that is not axis-aligned.  With
-		// N = the homogeneous near point, N' = N.xyz - E N.w and s = sign(-Z.w), both s N' and s N.w are affine in the pixel
-		// position (binary64 constants, like the pinhole's):
-		//   base_c = fma(eye_q1[c], x, fma(eye_q2[c], y, eye_q0[c])),   base_w = fma(eye_w1, x, fma(eye_w2, y, eye_w0))    per pixel
-		//   t_c    = fma(eye_jq1[c], ka, fma(eye_jq2[c], kb, base_c)),  ws     = fma(eye_jw1, ka, fma(eye_jw2, kb, base_w)) per sample
-		//   origin_c = fma(t_c, 1 / ws, eye_e[c]);   toward = t, negated if ws * (ws + eye_zws) < 0   (= N.w F.w < 0)
-		// One division per sample and no far point.  A matrix without a finite eye (an orthographic frustum) takes the
-		// homogeneous form from mx .. k_far above.
-		uint32_t eye_form; // 1 as above; 2: additionally s N.w and s F.w keep one sign and stay deep inside the reciprocal's band over the whole frame (render.hip): no guard, no flip
-		float eye_q0[3], eye_q1[3], eye_q2[3];
-		float eye_jq1[3], eye_jq2[3];
-		float eye_w0, eye_w1, eye_w2, eye_jw1, eye_jw2;
-		float eye_e[3];
-		float eye_zws;
 	};
 
 	// the whole scene of the `small` kernel, passed by value as a kernel argument (-> SGPRs); host copy kept by the context

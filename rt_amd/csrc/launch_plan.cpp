@@ -9,7 +9,7 @@ namespace rt_hip
 	uint32_t choose_kernel(uint32_t n_spheres, uint32_t n_planes, bool planes_tame, uint32_t flags, uint32_t samples_per_pixel, bool perspective, uint64_t pixels)
 	{
 		const uint32_t primitives = n_spheres + n_planes;
-		if (flags & RT_HIP_FLAG_BVH) // (render.hip refuses it with the FORCE_ flags, and builds the hierarchy first)
+		if (flags & RT_HIP_FLAG_BVH) // (check_render_request refuses it with the FORCE_ flags; render.hip builds the hierarchy first)
 			return RT_HIP_KERNEL_BVH;
 		if (flags & RT_HIP_FLAG_FORCE_STREAMED)
 			return RT_HIP_KERNEL_STREAMED;
