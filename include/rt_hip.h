@@ -466,6 +466,83 @@ RT_HIP_API rt_hip_status rt_hip_render(rt_hip_ctx* ctx,
 							float* rgb_f32,
 							rt_hip_stats* stats);
 
+/* ---- progressive frames: resumable sample passes ------------------------------------------------------------------ */
+/*
+ * A frame in PASSES: every call traces the next run of samples of every pixel and leaves the frame as it then stands, so that a
+ * caller sees a noisy frame at once and watches it converge while the camera rests.  The arithmetic contract makes this exact
+ * (DESIGN.md §3.6): a pixel's value is the fold, in chunk order, of sums of 16 consecutive samples, and a sample's random window
+ * does not depend on the sample count — so the frame after samples [0, s) is, BIT FOR BIT, the one-shot frame of the same scene
+ * at samples_per_pixel = s, and the frame after the last pass is rt_hip_render's.  A pixel's running sum lives between passes
+ * in an accumulator of 3 floats per pixel.
+ * Additions to ABI 6 (RT_HIP_ABI_VERSION stays 6): a caller that may meet an older library looks them up with dlsym.
+ * Both entry points take RT_HIP_FLAG_NONE, RT_HIP_FLAG_SM_MATERIALS, RT_HIP_FLAG_BVH, RT_HIP_FLAG_BVH_DEVICE_BUILD and
+ * RT_HIP_FLAG_STATS (the device level keeps its counters anyway, as rt_hip_render_device does) and refuse every other flag with RT_HIP_UNSUPPORTED and a message that
+ * names it: passes are built for the parity contract's tile-per-wave kernels only.  kernel_variant is RT_HIP_KERNEL_RESIDENT,
+ * or RT_HIP_KERNEL_BVH — with RT_HIP_FLAG_BVH, and for every scene of the streamed kernel's size (above about 1300 primitives)
+ * with or without the flag.  samples_per_pixel may be anything up to 2^20 (beyond that the samples' windows alias): rt_hip_render's
+ * limit of 4096 applies to ONE PASS, not to the frame; a pass that is too large is refused with RT_HIP_UNSUPPORTED.
+ * What passes cost next to the one-shot frame through the same kernel (per pass: a launch, 12 bytes per pixel read and
+ * written, the per-pixel finish): DESIGN.md §3.6 says what has been measured (tools/progressive_bench.py); nothing here
+ * promises more than it says.
+ */
+typedef struct rt_hip_progress
+{
+	uint32_t samples_done;	/* samples per pixel the delivered frame holds */
+	uint32_t samples_total; /* the scene's samples_per_pixel */
+	uint32_t passes;		/* passes launched for this accumulation so far */
+	uint32_t restarted;		/* 1: this call started a new accumulation (the first call, or something the frame depends on changed) */
+} rt_hip_progress;
+
+/*
+ * Device level: samples [first_sample, first_sample + n_samples) of the resident scene, folded onto d_accum; d_rgba8 (and
+ * d_rgb_f32, optional) receive the frame at first_sample + n_samples samples per pixel.  Buffers, partition, seed and stream as
+ * for rt_hip_render_device (streams are keyed by the global pixel).
+ *   first_sample  a multiple of 16 (else RT_HIP_INVALID_ARGUMENT).  0 starts an accumulation: d_accum is not read, and need not
+ *                 be cleared.
+ *   n_samples     a multiple of 16, or whatever reaches the scene's samples_per_pixel (the last pass)
+ *   d_accum       DEVICE buffer, padded_local_rows x width x 3 floats, the caller's to keep from pass to pass: pass k must find
+ *                 what pass k-1 of the same scene, size, seed, partition and flags left
+ */
+RT_HIP_API rt_hip_status rt_hip_render_pass_device(rt_hip_ctx* ctx,
+										uint32_t width,
+										uint32_t height,
+										uint64_t seed,
+										uint32_t flags,
+										const rt_hip_partition* part, /* NULL = whole image */
+										uint32_t first_sample,
+										uint32_t n_samples,
+										float* d_accum,
+										uint32_t* d_rgba8,
+										float* d_rgb_f32,
+										void* stream);
+
+/*
+ * Drop-in level: rt_hip_render in passes.  Every call traces the next pass_samples samples (rounded up to a multiple of 16,
+ * clamped to what is left; 0 = all that is left) of the accumulation in flight and fills `pixels_rgba8888` (and rgb_f32) with
+ * the frame as it then stands — or starts a new accumulation, if anything the frame depends on differs from the call before:
+ * the columns' fingerprint, samples_per_pixel, max_bounces, the matrix, the size, the seed, RT_HIP_FLAG_SM_MATERIALS.  (A
+ * caller keeps the seed constant while the camera rests.)  The accumulator belongs to the context: 12 bytes per pixel, grown
+ * on demand, freed with it.  The frame travels as in rt_hip_render without RT_HIP_FLAG_PERSISTENT_FRAME: the caller's
+ * buffer is plain memory and may be another one on every call.
+ *   A call on a FINISHED accumulation launches nothing: it delivers the finished frame again, leaves `passes` as it was, and
+ *   reports stats of zero work (primary_samples = segments = 0, render_ms = 0, kernel_variant = RT_HIP_KERNEL_NONE).
+ *   stats         optional: THIS PASS — primary_samples = pixels x the pass's samples, segments = the pass's; summed over the
+ *                 passes of a frame they are the one-shot frame's.
+ *   out_progress  optional.
+ * Contexts from rt_hip_create only: multi-GPU, rank and frame-group contexts return RT_HIP_UNSUPPORTED.
+ */
+RT_HIP_API rt_hip_status rt_hip_render_progressive(rt_hip_ctx* ctx,
+										const rt_hip_scene* scene,
+										uint32_t* pixels_rgba8888,
+										uint32_t width,
+										uint32_t height,
+										uint64_t seed,
+										uint32_t flags,
+										uint32_t pass_samples,
+										float* rgb_f32,
+										rt_hip_stats* stats,
+										rt_hip_progress* out_progress);
+
 /* Drop the page-lock taken under RT_HIP_FLAG_PERSISTENT_FRAME (see there).  Waits for the context's stream first. */
 RT_HIP_API void rt_hip_forget_frame(rt_hip_ctx* ctx);
 

@@ -137,6 +137,15 @@ class RtHipPhases(C.Structure):
         return d
 
 
+class RtHipProgress(C.Structure):
+    """``rt_hip_progress`` (include/rt_hip.h): where a progressive frame stands after a call of rt_hip_render_progressive."""
+
+    _fields_ = [("samples_done", C.c_uint32), ("samples_total", C.c_uint32), ("passes", C.c_uint32), ("restarted", C.c_uint32)]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 # every symbol include/rt_hip.h declares: (name, restype, argtypes)
 RT_HIP_SYMBOLS = [
     ("rt_hip_abi_version", C.c_uint32, []),
@@ -169,6 +178,16 @@ RT_HIP_SYMBOLS = [
         "rt_hip_render",
         C.c_int,
         [C.c_void_p, C.POINTER(RtHipScene), C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p, C.POINTER(RtHipStats)],
+    ),
+    (
+        "rt_hip_render_pass_device",
+        C.c_int,
+        [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(RtHipPartition), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    ),
+    (
+        "rt_hip_render_progressive",
+        C.c_int,
+        [C.c_void_p, C.POINTER(RtHipScene), C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(RtHipStats), C.POINTER(RtHipProgress)],
     ),
     ("rt_hip_forget_frame", None, [C.c_void_p]),
     ("rt_hip_live_frame_locks", C.c_uint32, []),

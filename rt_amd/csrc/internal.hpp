@@ -7,6 +7,8 @@
 //                 the opt-in page-lock of the caller's own buffer, NUMA placement
 //   render.hip    one launch (rt_hip_render_device), the work counters, the single-GPU drop-in rt_hip_render
 //   frame_setup.cpp, launch_plan.cpp   (host compiler, no HIP) what a launch is refused for, its per-frame constants, its plan
+//   passes.hip    a frame in resumable passes: rt_hip_render_progressive (sequencing: progressive.cpp, host compiler; one pass at the
+//                 device level, rt_hip_render_pass_device, is render.hip's)
 //   multi.hip     rt_hip_render on several GPUs: stripes, one gather, assemble
 //   group.hip     rt_hip_render as one rank of a frame group (rank processes storing into one shared back buffer)
 //   kernels.hip   the gfx950 kernels (compiled twice: parity contract and RT_HIP_FLAG_FAST arithmetic)
@@ -21,6 +23,7 @@
 #include "delivery.hpp"
 #include "frame_group.hpp"
 #include "kernels.hpp"
+#include "progressive.hpp"
 
 #include <rccl/rccl.h>
 
@@ -231,6 +234,12 @@ struct rt_hip_ctx
 
 	rt_hip_stats stats{};
 
+	// ---- a frame in passes (rt_hip_render_progressive, passes.hip) ----
+	rt_hip::pass_state progressive;			  // the accumulation in flight
+	uint32_t progressive_passes = 0;		  // passes launched for it so far
+	rt_hip::device_buffer accum;			  // the pixels' running sums: 3 floats per pixel, kept from pass to pass
+	std::vector<uint32_t> progressive_frame;  // the finished frame, kept on the host for calls that come after the last pass
+
 	rt_hip_ctx() = default;
 	rt_hip_ctx(const rt_hip_ctx&) = delete;
 	rt_hip_ctx& operator=(const rt_hip_ctx&) = delete;
@@ -278,7 +287,14 @@ namespace rt_hip
 	// keep_stats: bracket the launch with timing events, zero the work counters before it and read them back after it.  Without
 	// it NOTHING but the kernel is enqueued (the plug-in's call: rt_hip_render with stats == NULL).
 	// host_frame: d_rgba8 is page-locked host memory (a mapped frame): the tiles are cut for PCIe writes (choose_queue).
-	rt_hip_status render_device(rt_hip_ctx* ctx, uint32_t width, uint32_t height, uint64_t seed, uint32_t flags, const rt_hip_partition* part, uint32_t* d_rgba8, float* d_rgb_f32, void* stream, bool whole_frame_buffers, bool keep_stats, bool host_frame);
+	// pass: one pass of a progressive frame instead of the whole frame (NULL: the whole frame, as ever)
+	struct render_pass
+	{
+		uint32_t first_sample, n_samples; // whole chunks, or up to the scene's samples_per_pixel (checked by the caller)
+		float* d_accum;					  // the pixels' running sums, laid out like d_rgb_f32
+	};
+	rt_hip_status render_device(rt_hip_ctx* ctx, uint32_t width, uint32_t height, uint64_t seed, uint32_t flags, const rt_hip_partition* part, uint32_t* d_rgba8, float* d_rgb_f32, void* stream, bool whole_frame_buffers, bool keep_stats, bool host_frame,
+								const render_pass* pass = nullptr);
 	rt_hip_status fetch_member_stats(rt_hip_ctx* ctx);
 	rt_hip_stats stats_of_group_rank(const rt_hip_ctx* ctx, uint32_t rank);
 	void sum_group_stats(const rt_hip_ctx* ctx, rt_hip_stats* out);

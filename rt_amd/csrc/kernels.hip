@@ -438,8 +438,15 @@ namespace rt_hip
 		// something to round away), i.e. every frame while the user looks around.  Those frames used to fall to the
 		// LDS-resident kernel (+35 % on basic.toml); now they keep the scalar-register kernel, in a build of it that carries
 		// the 18 scalars of the general form INSTEAD of the 18 of the affine one (both would not fit its scalar registers).
-		template <int NS, bool SM, bool HALF = false, int NP = 0, bool GC = false>
-		__global__ __launch_bounds__(block_threads, waves_per_simd(NS, NP)) void render_queue(const frame_params p,
+		// PASS (progressive frames; the tile-per-wave whole-chunk kernels only): the launch traces chunks [first_chunk, first_chunk +
+		// q.chunks) of every pixel and its fold CONTINUES the pixel's running sum, kept between passes in an accumulator of 3 floats per pixel
+		// laid out like out_rgb.  p.samples_per_pixel is the sample count AFTER the pass, so the frame a pass leaves is the one-shot frame at that
+		// sample count, bit for bit.  A pass build is named by its scan code — scan_resident_pass, scan_bvh_pass: the kernel's first template
+		// argument, of which NS below is the scan proper — so that every other instantiation keeps its symbol, and with it its place in the
+		// listings the unchanged-kernels check compares (tools/kernel_listing_diff.py).  Neither the accumulator nor first_chunk is an argument
+		// of its own: they travel in words these builds do not read (rolling_buffers::accum, kernels.hpp).
+		template <int SCAN, bool SM, bool HALF = false, int NP = 0, bool GC = false>
+		__global__ __launch_bounds__(block_threads, waves_per_simd(scan_of(SCAN), NP)) void render_queue(const frame_params p,
 																	  const queue_params q,
 																	  const small_scene small,
 																	  const device_scene s,
@@ -449,8 +456,11 @@ namespace rt_hip
 																	  device_counters* __restrict__ counters,
 																	  unsigned long long* item_sums, // [NS < 0] chunk sums in transit: 16 bytes per item; [NS == scan_bvh] the device_bvh
 																									 // descriptor (rolling_buffers::bvh)
-																	  uint32_t* pixel_done)			 // [NS < 0] items arrived per pixel (zeroed in front of every launch)
+																	  uint32_t* pixel_done)			 // [NS < 0] items arrived per pixel (zeroed in front of every launch); [PASS] the accumulator
 		{
+			constexpr int NS = scan_of(SCAN);
+			constexpr bool PASS = scan_is_pass(SCAN);
+			static_assert(!PASS || !HALF, "passes are built for whole chunks only");
 			extern __shared__ float4 lds[];
 			// [NS > 0] 8 geometry (with the scatter function) + 8 shading float4s | [NS == scan_resident] all primitives; then the chunk slots
 			float4* const lds_geometry = lds;
@@ -489,6 +499,10 @@ namespace rt_hip
 			uint32_t region_runs[device_counters::regions] = {}, region_lanes[device_counters::regions] = {};
 #endif
 			constexpr bool ROLLING = NS < 0 && !BVH;
+			// [PASS] where the two words of a pass travel (launch_queue_sm): the first chunk in q.block_items, which only the rolling kernels
+			// read; the accumulator in pixel_done's place, which only they have
+			const uint32_t first_chunk = PASS ? q.block_items : 0u;
+			float* const accum = PASS ? reinterpret_cast<float*>(pixel_done) : nullptr;
 			// [BVH] the hierarchy, read once into scalar registers (its pointers and counts are the same for the whole launch)
 			device_bvh bvh{};
 			if constexpr (BVH)
@@ -589,8 +603,18 @@ namespace rt_hip
 						else
 						{
 							sum = sums[pixel * 3u + channel];
+							// [PASS] the pixel's running sum goes on from the earlier passes' chunks (pass 0: from the first chunk's sum, as in one shot)
+							float* running = nullptr;
+							if constexpr (PASS)
+							{
+								running = accum + (static_cast<size_t>(output_row(ly, p)) * p.width + lx) * 3u + channel;
+								if (first_chunk)
+									sum = *running + sum;
+							}
 							for (uint32_t c = 1; c < q.chunks; c++)
 								sum = sum + sums[((c << q.pixels_log2) + pixel) * 3u + channel];
+							if constexpr (PASS)
+								*running = sum;
 						}
 					}
 					const float mean = sum / static_cast<float>(p.samples_per_pixel);
@@ -626,11 +650,20 @@ namespace rt_hip
 						else
 						{
 							colour = { sums[pixel * 3u], sums[pixel * 3u + 1u], sums[pixel * 3u + 2u] };
+							float* running = nullptr;
+							if constexpr (PASS)
+							{
+								running = accum + (static_cast<size_t>(output_row(ly, p)) * p.width + lx) * 3u;
+								if (first_chunk)
+									colour = vec3{ running[0], running[1], running[2] } + colour;
+							}
 							for (uint32_t c = 1; c < q.chunks; c++)
 							{
 								const uint32_t at = ((c << q.pixels_log2) + pixel) * 3u;
 								colour = colour + vec3{ sums[at], sums[at + 1u], sums[at + 2u] };
 							}
+							if constexpr (PASS)
+								running[0] = colour.x, running[1] = colour.y, running[2] = colour.z;
 						}
 						finish_pixel(colour, p, lx, ly, out_rgba, out_rgb);
 					}
@@ -1048,7 +1081,7 @@ namespace rt_hip
 					}
 					st.keys.function_key = pixel_function_key(p.frame_key_a, gy * p.width + lx); // image_view::position_of, image.hpp:155-159
 					st.keys.stride = pixel_stride(p.frame_key_b, st.keys.function_key);
-					const uint32_t first = chunk * item_samples, end = min(first + item_samples, p.samples_per_pixel);
+					const uint32_t first = (PASS ? first_chunk + chunk : chunk) * item_samples, end = min(first + item_samples, p.samples_per_pixel);
 					st.sample = first;
 					st.sample_end = end;
 					st.window = sample_counter(st.keys.stride, first);
@@ -1592,6 +1625,20 @@ namespace rt_hip
 			}
 			// (the BVH kernel takes its hierarchy's descriptor in the item_sums argument's place)
 			unsigned long long* const item_sums = NS == scan_bvh ? reinterpret_cast<unsigned long long*>(const_cast<device_bvh*>(a.rolling.bvh)) : a.rolling.item_sums;
+#ifndef RT_HIP_FAST_BUILD
+			if constexpr (NS == scan_resident || NS == scan_bvh)
+			{
+				if (plan.build.pass) // (a pass of a progressive frame: first_chunk and the accumulator in the words these kernels do not read)
+				{
+					constexpr int pass_scan = NS == scan_bvh ? scan_bvh_pass : scan_resident_pass;
+					queue_params queue = plan.queue;
+					queue.block_items = plan.first_chunk;
+					hipLaunchKernelGGL((render_queue<pass_scan, SM, false, NP, GC>), grid, dim3(block_threads), plan.lds_bytes, a.stream, a.frame, queue, a.small, a.scene, a.scene.primitive_geometry, a.d_rgba8, a.d_rgb_f32, a.d_counters, item_sums,
+									   reinterpret_cast<uint32_t*>(a.rolling.accum));
+					return;
+				}
+			}
+#endif
 			if constexpr (!SM) // (the sm table keeps whole chunks: one set of kernels fewer to build)
 			{
 				if (plan.build.sub_chunk_items)

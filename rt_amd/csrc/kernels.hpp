@@ -89,6 +89,11 @@ namespace rt_hip
 		// RT_HIP_FLAG_BVH: the hierarchy's descriptor in device memory.  The BVH kernel keeps no sums in HBM; it is handed this in
 		// the item_sums argument's place (render_queue), so that no kernel's argument block changes.
 		const device_bvh* bvh = nullptr;
+		// A pass of a progressive frame (launch_plan::build.pass; render_queue<scan_*_pass, ..>): the pixels' running sums, 3 floats per pixel laid out
+		// like the float mean.  The pass builds are tile-per-wave kernels, which have no arrival counters: the accumulator is handed over in
+		// the pixel_done argument's place, and the pass's first chunk in queue_params::block_items, a word only the rolling kernels read —
+		// again no kernel's argument block changes.
+		float* accum = nullptr;
 	};
 
 	struct device_counters

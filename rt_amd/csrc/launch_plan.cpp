@@ -192,11 +192,19 @@ namespace rt_hip
 	{
 		launch_plan plan{};
 		const uint64_t pixels = static_cast<uint64_t>(request.width) * request.local_rows;
-		const uint32_t kernel = choose_kernel(request.n_spheres, request.n_planes, request.planes_tame, request.flags, request.samples_per_pixel, request.camera != camera_form::other, pixels);
+		uint32_t kernel = choose_kernel(request.n_spheres, request.n_planes, request.planes_tame, request.flags, request.samples_per_pixel, request.camera != camera_form::other, pixels);
+		// A pass of a progressive frame: only the tile-per-wave whole-chunk kernels have a pass build (kernels.hip, render_queue: PASS).  A scene
+		// of the streamed kernel's size goes through the sphere hierarchy, a scene of the scalar-register kernel's takes the resident one (as
+		// under RT_HIP_FLAG_FORCE_RESIDENT); the queue is cut for the PASS's samples, in whole chunks.  (The API admits no FORCE_ flag here.)
+		const bool pass = request.pass_samples != 0u;
+		if (pass)
+			kernel = (kernel == RT_HIP_KERNEL_BVH || kernel == RT_HIP_KERNEL_STREAMED) ? RT_HIP_KERNEL_BVH : RT_HIP_KERNEL_RESIDENT;
 		plan.variant = pixels ? kernel : static_cast<uint32_t>(RT_HIP_KERNEL_NONE);
 		const bool big_scene = plan.big_scene = kernel == RT_HIP_KERNEL_TILED || kernel == RT_HIP_KERNEL_STREAMED;
-		const queue_params queue = plan.queue = choose_queue(request.samples_per_pixel, request.width, request.local_rows, big_scene, request.host_frame, half_chunk_choice(request.flags), request.n_spheres + request.n_planes,
-															 kernel == RT_HIP_KERNEL_STREAMED && request.n_spheres >= sparse_launch_min_spheres);
+		const queue_params queue = plan.queue = choose_queue(pass ? request.pass_samples : request.samples_per_pixel, request.width, request.local_rows, big_scene, request.host_frame, pass ? 0 : half_chunk_choice(request.flags),
+															 request.n_spheres + request.n_planes, kernel == RT_HIP_KERNEL_STREAMED && request.n_spheres >= sparse_launch_min_spheres);
+		plan.build.pass = pass;
+		plan.first_chunk = pass ? request.pass_first_sample / sample_chunk : 0u;
 
 		// small scenes: one wave per tile, four tiles side by side per workgroup.  Big scenes: a persistent launch — what
 		// the device keeps resident, and no more lanes than items

@@ -105,8 +105,13 @@ namespace rt_hip
 		scan_tiled = -1,		  // rolling items; the primitives stream through one LDS tile per workgroup
 		scan_streamed = -2,		  // rolling items; wave-uniform scalar loads, sparse waves scan cooperatively
 		scan_streamed_dense = -3, // ... without the cooperative scan: frames that fill the device
-		scan_bvh = -4			  // RT_HIP_FLAG_BVH: a pixel tile per wave, spheres through the hierarchy
+		scan_bvh = -4,			  // RT_HIP_FLAG_BVH: a pixel tile per wave, spheres through the hierarchy
+		// the PASS builds of the two tile-per-wave scans (kernel_build::pass; progressive frames): the same scans, a fold that continues
+		scan_resident_pass = -5,
+		scan_bvh_pass = -6
 	};
+	constexpr bool scan_is_pass(int code) { return code == scan_resident_pass || code == scan_bvh_pass; }
+	constexpr int scan_of(int code) { return code == scan_resident_pass ? static_cast<int>(scan_resident) : (code == scan_bvh_pass ? static_cast<int>(scan_bvh) : code); } // the scan a build's code stands for
 	// the rolling kernels are launched persistent: as many workgroups as the device keeps resident (launch_cache, kernels.hpp)
 	constexpr bool scan_is_persistent(int scan) { return scan == scan_tiled || scan == scan_streamed || scan == scan_streamed_dense; }
 	constexpr unsigned persistent_cache_slots = 18; // { tiled, streamed, streamed for dense frames } x { mg, sm scatter table, fast arithmetic } x { whole chunks, sub-chunk items }
@@ -128,6 +133,10 @@ namespace rt_hip
 		uint32_t flags;		  // RT_HIP_FLAG_*
 		bool host_frame;	  // the packed pixels go to page-locked host memory (choose_queue)
 		bool fast_arithmetic; // RT_HIP_FLAG_FAST's build of the kernels (launch_render_fast)
+		// One PASS of a progressive frame (pass_samples != 0): samples [pass_first_sample, pass_first_sample + pass_samples) of every pixel,
+		// folded onto the pixels' running sums.  pass_first_sample is a multiple of sample_chunk; samples_per_pixel stays the frame's.
+		// Both 0: a frame in one launch, planned as it always was.
+		uint32_t pass_first_sample = 0, pass_samples = 0;
 	};
 
 	// the instantiation render_queue<scan, sm_table, sub_chunk_items, planes, general_camera>
@@ -138,6 +147,7 @@ namespace rt_hip
 		bool general_camera;  // GC: the frame is not a pinhole's (scalar-register kernels and the resident LDS scan)
 		bool sub_chunk_items; // HALF
 		bool sm_table;		  // SM: RT_HIP_FLAG_SM_MATERIALS
+		bool pass;			  // one pass of a progressive frame: the scan's PASS build (scan_resident_pass / scan_bvh_pass; `scan` stays the scan proper)
 	};
 
 	struct launch_plan
@@ -155,6 +165,7 @@ namespace rt_hip
 		size_t item_sums_bytes, pixel_done_bytes; // rolling_buffer_bytes
 		int persistent_slot; // index into launch_cache::persistent, or -1: not a persistent launch
 		int per_cu_cap;		 // persistent launches: workgroups per CU at most
+		uint32_t first_chunk; // a pass: the chunk of every pixel its items start at (queue.chunks is the PASS's chunk count); else 0
 	};
 	launch_plan plan_launch(const launch_request& request);
 }

@@ -41,9 +41,44 @@ extern "C" rt_hip_status rt_hip_render_device(rt_hip_ctx* ctx,
 	return render_device(ctx, width, height, seed, flags, part, d_rgba8, d_rgb_f32, stream, false, true, ctx && d_rgba8 && is_host_memory(ctx, d_rgba8));
 }
 
+// one pass of a progressive frame at the device level (rt_hip.h): samples [first_sample, first_sample + n_samples) of the
+// resident scene, folded onto the caller's accumulator
+extern "C" rt_hip_status rt_hip_render_pass_device(rt_hip_ctx* ctx,
+													   uint32_t width,
+													   uint32_t height,
+													   uint64_t seed,
+													   uint32_t flags,
+													   const rt_hip_partition* part,
+													   uint32_t first_sample,
+													   uint32_t n_samples,
+													   float* d_accum,
+													   uint32_t* d_rgba8,
+													   float* d_rgb_f32,
+													   void* stream)
+{
+	if (first_sample % sample_chunk)
+		return fail(RT_HIP_INVALID_ARGUMENT, "rt_hip_render_pass_device: first_sample %u is not a multiple of %u (a pass continues the chunk-wise fold of the pixel sums)", first_sample, sample_chunk);
+	if (!ctx || !d_accum || !d_rgba8)
+		return fail(RT_HIP_INVALID_ARGUMENT, "rt_hip_render_pass_device: NULL argument");
+	if (const char* const refused = refused_pass_flag(flags))
+		return fail(RT_HIP_UNSUPPORTED, "rt_hip_render_pass_device: %s is not available for passes (0x%x): they take RT_HIP_FLAG_SM_MATERIALS, RT_HIP_FLAG_BVH, RT_HIP_FLAG_BVH_DEVICE_BUILD and RT_HIP_FLAG_STATS", refused, flags);
+	if (!ctx->have_scene)
+		return fail(RT_HIP_NO_SCENE, "rt_hip_render_pass_device: no scene uploaded");
+	const uint32_t total = ctx->samples_per_pixel;
+	if (total > pass_max_samples_per_pixel)
+		return fail(RT_HIP_UNSUPPORTED, "rt_hip_render_pass_device: %u samples per pixel: the samples' random windows alias beyond %u", total, pass_max_samples_per_pixel);
+	if (!n_samples || first_sample >= total || n_samples > total - first_sample || (n_samples % sample_chunk && first_sample + n_samples != total))
+		return fail(RT_HIP_INVALID_ARGUMENT, "rt_hip_render_pass_device: samples [%u, %u + %u) are not whole chunks of %u within the scene's %u samples per pixel (the last pass alone may end on the sample count)", first_sample,
+					first_sample, n_samples, sample_chunk, total);
+	const render_pass pass = { first_sample, n_samples, d_accum };
+	// (RT_HIP_FLAG_STATS asks for what this call keeps anyway, as rt_hip_render_device does: it is not the launch's)
+	return render_device(ctx, width, height, seed, flags & pass_flag_mask, part, d_rgba8, d_rgb_f32, stream, false, true, is_host_memory(ctx, d_rgba8), &pass);
+}
+
 namespace rt_hip
 {
-rt_hip_status render_device(rt_hip_ctx* ctx, uint32_t width, uint32_t height, uint64_t seed, uint32_t flags, const rt_hip_partition* part, uint32_t* d_rgba8, float* d_rgb_f32, void* stream, bool whole_frame_buffers, bool keep_stats, bool host_frame)
+rt_hip_status render_device(rt_hip_ctx* ctx, uint32_t width, uint32_t height, uint64_t seed, uint32_t flags, const rt_hip_partition* part, uint32_t* d_rgba8, float* d_rgb_f32, void* stream, bool whole_frame_buffers, bool keep_stats, bool host_frame,
+							const render_pass* pass)
 {
 	if (!ctx || !d_rgba8)
 		return fail(RT_HIP_INVALID_ARGUMENT, "rt_hip_render_device: NULL argument");
@@ -56,7 +91,7 @@ rt_hip_status render_device(rt_hip_ctx* ctx, uint32_t width, uint32_t height, ui
 	if (flags & RT_HIP_FLAG_BVH)
 		if (const rt_hip_status st = ensure_bvh(ctx, checked.bvh_device_build, static_cast<hipStream_t>(stream), keep_stats))
 			return st;
-	const device_bvh* const bvh = (flags & RT_HIP_FLAG_BVH) ? ctx->bvh_descriptor : nullptr;
+	const device_bvh* bvh = (flags & RT_HIP_FLAG_BVH) ? ctx->bvh_descriptor : nullptr;
 
 	RT_HIP_TRY(hipSetDevice(ctx->device));
 	const hipStream_t s = static_cast<hipStream_t>(stream);
@@ -68,7 +103,8 @@ rt_hip_status render_device(rt_hip_ctx* ctx, uint32_t width, uint32_t height, ui
 
 	frame_request wanted{};
 	wanted.width = width, wanted.height = height, wanted.partition = checked.partition;
-	wanted.samples_per_pixel = ctx->samples_per_pixel, wanted.max_bounces = ctx->max_bounces;
+	// (a pass: the kernels' sample count is the one AFTER the pass — what its fold divides by, and where its last chunk ends)
+	wanted.samples_per_pixel = pass ? pass->first_sample + pass->n_samples : ctx->samples_per_pixel, wanted.max_bounces = ctx->max_bounces;
 	wanted.seed = seed, wanted.whole_frame_buffers = whole_frame_buffers;
 	std::copy(ctx->inverse_view_projection, ctx->inverse_view_projection + 16, wanted.inverse_view_projection);
 	const frame_params f = make_frame_params(wanted);
@@ -81,13 +117,26 @@ rt_hip_status render_device(rt_hip_ctx* ctx, uint32_t width, uint32_t height, ui
 	{
 		launch_request request{};
 		request.n_spheres = ctx->scene.n_spheres, request.n_planes = ctx->scene.n_planes, request.planes_tame = ctx->scene.planes_tame != 0;
-		request.width = width, request.local_rows = f.local_rows, request.samples_per_pixel = f.samples_per_pixel;
+		request.width = width, request.local_rows = f.local_rows, request.samples_per_pixel = pass ? ctx->samples_per_pixel : f.samples_per_pixel;
+		if (pass)
+			request.pass_first_sample = pass->first_sample, request.pass_samples = pass->n_samples;
 		request.camera = camera_form_of(f);
 		request.flags = flags, request.host_frame = host_frame, request.fast_arithmetic = (flags & RT_HIP_FLAG_FAST) != 0;
 		plan = plan_launch(request);
 		// small scenes: a pixel's chunk sums (one per 16 samples) are parked in LDS until the pixel is complete
+		if (pass && plan.slot_bytes > 48u * 1024u)
+			return fail(RT_HIP_UNSUPPORTED, "rt_hip_render_pass_device: a pass of %u samples is more than the kernels hold chunk sums for (4096 per pass; the frame's samples_per_pixel has no such limit)", pass->n_samples);
 		if (plan.slot_bytes > 48u * 1024u)
 			return fail(RT_HIP_UNSUPPORTED, "rt_hip_render_device: %u samples per pixel are more than the kernels hold chunk sums for (4096; the reference clamps to 1000, src/scene.cpp:544)", f.samples_per_pixel);
+		if (pass && plan.build.scan == scan_bvh && !bvh) // a pass of a scene of the streamed kernel's size goes through the hierarchy (plan_launch), flag or no flag
+		{
+			if (const rt_hip_status st = ensure_bvh(ctx, false, s, keep_stats))
+				return st;
+			RT_HIP_TRY(hipSetDevice(ctx->device));
+			rolling.bvh = bvh = ctx->bvh_descriptor;
+		}
+		if (pass)
+			rolling.accum = pass->d_accum;
 		// big scenes: they meet in HBM, 16 bytes per chunk (or per sample) of this rank's rows
 		if (plan.item_sums_bytes > ctx->item_sums.bytes && plan.queue.halves && plan.big_scene && ctx->item_sums.reserve(plan.item_sums_bytes) != hipSuccess)
 		{
@@ -98,7 +147,7 @@ rt_hip_status render_device(rt_hip_ctx* ctx, uint32_t width, uint32_t height, ui
 			plan = plan_launch(request);
 		}
 		if (plan.item_sums_bytes > (64ull << 30))
-			return fail(RT_HIP_UNSUPPORTED, "rt_hip_render_device: %ux%u at %u samples per pixel needs %zu GiB for the chunk sums of a scene of this size", width, height, f.samples_per_pixel, plan.item_sums_bytes >> 30);
+			return fail(RT_HIP_UNSUPPORTED, "%s: %ux%u at %u samples per pixel needs %zu GiB for the chunk sums of a scene of this size", pass ? "rt_hip_render_pass_device" : "rt_hip_render_device", width, height, f.samples_per_pixel, plan.item_sums_bytes >> 30);
 		if (plan.item_sums_bytes)
 		{
 			RT_HIP_TRY(ctx->item_sums.reserve(plan.item_sums_bytes));
@@ -138,7 +187,7 @@ rt_hip_status render_device(rt_hip_ctx* ctx, uint32_t width, uint32_t height, ui
 	}
 	ctx->render_recorded = keep_stats;
 	ctx->stats.kernel_variant = variant;
-	ctx->stats.primary_samples = static_cast<uint64_t>(f.local_rows) * width * ((flags & RT_HIP_FLAG_PREVIEW) ? 1u : f.samples_per_pixel);
+	ctx->stats.primary_samples = static_cast<uint64_t>(f.local_rows) * width * ((flags & RT_HIP_FLAG_PREVIEW) ? 1u : (pass ? pass->n_samples : f.samples_per_pixel));
 	if (!keep_stats) // the counters of this frame were not kept: nothing stale may be reported for it
 	{
 		ctx->stats.render_ms = 0.0f;

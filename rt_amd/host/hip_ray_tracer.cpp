@@ -123,6 +123,20 @@ namespace
 		return flags;
 	}
 
+	// RT_HIP_PROGRESSIVE=<samples per pass> makes render() one PASS of a progressive frame (rt_hip_render_progressive): every call adds
+	// that many samples per pixel to the frame in flight and shows it as it then stands, until the scene's samples_per_pixel are in —
+	// a noisy frame at once that converges while the camera rests; anything the frame depends on starts it again.  0 / unset: every
+	// render() is a whole frame.  (Not for the preview, which is one ray per pixel.)
+	uint32_t progressive_pass_samples()
+	{
+		static const uint32_t samples = []
+		{
+			const char* progressive = std::getenv("RT_HIP_PROGRESSIVE");
+			return progressive ? static_cast<uint32_t>(std::strtoul(progressive, nullptr, 0)) : 0u;
+		}();
+		return samples;
+	}
+
 	// ModeFlags: 0 = mg_ray_tracer's scatter table; RT_HIP_FLAG_SM_MATERIALS = sm_ray_tracer's (dielectrics refract);
 	// RT_HIP_FLAG_PREVIEW = the one-ray-per-pixel preview of src/renderers/rasterizer.cpp
 	template <uint32_t ModeFlags>
@@ -184,6 +198,14 @@ namespace
 			const char* fixed = std::getenv("RT_HIP_SEED");
 			const uint64_t seed = fixed ? std::strtoull(fixed, nullptr, 0) : ++frame_number;
 
+			if constexpr (ModeFlags != RT_HIP_FLAG_PREVIEW)
+				if (const uint32_t pass_samples = progressive_pass_samples())
+				{
+					// (a seed per frame would start the accumulation again on every call: RT_HIP_SEED, or 1, for all of them)
+					if (rt_hip_render_progressive(ctx, &s, pixels.data(), pixels.size().x, pixels.size().y, fixed ? seed : 1u, accel_flags() | ModeFlags, pass_samples, nullptr, nullptr, nullptr) != RT_HIP_OK)
+						std::cerr << "error: hip_ray_tracer: " << rt_hip_last_error() << "\n";
+					return;
+				}
 			if (rt_hip_render(ctx, &s, pixels.data(), pixels.size().x, pixels.size().y, seed, frame_flags() | accel_flags() | ModeFlags, nullptr, nullptr) != RT_HIP_OK)
 				std::cerr << "error: hip_ray_tracer: " << rt_hip_last_error() << "\n";
 		}

@@ -9,6 +9,9 @@
 //   --seed N     pin the random streams (exported to the renderer as RT_HIP_SEED)
 //   --frames N   render N frames, report the last
 //   --out file.ppm   write the frame (binary PPM, RGB)
+//   --progressive SAMPLES   the frame in passes of SAMPLES samples per pixel (exported to the renderer as RT_HIP_PROGRESSIVE):
+//                render() is called ceil(spp / SAMPLES) times — every call shows the frame as it stands — and the last frame,
+//                the same as without the option, is the one reported and written (hip renderers only; not together with --frames)
 //   --shared-frame NAME --rank R --world N   this process is rank R of N rt_headless processes that render ONE frame
 //                together (one per GPU: RT_HIP_DEVICE picks this one's): the back buffer is every process's mapping of the
 //                POSIX shared-memory object /NAME_frame (rank 0 creates it) and the plug-in joins the frame group
@@ -121,7 +124,8 @@ namespace
 int main(int argc, char** argv)
 {
 	std::string scene_path, renderer_name, out_path, shared_name;
-	unsigned width = 800, height = 600, spp = 0, bounces = 0, frames = 1, rank = 0, world = 1;
+	unsigned width = 800, height = 600, spp = 0, bounces = 0, frames = 1, rank = 0, world = 1, progressive = 0;
+	bool frames_given = false;
 	bool list = false;
 	// default renderer: the first whose name starts with "hip", else the first registered (reference: first "mg", :350)
 	for (auto& r : renderers::all())
@@ -161,11 +165,22 @@ int main(int argc, char** argv)
 		else if (arg == "--bounces"sv)
 			bounces = static_cast<unsigned>(std::strtoul(value(), nullptr, 10));
 		else if (arg == "--frames"sv)
-			frames = static_cast<unsigned>(std::strtoul(value(), nullptr, 10));
+			frames = static_cast<unsigned>(std::strtoul(value(), nullptr, 10)), frames_given = true;
 		else if (arg == "--seed"sv)
 			::setenv("RT_HIP_SEED", value(), 1);
 		else if (arg == "--out"sv)
 			out_path = value();
+		else if (arg == "--progressive"sv)
+		{
+			const char* const samples = value();
+			progressive = static_cast<unsigned>(std::strtoul(samples, nullptr, 10));
+			if (!progressive)
+			{
+				error("--progressive expects the samples per pass (>= 1)");
+				return 2;
+			}
+			::setenv("RT_HIP_PROGRESSIVE", std::to_string(progressive).c_str(), 1); // (the number as read here, whatever way it was spelled)
+		}
 		else if (arg == "--shared-frame"sv)
 			shared_name = value();
 		else if (arg == "--rank"sv)
@@ -174,7 +189,7 @@ int main(int argc, char** argv)
 			world = static_cast<unsigned>(std::strtoul(value(), nullptr, 10));
 		else if (arg == "--help"sv || arg == "-h"sv)
 		{
-			log("usage: rt_headless [--list] [--scene file.toml] [--renderer name] [--size WxH] [--spp N] [--bounces N] [--seed N] [--frames N] [--out file.ppm] [--shared-frame NAME --rank R --world N]");
+			log("usage: rt_headless [--list] [--scene file.toml] [--renderer name] [--size WxH] [--spp N] [--bounces N] [--seed N] [--frames N] [--out file.ppm] [--progressive SAMPLES] [--shared-frame NAME --rank R --world N]");
 			return 0;
 		}
 		else
@@ -197,6 +212,11 @@ int main(int argc, char** argv)
 		error("no known renderer with name '", renderer_name, "'");
 		return 1;
 	}
+	if (progressive && (frames_given || std::string_view{ desc->name }.substr(0, 3) != "hip"sv))
+	{
+		error("--progressive sets the number of frames itself (not with --frames) and needs a hip renderer, not '", desc->name, "'");
+		return 2;
+	}
 	std::unique_ptr<renderer_interface> renderer{ desc->create() };
 	log("created renderer: ", desc->name);
 
@@ -215,6 +235,11 @@ int main(int argc, char** argv)
 		scene.samples_per_pixel = spp;
 	if (bounces)
 		scene.max_bounces = bounces;
+	if (progressive)
+	{
+		const unsigned pass = (progressive + 15u) / 16u * 16u; // (passes are whole chunks of 16 samples: rt_hip_render_progressive rounds up)
+		frames = (scene.samples_per_pixel + pass - 1u) / pass;
+	}
 
 	image frame;
 	image_view pixels;

@@ -19,7 +19,7 @@ import ctypes as C
 import numpy as np
 
 from . import capi
-from .capi import RtHipPartition, RtHipPhases, RtHipScene, RtHipStats, check
+from .capi import RtHipPartition, RtHipPhases, RtHipProgress, RtHipScene, RtHipStats, check
 
 
 def local_rows(height: int, rank: int, world: int, stripe_rows: int = capi.RT_HIP_DEFAULT_STRIPE_ROWS) -> int:
@@ -177,6 +177,32 @@ class HipRayTracer:
         )
         return rgba, rgb, stats.as_dict() if want_stats else {}
 
+    def render_progressive(self, scene: RtHipScene, width: int, height: int, seed: int = 1, flags: int = 0, pass_samples: int = 16, want_rgb: bool = False, out: np.ndarray | None = None, stats: bool = True):
+        """rt_hip_render_progressive: the next `pass_samples` samples per pixel (0 = all that is left) of the frame in flight —
+        or of a new one, if anything the frame depends on changed.  Returns (rgba8 uint32[H, W], rgb float32[H, W, 3] or None,
+        stats dict of THIS pass, progress dict: samples_done, samples_total, passes, restarted).  The frame returned is the
+        one-shot frame at samples_per_pixel = samples_done, bit for bit."""
+        stats_pod, progress = RtHipStats(), RtHipProgress()
+        rgba = out if out is not None else np.empty((height, width), dtype=np.uint32)
+        assert rgba.dtype == np.uint32 and rgba.shape == (height, width) and rgba.flags.c_contiguous
+        rgb = np.empty((height, width, 3), dtype=np.float32) if want_rgb else None
+        check(
+            self._lib.rt_hip_render_progressive(
+                self._ctx,
+                C.byref(scene),
+                rgba.ctypes.data,
+                width,
+                height,
+                seed,
+                flags,
+                pass_samples,
+                rgb.ctypes.data if rgb is not None else None,
+                C.byref(stats_pod) if stats else None,
+                C.byref(progress),
+            )
+        )
+        return rgba, rgb, stats_pod.as_dict() if stats else {}, progress.as_dict()
+
     def forget_frame(self) -> None:
         """Drop the page-lock on the back buffer last rendered into with RT_HIP_FLAG_PERSISTENT_FRAME."""
         self._lib.rt_hip_forget_frame(self._ctx)
@@ -202,6 +228,25 @@ class HipRayTracer:
     ) -> None:
         part = C.byref(RtHipPartition(*partition)) if partition is not None else None
         check(self._lib.rt_hip_render_device(self._ctx, width, height, seed, flags, part, d_rgba8, d_rgb_f32, stream))
+
+    def render_pass_device(
+        self,
+        width: int,
+        height: int,
+        first_sample: int,
+        n_samples: int,
+        d_accum: int,
+        d_rgba8: int,
+        seed: int = 1,
+        flags: int = 0,
+        partition: tuple | None = None,
+        d_rgb_f32: int | None = None,
+        stream: int | None = None,
+    ) -> None:
+        """rt_hip_render_pass_device: samples [first_sample, first_sample + n_samples) of the resident scene, folded onto the
+        caller's accumulator `d_accum` (padded_local_rows x width x 3 floats on the device, kept from pass to pass)."""
+        part = C.byref(RtHipPartition(*partition)) if partition is not None else None
+        check(self._lib.rt_hip_render_pass_device(self._ctx, width, height, seed, flags, part, first_sample, n_samples, d_accum, d_rgba8, d_rgb_f32, stream))
 
     def assemble_device(self, width: int, height: int, world: int, stripe_rows: int, d_gathered: int, d_frame: int, stream: int | None = None) -> None:
         check(self._lib.rt_hip_assemble_device(self._ctx, width, height, world, stripe_rows, d_gathered, d_frame, stream))
