@@ -21,7 +21,7 @@ HIP_HDR  := rt_amd/csrc/kernels.hpp rt_amd/csrc/launch_plan.hpp rt_amd/csrc/prog
 HOST_SRC := rt_amd/host/host_capi.cpp rt_amd/host/scene.cpp rt_amd/host/toml_subset.cpp
 HOST_HDR := $(wildcard rt_amd/host/*.hpp) rt_amd/host/host_capi.h rt_amd/host/named_colours.inc include/rt_hip.h
 
-all: $(LIBDIR)/librt_hip.so $(LIBDIR)/librt_hip_kat.so $(LIBDIR)/librt_host.so rt_amd/bin/rt_headless tests/native/lbvh_reference oracle
+all: $(LIBDIR)/librt_hip.so $(LIBDIR)/librt_hip_kat.so $(LIBDIR)/librt_host.so rt_amd/bin/rt_headless tests/native/lbvh_reference tests/native/libbox_reference.so oracle
 
 # kernels.hip is compiled twice: the parity contract (contraction off), and RT_HIP_FLAG_FAST's arithmetic
 # (-DRT_HIP_FAST_BUILD -ffp-contract=fast: only launch_render_fast comes out of that one)
@@ -98,6 +98,11 @@ rt_amd/bin/rt_headless: $(HEADLESS_SRC) $(HOST_HDR) $(LIBDIR)/librt_hip.so
 tests/native/lbvh_reference: tests/native/lbvh_reference.cpp rt_amd/csrc/bvh_build.hpp
 	$(CXX) -std=c++20 -O2 -ffp-contract=off -Wall -Wextra $< -o $@
 
+# the CPU restatement of RT_HIP_FLAG_TRACE_BOXES: the oracle's own translation unit with a test_boxes that hits (it includes
+# oracle/cpu_ref.cpp and restates nothing of it), g++ alone, the oracle's strict flags; tests/box_reference.py binds it
+tests/native/libbox_reference.so: tests/native/box_reference.cpp oracle/cpu_ref.cpp oracle/cpu_ref.h include/rt_hip.h
+	$(CXX) -O2 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -fno-math-errno -mfma -Wall -Wextra -shared $< -o $@ -lpthread
+
 oracle:
 	$(MAKE) -C oracle
 
@@ -113,7 +118,7 @@ oracle/_ref/soagen_columns: tests/native/soagen_columns.cpp $(LIBDIR)/librt_hip.
 endif
 
 clean:
-	rm -f $(LIBDIR)/*.so rt_amd/bin/rt_headless tests/native/lbvh_reference
+	rm -f $(LIBDIR)/*.so rt_amd/bin/rt_headless tests/native/lbvh_reference tests/native/libbox_reference.so
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean variant

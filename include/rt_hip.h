@@ -112,8 +112,9 @@ typedef struct rt_hip_scene
 	float inverse_view_projection[16];
 
 	/* rt::boxes — center_x..center_z/extents_x..extents_z/material columns (src/soa.toml:35-45); extents are half
-	 * sizes (muu::bounding_box).  mg_ray_tracer never hits boxes (mg_ray_tracer.cpp:89-93): only the preview
-	 * (RT_HIP_FLAG_PREVIEW, reference src/renderers/rasterizer.cpp:57) draws them. */
+	 * sizes (muu::bounding_box).  mg_ray_tracer never hits boxes (mg_ray_tracer.cpp:89-93): the preview
+	 * (RT_HIP_FLAG_PREVIEW, reference src/renderers/rasterizer.cpp:57) draws them, and the traced frame does under
+	 * RT_HIP_FLAG_TRACE_BOXES only. */
 	uint32_t n_boxes;
 	const float* box_center_x;
 	const float* box_center_y;
@@ -147,7 +148,7 @@ typedef struct rt_hip_stats
 	uint64_t primary_samples; /* pixels rendered by this rank x samples_per_pixel */
 	uint64_t segments;		  /* calls of trace() that did not return at the bounce limit check, i.e. closest-hit queries */
 	uint64_t sphere_tests;	  /* segments x n_spheres (also under RT_HIP_FLAG_BVH: the linear scan's count, not the spheres the tree visited) */
-	uint64_t plane_tests;	  /* segments x n_planes */
+	uint64_t plane_tests;	  /* segments x n_planes (box tests under RT_HIP_FLAG_TRACE_BOXES are not counted) */
 	float render_ms;		  /* device time of the render kernel(s), HIP events on the launch stream */
 	float upload_ms;		  /* host wall time of the last scene upload */
 	float readback_ms;		  /* rt_hip_render only: host wall time from "kernels done" to "frame in the caller's buffer" */
@@ -237,7 +238,28 @@ enum
 	 * builder: asking for the other one after the same upload rebuilds it.  `upload_ms` includes the build on frames that keep
 	 * stats (the call then waits for it).  Takes scenes of up to 2^26 spheres.  Refused (RT_HIP_UNSUPPORTED) without
 	 * RT_HIP_FLAG_BVH and wherever RT_HIP_FLAG_BVH is refused; ignored with RT_HIP_FLAG_PREVIEW. */
-	RT_HIP_FLAG_BVH_DEVICE_BUILD = 1u << 11
+	RT_HIP_FLAG_BVH_DEVICE_BUILD = 1u << 11,
+	/* (bit 12 stays unassigned: the tests pin 1u << 12 as "unknown flag bits") */
+	/* OPT-IN: trace the scene's BOXES.  The reference's path tracers never hit a box (test_boxes is a stub that always misses,
+	 * mg_ray_tracer.cpp:89-93, sm_ray_tracer.cpp:90), and without this flag neither does the module: a scene with boxes renders
+	 * exactly as it always did.  With it every closest-hit query also scans the boxes — the slab test of the preview, accepted
+	 * like spheres and planes (nothing nearer than 0.001, ties to the lower index), combined as the reference's own line
+	 * mg_ray_tracer.cpp:162 combines its stub: a box wins a distance tie against a sphere or a plane — and a box hit is shaded
+	 * through box_material like any other primitive, from its outward face normal (DESIGN.md §3.7 has the contract; the frame is
+	 * held bit for bit to its CPU restatement, tests/native/box_reference.cpp).  kernel_variant reports RT_HIP_KERNEL_RESIDENT, or
+	 * RT_HIP_KERNEL_BVH with RT_HIP_FLAG_BVH and for scenes of the streamed kernel's size (the hierarchy is then built as for
+	 * RT_HIP_FLAG_BVH); scenes of the scalar-register kernel's size take the resident one.  Box tests are not counted: `segments`
+	 * counts as before, rt_hip_stats is unchanged.
+	 * Works with RT_HIP_FLAG_SM_MATERIALS, RT_HIP_FLAG_BVH, RT_HIP_FLAG_BVH_DEVICE_BUILD and RT_HIP_FLAG_STATS, in rt_hip_render and
+	 * rt_hip_render_device, on every kind of context.  With n_boxes == 0 it changes nothing at all; ignored with
+	 * RT_HIP_FLAG_PREVIEW, which draws boxes already.  Refused (RT_HIP_UNSUPPORTED, the message names the flag) with
+	 * RT_HIP_FLAG_FAST, RT_HIP_FLAG_FORCE_TILED, _FORCE_RESIDENT, _FORCE_STREAMED and RT_HIP_FLAG_FORCE_HALF_CHUNKS, by both
+	 * progressive entry points, for more than 256 boxes (a linear scan from LDS; no hierarchy over boxes) and for a frame whose
+	 * tables and chunk sums exceed a workgroup's LDS.  Known limit: a ray refracted INTO a box starts on its face, and where its
+	 * entry distance comes out as a tiny positive number the 0.001 rule rejects the box and the exit face is not found (the
+	 * reference's sphere test has the same weakness).  A library older than this flag refuses the bit (unknown flag bits): that
+	 * is how a caller finds out whether it is there. */
+	RT_HIP_FLAG_TRACE_BOXES = 1u << 13
 };
 
 typedef struct rt_hip_ctx rt_hip_ctx;

@@ -82,6 +82,18 @@ RT_HIP_API rt_hip_status rt_hip_kat_closest_hit_bvh_device(rt_hip_ctx* ctx,
 													uint32_t* out_index,
 													float* out_normal);
 
+/* rt_hip_kat_closest_hit with the scene's BOXES in the query, as RT_HIP_FLAG_TRACE_BOXES' kernels answer it (the same device
+ * functions: rt_amd/csrc/scan.hpp, contract.hpp hits_box_face): kind 3 = box, index = the box's, normal = its outward face normal
+ * (DESIGN.md §3.7).  At most 256 boxes (RT_HIP_UNSUPPORTED beyond).  Must equal tests/native/box_reference.cpp bit for bit. */
+RT_HIP_API rt_hip_status rt_hip_kat_closest_hit_boxes(rt_hip_ctx* ctx,
+											   uint32_t n,
+											   const float* origins,
+											   const float* directions,
+											   float* out_distance,
+											   uint32_t* out_kind,
+											   uint32_t* out_index,
+											   float* out_normal);
+
 /* out_sqrt[i] = sqrtf(a[i]), out_div[i] = a[i] / b[i] as the device computes them (must be correctly rounded). */
 RT_HIP_API rt_hip_status rt_hip_kat_sqrt_div(rt_hip_ctx* ctx, uint32_t n, const float* a, const float* b, float* out_sqrt, float* out_div);
 

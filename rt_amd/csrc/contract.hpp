@@ -342,7 +342,7 @@ namespace rt_hip
 	}
 
 	// Axis-aligned box given by its min and max corners (muu::bounding_box = center -/+ extents), slab method.  Drawn by
-	// the preview only.  Selections are written as compare-and-select so that NaN (0 * inf: a ray parallel to a slab and
+	// the preview, and traced under RT_HIP_FLAG_TRACE_BOXES (hits_box_face below).  Selections are written as compare-and-select so that NaN (0 * inf: a ray parallel to a slab and
 	// starting exactly on it) and signed zeros behave the same here and in the oracle; a NaN that survives makes
 	// `tmax >= tmin` false = miss.  Origin inside the box: the exit distance, like hits_sphere's far root.
 	__device__ __forceinline__ float select_min(float a, float b) { return a < b ? a : b; }
@@ -357,6 +357,48 @@ namespace rt_hip
 		if (!(tmax >= tmin) || tmax < 0.0f)
 			return false;
 		t = tmin >= 0.0f ? tmin : tmax;
+		return true;
+	}
+
+	// Boxes on the traced path (RT_HIP_FLAG_TRACE_BOXES).  A scan tests every box against one ray, so the
+	// reciprocals of its direction are taken once per query; the two functions below are hits_box with them handed in — the
+	// same operations in the same order, the same t bit for bit (tests/test_gpu_boxes.py holds both to oracle_hits_box).
+	__device__ __forceinline__ vec3 box_reciprocals(vec3 d) { return { rcp_rn(d.x), rcp_rn(d.y), rcp_rn(d.z) }; }
+	__device__ __forceinline__ bool hits_box_given(vec3 o, vec3 inv, vec3 lo, vec3 hi, float& t)
+	{
+		const vec3 t1 = (lo - o) * inv;
+		const vec3 t2 = (hi - o) * inv;
+		const float tmin = select_max(select_max(select_min(t1.x, t2.x), select_min(t1.y, t2.y)), select_min(t1.z, t2.z));
+		const float tmax = select_min(select_min(select_max(t1.x, t2.x), select_max(t1.y, t2.y)), select_max(t1.z, t2.z));
+		if (!(tmax >= tmin) || tmax < 0.0f)
+			return false;
+		t = tmin >= 0.0f ? tmin : tmax;
+		return true;
+	}
+	// ... and the face that was hit, as its OUTWARD normal (never flipped toward the ray; the reference defines none, §3.7 does):
+	//   entering (t is tmin): the first axis in x, y, z order whose select_min(t1, t2) equals tmin; -1 on it for a direction
+	//                         component that points up the axis, +1 for one that points down it
+	//   leaving (t is tmax, the origin inside): the first axis whose select_max(t1, t2) equals tmax; the component's own sign
+	// The component's sign is read off its reciprocal, `inv < 0`: a zero component has the sign of its sign bit (1 / -0 = -inf),
+	// a NaN counts as positive.  z is the axis when neither x nor y compares equal.
+	__device__ __forceinline__ bool hits_box_face(vec3 o, vec3 inv, vec3 lo, vec3 hi, float& t, vec3& normal)
+	{
+		const vec3 t1 = (lo - o) * inv;
+		const vec3 t2 = (hi - o) * inv;
+		const vec3 near = { select_min(t1.x, t2.x), select_min(t1.y, t2.y), select_min(t1.z, t2.z) };
+		const vec3 far = { select_max(t1.x, t2.x), select_max(t1.y, t2.y), select_max(t1.z, t2.z) };
+		const float tmin = select_max(select_max(near.x, near.y), near.z);
+		const float tmax = select_min(select_min(far.x, far.y), far.z);
+		if (!(tmax >= tmin) || tmax < 0.0f)
+			return false;
+		const bool entering = tmin >= 0.0f;
+		t = entering ? tmin : tmax;
+		const bool on_x = (entering ? near.x : far.x) == t;
+		const bool on_y = !on_x && (entering ? near.y : far.y) == t;
+		const bool on_z = !on_x && !on_y;
+		const float along = on_x ? inv.x : (on_y ? inv.y : inv.z);
+		const float sign = ((along < 0.0f) != entering) ? -1.0f : 1.0f;
+		normal = { on_x ? sign : 0.0f, on_y ? sign : 0.0f, on_z ? sign : 0.0f };
 		return true;
 	}
 

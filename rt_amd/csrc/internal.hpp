@@ -155,7 +155,7 @@ namespace rt_hip
 	struct frame_delivery; // below: the module-owned frame and the threads that carry it to the caller's buffer
 
 	// (RT_HIP_FLAG_PERSISTENT_FRAME and RT_HIP_FLAG_STATS are rt_hip_render's own: they do not travel to the launch)
-	constexpr uint32_t render_flag_mask = RT_HIP_FLAG_FORCE_TILED | RT_HIP_FLAG_FORCE_RESIDENT | RT_HIP_FLAG_SM_MATERIALS | RT_HIP_FLAG_PREVIEW | RT_HIP_FLAG_FORCE_STREAMED | RT_HIP_FLAG_FAST | RT_HIP_FLAG_FORCE_HALF_CHUNKS | RT_HIP_FLAG_FORCE_WHOLE_CHUNKS | RT_HIP_FLAG_BVH | RT_HIP_FLAG_BVH_DEVICE_BUILD;
+	constexpr uint32_t render_flag_mask = RT_HIP_FLAG_FORCE_TILED | RT_HIP_FLAG_FORCE_RESIDENT | RT_HIP_FLAG_SM_MATERIALS | RT_HIP_FLAG_PREVIEW | RT_HIP_FLAG_FORCE_STREAMED | RT_HIP_FLAG_FAST | RT_HIP_FLAG_FORCE_HALF_CHUNKS | RT_HIP_FLAG_FORCE_WHOLE_CHUNKS | RT_HIP_FLAG_BVH | RT_HIP_FLAG_BVH_DEVICE_BUILD | RT_HIP_FLAG_TRACE_BOXES;
 
 }
 
@@ -257,9 +257,9 @@ namespace rt_hip
 		size_t scx, scy, scz, sr, sm;				 // sphere columns
 		size_t pnx, pny, pnz, pd, pm;				 // plane columns
 		size_t shading, type;						 // per material
-		size_t geometry, prim_shading, prim_metal;	 // derived per-primitive tables (spheres, then planes)
+		size_t geometry, prim_shading, prim_metal;	 // derived per-primitive tables (spheres, then planes, then boxes: of a box only its material's entries mean anything)
 		size_t prim_shading_sm, prim_scatter_sm;	 // the same under sm_ray_tracer's scatter table
-		size_t box_bounds, albedo;					 // what only the preview reads
+		size_t box_bounds, albedo;					 // the boxes' corners (the preview, RT_HIP_FLAG_TRACE_BOXES); what only the preview reads
 		size_t total;
 	};
 	// One render()'s view of the caller's scene: pointers checked, fingerprint taken once — shared by all members of a

@@ -87,7 +87,9 @@ namespace
 	}
 
 	// BVH: the spheres through RT_HIP_FLAG_BVH's traversal (`tree`) instead of the linear scan
-	template <bool BVH>
+	// BOXES: RT_HIP_FLAG_TRACE_BOXES' query — the scene's boxes (at most box_max_count: checked by the caller) scanned after spheres and
+	// planes, the three-way selection, a box's normal from the contract's face rule (scan.hpp: the render kernels' own functions)
+	template <bool BVH, bool BOXES = false>
 	__global__ __launch_bounds__(block_threads) void kat_closest_hit(const device_scene s,
 																	 uint32_t n,
 																	 const float* __restrict__ origins,
@@ -137,15 +139,34 @@ namespace
 				if (alive)
 					scan_lds<true>(spheres, o, d, tile, count, first);
 			}
+		__shared__ float4 box_tile[BOXES ? 2u * box_max_count : 1u];
+		if constexpr (BOXES)
+		{
+			for (uint32_t k = threadIdx.x; k < 2u * s.n_boxes; k += block_threads)
+				box_tile[k] = s.box_bounds[k];
+			__syncthreads();
+		}
 		if (alive)
 		{
 			float distance;
 			uint32_t index;
-			const uint32_t kind = select_hit(spheres, planes, distance, index);
+			uint32_t kind;
 			vec3 normal;
 			float4 shading;
 			uint32_t scatter;
-			fetch_hit<false>(s, o, d, kind, distance, index, normal, shading, scatter);
+			if constexpr (BOXES)
+			{
+				candidate boxes = { 0.0f, 0u, false };
+				const vec3 inv = box_reciprocals(d);
+				scan_boxes(boxes, o, inv, box_tile, s.n_boxes);
+				kind = select_hit(spheres, planes, boxes, distance, index);
+				fetch_hit<false>(s, box_tile, o, d, inv, kind, distance, index, normal, shading, scatter);
+			}
+			else
+			{
+				kind = select_hit(spheres, planes, distance, index);
+				fetch_hit<false>(s, o, d, kind, distance, index, normal, shading, scatter);
+			}
 			if (!kind)
 				normal = { 0.0f, 0.0f, 0.0f }; // hit_result{ -1 } of the reference: no normal
 			out_distance[i] = distance;
@@ -213,6 +234,7 @@ static void launch_kat_random(uint32_t frame_key_a, uint32_t frame_key_b, uint32
 }
 
 static void launch_kat_closest_hit(bool bvh,
+							bool boxes,
 							const device_scene& scene,
 							const device_bvh& tree,
 							uint32_t n,
@@ -225,7 +247,9 @@ static void launch_kat_closest_hit(bool bvh,
 							hipStream_t stream)
 {
 	const dim3 grid((n + block_threads - 1) / block_threads);
-	if (bvh)
+	if (boxes)
+		hipLaunchKernelGGL((kat_closest_hit<false, true>), grid, dim3(block_threads), 0, stream, scene, n, d_origins, d_directions, d_distance, d_kind, d_index, d_normal, tree);
+	else if (bvh)
 		hipLaunchKernelGGL(kat_closest_hit<true>, grid, dim3(block_threads), 0, stream, scene, n, d_origins, d_directions, d_distance, d_kind, d_index, d_normal, tree);
 	else
 		hipLaunchKernelGGL(kat_closest_hit<false>, grid, dim3(block_threads), 0, stream, scene, n, d_origins, d_directions, d_distance, d_kind, d_index, d_normal, tree);
@@ -266,7 +290,7 @@ extern "C" rt_hip_status rt_hip_kat_random(rt_hip_ctx* ctx, uint64_t seed, uint3
 	return RT_HIP_OK;
 }
 
-// bvh: 0 = the linear scan, 1 = the host builder's hierarchy, 2 = the device builder's
+// bvh: 0 = the linear scan, 1 = the host builder's hierarchy, 2 = the device builder's, 3 = the linear scan with the scene's boxes
 static rt_hip_status closest_hit(int bvh,
 								 rt_hip_ctx* ctx,
 								 uint32_t n,
@@ -277,13 +301,18 @@ static rt_hip_status closest_hit(int bvh,
 								 uint32_t* out_index,
 								 float* out_normal)
 {
-	const char* const name = bvh == 2 ? "rt_hip_kat_closest_hit_bvh_device" : (bvh ? "rt_hip_kat_closest_hit_bvh" : "rt_hip_kat_closest_hit");
+	const bool boxes = bvh == 3;
+	if (boxes)
+		bvh = 0;
+	const char* const name = boxes ? "rt_hip_kat_closest_hit_boxes" : (bvh == 2 ? "rt_hip_kat_closest_hit_bvh_device" : (bvh ? "rt_hip_kat_closest_hit_bvh" : "rt_hip_kat_closest_hit"));
 	if (!ctx || !n || !origins || !directions || !out_distance || !out_kind || !out_index || !out_normal)
 		return kat_fail(RT_HIP_INVALID_ARGUMENT, "%s: invalid argument", name);
 	if (!ctx->have_scene)
 		return kat_fail(RT_HIP_NO_SCENE, "%s: no scene uploaded", name);
 	RT_HIP_KAT_TRY(hipSetDevice(ctx->device));
 	const device_scene& scene = ctx->scene;
+	if (boxes && scene.n_boxes > box_max_count)
+		return kat_fail(RT_HIP_UNSUPPORTED, "%s: %u boxes (at most %u are traced)", name, scene.n_boxes, box_max_count);
 	device_bvh tree_desc{};
 	scratch tree_block;
 	device_buffer device_tree, device_tree_scratch;
@@ -349,7 +378,7 @@ static rt_hip_status closest_hit(int bvh,
 	uint32_t* d_kind = reinterpret_cast<uint32_t*>(d_out + scalar_bytes);
 	uint32_t* d_index = reinterpret_cast<uint32_t*>(d_out + 2 * scalar_bytes);
 	float* d_normal = reinterpret_cast<float*>(d_out + 3 * scalar_bytes);
-	launch_kat_closest_hit(bvh != 0, scene, tree_desc, n, reinterpret_cast<const float*>(d_in), reinterpret_cast<const float*>(d_in + vec_bytes), d_distance, d_kind, d_index, d_normal, nullptr);
+	launch_kat_closest_hit(bvh != 0, boxes, scene, tree_desc, n, reinterpret_cast<const float*>(d_in), reinterpret_cast<const float*>(d_in + vec_bytes), d_distance, d_kind, d_index, d_normal, nullptr);
 	RT_HIP_KAT_TRY(hipGetLastError());
 	RT_HIP_KAT_TRY(hipMemcpy(out.host.ptr, out.device.ptr, vec_bytes + 3 * scalar_bytes, hipMemcpyDeviceToHost));
 	const unsigned char* const h_out = out.host.as<unsigned char>();
@@ -382,6 +411,18 @@ extern "C" rt_hip_status rt_hip_kat_closest_hit_bvh(rt_hip_ctx* ctx,
 													float* out_normal)
 {
 	return closest_hit(1, ctx, n, origins, directions, out_distance, out_kind, out_index, out_normal);
+}
+
+extern "C" rt_hip_status rt_hip_kat_closest_hit_boxes(rt_hip_ctx* ctx,
+													  uint32_t n,
+													  const float* origins,
+													  const float* directions,
+													  float* out_distance,
+													  uint32_t* out_kind,
+													  uint32_t* out_index,
+													  float* out_normal)
+{
+	return closest_hit(3, ctx, n, origins, directions, out_distance, out_kind, out_index, out_normal);
 }
 
 extern "C" rt_hip_status rt_hip_kat_closest_hit_bvh_device(rt_hip_ctx* ctx,

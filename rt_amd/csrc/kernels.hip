@@ -445,6 +445,12 @@ namespace rt_hip
 		// argument, of which NS below is the scan proper — so that every other instantiation keeps its symbol, and with it its place in the
 		// listings the unchanged-kernels check compares (tools/kernel_listing_diff.py).  Neither the accumulator nor first_chunk is an argument
 		// of its own: they travel in words these builds do not read (rolling_buffers::accum, kernels.hpp).
+		// BOXES (RT_HIP_FLAG_TRACE_BOXES; the same two kernels, whole chunks only): the query also scans the scene's boxes — staged
+		// ONCE per workgroup into LDS behind the scan's own table (the resident kernel's primitives, the hierarchy kernel's stacks), two float4s
+		// each, read with wave-uniform addresses after spheres and planes, no votes — and selects among three candidates (scan.hpp).  Named by
+		// scan code like the pass builds — scan_resident_boxes, scan_bvh_boxes — so that every other instantiation keeps its symbol and its
+		// instructions; the box count and the table's pointer are device_scene's.  (Staged rather than read through scalar loads: the
+		// scalar-load build's scalar registers are spoken for by its two groups of four spheres, and 8 KiB of LDS cost no occupancy here.)
 		template <int SCAN, bool SM, bool HALF = false, int NP = 0, bool GC = false>
 		__global__ __launch_bounds__(block_threads, waves_per_simd(scan_of(SCAN), NP)) void render_queue(const frame_params p,
 																	  const queue_params q,
@@ -460,7 +466,9 @@ namespace rt_hip
 		{
 			constexpr int NS = scan_of(SCAN);
 			constexpr bool PASS = scan_is_pass(SCAN);
+			constexpr bool BOXES = scan_has_boxes(SCAN);
 			static_assert(!PASS || !HALF, "passes are built for whole chunks only");
+			static_assert(!BOXES || !HALF, "the box builds are built for whole chunks only");
 			extern __shared__ float4 lds[];
 			// [NS > 0] 8 geometry (with the scatter function) + 8 shading float4s | [NS == scan_resident] all primitives; then the chunk slots
 			float4* const lds_geometry = lds;
@@ -473,7 +481,11 @@ namespace rt_hip
 			const bool spheres_in_lds = RESIDENT && !RESIDENT_SCALAR_SCAN;
 			const uint32_t lds_spheres = spheres_in_lds ? s.n_spheres : 0u;
 			constexpr bool BVH = NS == scan_bvh;
-			const uint32_t table_float4s = NS > 0 ? small_table_float4s : (RESIDENT ? lds_spheres + s.n_planes : (NS == scan_tiled ? tile_primitives : (BVH ? bvh_stack_float4s : 0u)));
+			uint32_t table_float4s = NS > 0 ? small_table_float4s : (RESIDENT ? lds_spheres + s.n_planes : (NS == scan_tiled ? tile_primitives : (BVH ? bvh_stack_float4s : 0u)));
+			// [BOXES] the boxes' corners behind that table (launch_plan.cpp: at most box_max_count, and the whole within a workgroup's LDS)
+			float4* const lds_boxes = lds + table_float4s;
+			if constexpr (BOXES)
+				table_float4s += 2u * s.n_boxes;
 			if (NS > 0)
 			{
 				if (threadIdx.x == 0)
@@ -492,6 +504,11 @@ namespace rt_hip
 			{
 				for (uint32_t i = threadIdx.x; i < lds_spheres + s.n_planes; i += block_threads)
 					lds[i] = s.primitive_geometry[(s.n_spheres - lds_spheres) + i];
+			}
+			if constexpr (BOXES)
+			{
+				for (uint32_t i = threadIdx.x; i < 2u * s.n_boxes; i += block_threads)
+					lds_boxes[i] = s.box_bounds[i];
 			}
 			__syncthreads();
 
@@ -1010,8 +1027,19 @@ namespace rt_hip
 						else
 							scan_lds<true>(spheres, st.origin, st.dir, primitives, s.n_spheres, 0);
 						uint32_t index;
-						kind = select_hit(spheres, planes, distance, index);
-						fetch_hit<SM>(s, st.origin, st.dir, kind, distance, index, normal, shading, scatter_kind);
+						if constexpr (BOXES)
+						{
+							candidate boxes = { 0.0f, 0u, false };
+							const vec3 inv = box_reciprocals(st.dir);
+							scan_boxes(boxes, st.origin, inv, lds_boxes, s.n_boxes);
+							kind = select_hit(spheres, planes, boxes, distance, index);
+							fetch_hit<SM>(s, lds_boxes, st.origin, st.dir, inv, kind, distance, index, normal, shading, scatter_kind);
+						}
+						else
+						{
+							kind = select_hit(spheres, planes, distance, index);
+							fetch_hit<SM>(s, st.origin, st.dir, kind, distance, index, normal, shading, scatter_kind);
+						}
 					}
 					if (!kind)
 					{
@@ -1628,6 +1656,13 @@ namespace rt_hip
 #ifndef RT_HIP_FAST_BUILD
 			if constexpr (NS == scan_resident || NS == scan_bvh)
 			{
+				if (plan.build.boxes) // (RT_HIP_FLAG_TRACE_BOXES with at least one box: whole chunks, never a pass — the plan's and the API's rules)
+				{
+					constexpr int box_scan = NS == scan_bvh ? scan_bvh_boxes : scan_resident_boxes;
+					hipLaunchKernelGGL((render_queue<box_scan, SM, false, NP, GC>), grid, dim3(block_threads), plan.lds_bytes, a.stream, a.frame, plan.queue, a.small, a.scene, a.scene.primitive_geometry, a.d_rgba8, a.d_rgb_f32, a.d_counters, item_sums,
+									   a.rolling.pixel_done);
+					return;
+				}
 				if (plan.build.pass) // (a pass of a progressive frame: first_chunk and the accumulator in the words these kernels do not read)
 				{
 					constexpr int pass_scan = NS == scan_bvh ? scan_bvh_pass : scan_resident_pass;

@@ -43,7 +43,8 @@ namespace rt_hip
 		const uint32_t* plane_material;
 		const float4* material_shading; // per material: (attenuation.rgb, roughness)
 		const uint32_t* material_type;
-		// derived per-primitive tables; spheres first, then planes (index n_spheres + i)
+		// derived per-primitive tables; spheres first, then planes (index n_spheres + i), then boxes (index n_spheres + n_planes + i: the
+		// shading and scatter rows of the box's material, read under RT_HIP_FLAG_TRACE_BOXES; the geometry row is zero)
 		const float4* primitive_geometry; // sphere: (cx, cy, cz, r*r); plane: (nx, ny, nz, d)
 		const float4* primitive_shading;  // (attenuation.rgb, roughness) of the primitive's material
 		const uint32_t* primitive_scatter; // scatter function of the primitive's material: scatter_lambert / scatter_metal
@@ -51,8 +52,9 @@ namespace rt_hip
 		// and ice become scatter_dielectric, and their shading.w carries the reflectivity (= index of refraction)
 		const float4* primitive_shading_sm;
 		const uint32_t* primitive_scatter_sm;
-		// what only the preview reads (RT_HIP_FLAG_PREVIEW): the boxes as two float4 each — (min corner, material index
-		// as bits) and (max corner, 0), corners = center -/+ extents — and the materials' plain albedo
+		// the boxes as two float4 each — (min corner, material index as bits) and (max corner, 0), corners = center -/+ extents: read by
+		// the preview (RT_HIP_FLAG_PREVIEW) and by the box builds of the render kernels (RT_HIP_FLAG_TRACE_BOXES) — and, for the preview
+		// alone, the materials' plain albedo
 		uint32_t n_boxes;
 		const float4* box_bounds;
 		const float4* material_albedo;

@@ -2,6 +2,7 @@
 #include "launch_plan.hpp"
 
 #include <algorithm>
+#include <cstdio>
 #include <cstdlib>
 
 namespace rt_hip
@@ -199,11 +200,18 @@ namespace rt_hip
 		const bool pass = request.pass_samples != 0u;
 		if (pass)
 			kernel = (kernel == RT_HIP_KERNEL_BVH || kernel == RT_HIP_KERNEL_STREAMED) ? RT_HIP_KERNEL_BVH : RT_HIP_KERNEL_RESIDENT;
+		// Traced boxes (RT_HIP_FLAG_TRACE_BOXES and at least one box) are planned like a pass: the box builds are builds of the two
+		// tile-per-wave kernels, in whole chunks.  The scalar-register builds live at their register budget and get no box code: their scenes
+		// take the resident kernel.  Without the flag, or without a box, nothing below differs from the frame as it always was.
+		const bool boxes = (request.flags & RT_HIP_FLAG_TRACE_BOXES) && request.n_boxes != 0u;
+		if (boxes)
+			kernel = (kernel == RT_HIP_KERNEL_BVH || kernel == RT_HIP_KERNEL_STREAMED) ? RT_HIP_KERNEL_BVH : RT_HIP_KERNEL_RESIDENT;
 		plan.variant = pixels ? kernel : static_cast<uint32_t>(RT_HIP_KERNEL_NONE);
 		const bool big_scene = plan.big_scene = kernel == RT_HIP_KERNEL_TILED || kernel == RT_HIP_KERNEL_STREAMED;
-		const queue_params queue = plan.queue = choose_queue(pass ? request.pass_samples : request.samples_per_pixel, request.width, request.local_rows, big_scene, request.host_frame, pass ? 0 : half_chunk_choice(request.flags),
+		const queue_params queue = plan.queue = choose_queue(pass ? request.pass_samples : request.samples_per_pixel, request.width, request.local_rows, big_scene, request.host_frame, (pass || boxes) ? 0 : half_chunk_choice(request.flags),
 															 request.n_spheres + request.n_planes, kernel == RT_HIP_KERNEL_STREAMED && request.n_spheres >= sparse_launch_min_spheres);
 		plan.build.pass = pass;
+		plan.build.boxes = boxes;
 		plan.first_chunk = pass ? request.pass_first_sample / sample_chunk : 0u;
 
 		// small scenes: one wave per tile, four tiles side by side per workgroup.  Big scenes: a persistent launch — what
@@ -253,6 +261,15 @@ namespace rt_hip
 				build.scan = scan_tiled;
 				plan.table_bytes = tile_primitives * float4_bytes;
 				break;
+		}
+		if (boxes)
+		{
+			// the boxes' corners behind the scan's own table: the planes (and LDS-scanned spheres) of the resident kernel, the hierarchy kernel's stacks
+			plan.table_bytes += static_cast<size_t>(request.n_boxes) * 2u * float4_bytes;
+			if (request.n_boxes > box_max_count)
+				std::snprintf(plan.refusal, sizeof(plan.refusal), "RT_HIP_FLAG_TRACE_BOXES: %u boxes: at most %u are traced (a linear scan from LDS; there is no hierarchy over boxes)", request.n_boxes, box_max_count);
+			else if (plan.table_bytes + plan.slot_bytes > workgroup_lds_bytes)
+				std::snprintf(plan.refusal, sizeof(plan.refusal), "RT_HIP_FLAG_TRACE_BOXES: %zu bytes of tables and %zu of chunk sums do not fit a workgroup's %zu bytes of LDS", plan.table_bytes, plan.slot_bytes, workgroup_lds_bytes);
 		}
 		plan.lds_bytes = plan.table_bytes + plan.slot_bytes;
 

@@ -92,6 +92,10 @@ namespace rt_hip
 	constexpr uint32_t streamed_from_primitives = 1300;
 	constexpr uint32_t bvh_stack_float4s = 24u * 256u / 4u; // the BVH kernel's LDS traversal stacks: bvh_max_depth words per thread (bvh.hpp, kernels.hip)
 	constexpr uint32_t tile_primitives = 1024;		   // primitives per LDS tile in the tiled kernel
+	// RT_HIP_FLAG_TRACE_BOXES: the box builds scan the boxes linearly from LDS, two float4s each (the corners), staged behind the scan's own
+	// table — 8 KiB at the most; a hierarchy over boxes is not built
+	constexpr uint32_t box_max_count = 256;
+	constexpr size_t workgroup_lds_bytes = 64u * 1024u; // what one workgroup may ask for
 
 	// which kernel a launch takes (RT_HIP_KERNEL_*)
 	uint32_t choose_kernel(uint32_t n_spheres, uint32_t n_planes, bool planes_tame /* device_scene::planes_tame */, uint32_t flags, uint32_t samples_per_pixel,
@@ -108,10 +112,18 @@ namespace rt_hip
 		scan_bvh = -4,			  // RT_HIP_FLAG_BVH: a pixel tile per wave, spheres through the hierarchy
 		// the PASS builds of the two tile-per-wave scans (kernel_build::pass; progressive frames): the same scans, a fold that continues
 		scan_resident_pass = -5,
-		scan_bvh_pass = -6
+		scan_bvh_pass = -6,
+		// the BOX builds of the same two scans (kernel_build::boxes; RT_HIP_FLAG_TRACE_BOXES): the scene's boxes staged into LDS behind
+		// the scan's own table and scanned after spheres and planes
+		scan_resident_boxes = -7,
+		scan_bvh_boxes = -8
 	};
 	constexpr bool scan_is_pass(int code) { return code == scan_resident_pass || code == scan_bvh_pass; }
-	constexpr int scan_of(int code) { return code == scan_resident_pass ? static_cast<int>(scan_resident) : (code == scan_bvh_pass ? static_cast<int>(scan_bvh) : code); } // the scan a build's code stands for
+	constexpr bool scan_has_boxes(int code) { return code == scan_resident_boxes || code == scan_bvh_boxes; }
+	constexpr int scan_of(int code) // the scan a build's code stands for
+	{
+		return (code == scan_resident_pass || code == scan_resident_boxes) ? static_cast<int>(scan_resident) : ((code == scan_bvh_pass || code == scan_bvh_boxes) ? static_cast<int>(scan_bvh) : code);
+	}
 	// the rolling kernels are launched persistent: as many workgroups as the device keeps resident (launch_cache, kernels.hpp)
 	constexpr bool scan_is_persistent(int scan) { return scan == scan_tiled || scan == scan_streamed || scan == scan_streamed_dense; }
 	constexpr unsigned persistent_cache_slots = 18; // { tiled, streamed, streamed for dense frames } x { mg, sm scatter table, fast arithmetic } x { whole chunks, sub-chunk items }
@@ -137,6 +149,9 @@ namespace rt_hip
 		// folded onto the pixels' running sums.  pass_first_sample is a multiple of sample_chunk; samples_per_pixel stays the frame's.
 		// Both 0: a frame in one launch, planned as it always was.
 		uint32_t pass_first_sample = 0, pass_samples = 0;
+		// RT_HIP_FLAG_TRACE_BOXES: the resident scene's boxes (device_scene::n_boxes).  Without the flag, or with none, a frame is planned
+		// as it always was, field for field.
+		uint32_t n_boxes = 0;
 	};
 
 	// the instantiation render_queue<scan, sm_table, sub_chunk_items, planes, general_camera>
@@ -148,6 +163,7 @@ namespace rt_hip
 		bool sub_chunk_items; // HALF
 		bool sm_table;		  // SM: RT_HIP_FLAG_SM_MATERIALS
 		bool pass;			  // one pass of a progressive frame: the scan's PASS build (scan_resident_pass / scan_bvh_pass; `scan` stays the scan proper)
+		bool boxes;			  // RT_HIP_FLAG_TRACE_BOXES with at least one box: the scan's BOX build (scan_resident_boxes / scan_bvh_boxes)
 	};
 
 	struct launch_plan
@@ -166,6 +182,9 @@ namespace rt_hip
 		int persistent_slot; // index into launch_cache::persistent, or -1: not a persistent launch
 		int per_cu_cap;		 // persistent launches: workgroups per CU at most
 		uint32_t first_chunk; // a pass: the chunk of every pixel its items start at (queue.chunks is the PASS's chunk count); else 0
+		// a frame with traced boxes that is NOT launched (RT_HIP_UNSUPPORTED with this text): more than box_max_count boxes, or tables and
+		// chunk sums beyond a workgroup's LDS.  Empty: the plan stands.
+		char refusal[160];
 	};
 	launch_plan plan_launch(const launch_request& request);
 }

@@ -122,13 +122,16 @@ rt_hip_status render_device(rt_hip_ctx* ctx, uint32_t width, uint32_t height, ui
 			request.pass_first_sample = pass->first_sample, request.pass_samples = pass->n_samples;
 		request.camera = camera_form_of(f);
 		request.flags = flags, request.host_frame = host_frame, request.fast_arithmetic = (flags & RT_HIP_FLAG_FAST) != 0;
+		request.n_boxes = ctx->scene.n_boxes;
 		plan = plan_launch(request);
+		if (plan.refusal[0]) // (traced boxes beyond what the box builds hold: nothing is launched)
+			return fail(RT_HIP_UNSUPPORTED, "rt_hip_render_device: %s", plan.refusal);
 		// small scenes: a pixel's chunk sums (one per 16 samples) are parked in LDS until the pixel is complete
 		if (pass && plan.slot_bytes > 48u * 1024u)
 			return fail(RT_HIP_UNSUPPORTED, "rt_hip_render_pass_device: a pass of %u samples is more than the kernels hold chunk sums for (4096 per pass; the frame's samples_per_pixel has no such limit)", pass->n_samples);
 		if (plan.slot_bytes > 48u * 1024u)
 			return fail(RT_HIP_UNSUPPORTED, "rt_hip_render_device: %u samples per pixel are more than the kernels hold chunk sums for (4096; the reference clamps to 1000, src/scene.cpp:544)", f.samples_per_pixel);
-		if (pass && plan.build.scan == scan_bvh && !bvh) // a pass of a scene of the streamed kernel's size goes through the hierarchy (plan_launch), flag or no flag
+		if ((pass || plan.build.boxes) && plan.build.scan == scan_bvh && !bvh) // a pass, or a frame with traced boxes, of a scene of the streamed kernel's size goes through the hierarchy (plan_launch), flag or no flag
 		{
 			if (const rt_hip_status st = ensure_bvh(ctx, false, s, keep_stats))
 				return st;

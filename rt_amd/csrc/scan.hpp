@@ -166,6 +166,73 @@ namespace rt_hip
 		return use_sphere ? 1u : (use_plane ? 2u : 0u);
 	}
 
+	// ---- boxes (RT_HIP_FLAG_TRACE_BOXES) -----------------------------------------------------------
+	// One box of the scan the reference leaves a stub (test_boxes, mg_ray_tracer.cpp:89-93), accepted as test_spheres and
+	// test_planes accept: skip if `!hit || t < min_hit_dist || (have && best <= t)`, so a tie goes to the lower index.
+	// `lo`, `hi` = the box's two float4s of device_scene::box_bounds, wave-uniform; `inv` = box_reciprocals(d), once per query.
+	// Straight-line code, no votes (test_plane has the measurement).  Box tests are not counted (rt_hip_stats).
+	__device__ __forceinline__ void test_box(candidate& best, vec3 o, vec3 inv, float4 lo, float4 hi, uint32_t index)
+	{
+		float t = 0.0f;
+		const bool hit = hits_box_given(o, inv, { lo.x, lo.y, lo.z }, { hi.x, hi.y, hi.z }, t);
+		const bool accept = hit && !(t < min_hit_dist) && !(best.have && best.t <= t);
+		best.t = accept ? t : best.t;
+		best.index = accept ? index : best.index;
+		best.have = best.have || accept;
+	}
+
+	// scan `count` boxes held as pairs of float4s (LDS, wave-uniform addresses: broadcast reads)
+	__device__ __forceinline__ void scan_boxes(candidate& best, vec3 o, vec3 inv, const float4* bounds, uint32_t count)
+	{
+		for (uint32_t i = 0; i < count; i++)
+			test_box(best, o, inv, bounds[2u * i], bounds[2u * i + 1u], i);
+	}
+
+	// select(test_boxes, select(test_spheres, test_planes)), mg_ray_tracer.cpp:162 with a test_boxes that hits: a box wins a
+	// distance tie against a sphere or a plane.  Returns 0 = miss, 1 = sphere, 2 = plane, 3 = box.
+	__device__ __forceinline__ uint32_t select_hit(const candidate& spheres, const candidate& planes, const candidate& boxes, float& distance, uint32_t& index)
+	{
+		float other_distance;
+		uint32_t other_index;
+		const uint32_t other = select_hit(spheres, planes, other_distance, other_index);
+		const float box_distance = boxes.have ? boxes.t : -1.0f;
+		const bool a = box_distance >= 0.0f;
+		const bool use_box = a && (!other || box_distance <= other_distance);
+		distance = use_box ? box_distance : other_distance;
+		index = use_box ? boxes.index : other_index;
+		return use_box ? 3u : other;
+	}
+
+	// fetch_hit for a query that may have hit a box.  The derived per-primitive tables hold the boxes' materials behind the
+	// planes' (index n_spheres + n_planes + i); a box's normal comes from the contract's face rule (hits_box_face) on the
+	// winning box, read from the same pairs the scan read.
+	template <bool SM>
+	__device__ __forceinline__ void
+	fetch_hit(const device_scene& s, const float4* bounds, vec3 o, vec3 d, vec3 inv, uint32_t kind, float distance, uint32_t index, vec3& normal, float4& shading, uint32_t& scatter)
+	{
+		scatter = scatter_lambert;
+		if (kind)
+		{
+			const uint32_t primitive = kind == 1u ? index : (kind == 2u ? s.n_spheres + index : s.n_spheres + s.n_planes + index);
+			shading = SM ? s.primitive_shading_sm[primitive] : s.primitive_shading[primitive];
+			scatter = SM ? s.primitive_scatter_sm[primitive] : s.primitive_scatter[primitive];
+			if (kind == 3u)
+			{
+				const float4 lo = bounds[2u * index], hi = bounds[2u * index + 1u];
+				float t;
+				(void)hits_box_face(o, inv, { lo.x, lo.y, lo.z }, { hi.x, hi.y, hi.z }, t, normal); // (t == distance: the same arithmetic)
+			}
+			else
+			{
+				const float4 g = s.primitive_geometry[primitive];
+				if (kind == 1u)
+					normal = normalize(ray_at(o, d, distance) - vec3{ g.x, g.y, g.z }); // (:85)
+				else
+					normal = { g.x, g.y, g.z }; // the plane's normal, not flipped toward the ray (:58)
+			}
+		}
+	}
+
 	// lookups of the winning primitive from the global per-primitive tables (one indexed read each)
 	template <bool SM>
 	__device__ __forceinline__ void

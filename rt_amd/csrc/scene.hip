@@ -134,7 +134,7 @@ namespace
 		};
 		const size_t sphere_bytes = static_cast<size_t>(s.n_spheres) * 4;
 		const size_t plane_bytes = static_cast<size_t>(s.n_planes) * 4;
-		const size_t n_primitives = static_cast<size_t>(s.n_spheres) + s.n_planes;
+		const size_t n_primitives = static_cast<size_t>(s.n_spheres) + s.n_planes + s.n_boxes; // (a box's rows: its material's entries, RT_HIP_FLAG_TRACE_BOXES)
 		scene_layout L{};
 		L.scx = place(sphere_bytes), L.scy = place(sphere_bytes), L.scz = place(sphere_bytes), L.sr = place(sphere_bytes), L.sm = place(sphere_bytes);
 		L.pnx = place(plane_bytes), L.pny = place(plane_bytes), L.pnz = place(plane_bytes), L.pd = place(plane_bytes), L.pm = place(plane_bytes);
@@ -184,7 +184,7 @@ namespace rt_hip
 		};
 		const size_t sphere_bytes = static_cast<size_t>(s.n_spheres) * 4;
 		const size_t plane_bytes = static_cast<size_t>(s.n_planes) * 4;
-		const size_t n_primitives = static_cast<size_t>(s.n_spheres) + s.n_planes;
+		const size_t n_primitives = static_cast<size_t>(s.n_spheres) + s.n_planes + s.n_boxes;
 		put(L.scx, s.sphere_center_x, sphere_bytes);
 		put(L.scy, s.sphere_center_y, sphere_bytes);
 		put(L.scz, s.sphere_center_z, sphere_bytes);
@@ -215,16 +215,20 @@ namespace rt_hip
 			std::memcpy(&bounds[3], &s.box_material[i], 4);
 			put(L.box_bounds + i * 2 * sizeof(float4), bounds, sizeof(bounds));
 		}
-		// derived per-primitive tables (spheres, then planes)
+		// derived per-primitive tables (spheres, then planes; then the boxes, of which RT_HIP_FLAG_TRACE_BOXES' kernels read the shading and
+		// scatter rows: a box's corners are in box_bounds, its geometry row stays zero)
 		r.small = small_scene{};
 		r.small_sm = small_scene{};
 		for (size_t i = 0; i < n_primitives; i++)
 		{
 			const bool is_sphere = i < s.n_spheres;
-			const size_t k = is_sphere ? i : i - s.n_spheres;
-			float geometry[4];
+			const bool is_box = i >= static_cast<size_t>(s.n_spheres) + s.n_planes;
+			const size_t k = is_sphere ? i : (is_box ? i - s.n_spheres - s.n_planes : i - s.n_spheres);
+			float geometry[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
 			uint32_t material;
-			if (is_sphere)
+			if (is_box)
+				material = s.box_material[k];
+			else if (is_sphere)
 			{
 				const float radius = s.sphere_radius[k];
 				geometry[0] = s.sphere_center_x[k], geometry[1] = s.sphere_center_y[k], geometry[2] = s.sphere_center_z[k];
@@ -253,7 +257,7 @@ namespace rt_hip
 			put(L.prim_metal + i * 4, &metal, 4);
 			put(L.prim_shading_sm + i * sizeof(float4), shading_sm, sizeof(float4));
 			put(L.prim_scatter_sm + i * 4, &scatter_sm, 4);
-			if (i < scalar_max_spheres) // (what the scalar-register kernel is given: meaningful for scenes of <= 8 primitives)
+			if (i < scalar_max_spheres && !is_box) // (what the scalar-register kernel is given: meaningful for scenes of <= 8 spheres and planes)
 			{
 				std::memcpy(&r.small.geometry[i], geometry, sizeof(geometry));
 				std::memcpy(&r.small.shading[i], shading_mg, sizeof(float4));

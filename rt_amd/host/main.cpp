@@ -12,6 +12,8 @@
 //   --progressive SAMPLES   the frame in passes of SAMPLES samples per pixel (exported to the renderer as RT_HIP_PROGRESSIVE):
 //                render() is called ceil(spp / SAMPLES) times — every call shows the frame as it stands — and the last frame,
 //                the same as without the option, is the one reported and written (hip renderers only; not together with --frames)
+//   --boxes                 the traced frame hits the scene's boxes too (exported to the renderer as RT_HIP_TRACE_BOXES=1: RT_HIP_FLAG_TRACE_BOXES);
+//                           hip renderers only, not with --progressive
 //   --shared-frame NAME --rank R --world N   this process is rank R of N rt_headless processes that render ONE frame
 //                together (one per GPU: RT_HIP_DEVICE picks this one's): the back buffer is every process's mapping of the
 //                POSIX shared-memory object /NAME_frame (rank 0 creates it) and the plug-in joins the frame group
@@ -127,6 +129,7 @@ int main(int argc, char** argv)
 	unsigned width = 800, height = 600, spp = 0, bounces = 0, frames = 1, rank = 0, world = 1, progressive = 0;
 	bool frames_given = false;
 	bool list = false;
+	bool boxes = false;
 	// default renderer: the first whose name starts with "hip", else the first registered (reference: first "mg", :350)
 	for (auto& r : renderers::all())
 		if (renderer_name.empty() && r.name.starts_with("hip"))
@@ -181,6 +184,11 @@ int main(int argc, char** argv)
 			}
 			::setenv("RT_HIP_PROGRESSIVE", std::to_string(progressive).c_str(), 1); // (the number as read here, whatever way it was spelled)
 		}
+		else if (arg == "--boxes"sv)
+		{
+			boxes = true;
+			::setenv("RT_HIP_TRACE_BOXES", "1", 1); // (read by the plug-in: RT_HIP_FLAG_TRACE_BOXES, the traced frame hits the scene's boxes)
+		}
 		else if (arg == "--shared-frame"sv)
 			shared_name = value();
 		else if (arg == "--rank"sv)
@@ -189,7 +197,7 @@ int main(int argc, char** argv)
 			world = static_cast<unsigned>(std::strtoul(value(), nullptr, 10));
 		else if (arg == "--help"sv || arg == "-h"sv)
 		{
-			log("usage: rt_headless [--list] [--scene file.toml] [--renderer name] [--size WxH] [--spp N] [--bounces N] [--seed N] [--frames N] [--out file.ppm] [--progressive SAMPLES] [--shared-frame NAME --rank R --world N]");
+			log("usage: rt_headless [--list] [--scene file.toml] [--renderer name] [--size WxH] [--spp N] [--bounces N] [--seed N] [--frames N] [--out file.ppm] [--progressive SAMPLES] [--boxes] [--shared-frame NAME --rank R --world N]");
 			return 0;
 		}
 		else
@@ -215,6 +223,11 @@ int main(int argc, char** argv)
 	if (progressive && (frames_given || std::string_view{ desc->name }.substr(0, 3) != "hip"sv))
 	{
 		error("--progressive sets the number of frames itself (not with --frames) and needs a hip renderer, not '", desc->name, "'");
+		return 2;
+	}
+	if (boxes && (progressive || std::string_view{ desc->name }.substr(0, 3) != "hip"sv))
+	{
+		error("--boxes traces the scene's boxes in one-shot frames of a hip renderer (not with --progressive, not '", desc->name, "')");
 		return 2;
 	}
 	std::unique_ptr<renderer_interface> renderer{ desc->create() };

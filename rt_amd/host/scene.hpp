@@ -20,7 +20,7 @@ namespace rt
 		rt::spheres spheres{};
 		rt::planes planes{};
 		rt::materials materials{};
-		rt::boxes boxes{}; // loaded like the rest; mg_ray_tracer never hits them (mg_ray_tracer.cpp:89-93), the preview draws them
+		rt::boxes boxes{}; // loaded like the rest; mg_ray_tracer never hits them (mg_ray_tracer.cpp:89-93): the preview draws them, the traced frame under RT_HIP_FLAG_TRACE_BOXES
 
 		// ---- where it came from ("" for parse() / synthetic()) ----
 		std::string path{};

@@ -188,7 +188,7 @@ namespace rt
 		const float* radius() const noexcept { return radius_.data(); }
 	};
 
-	class boxes // drawn by the preview only; mg_ray_tracer's test_boxes never hits (mg_ray_tracer.cpp:89-93)
+	class boxes // mg_ray_tracer's test_boxes never hits (mg_ray_tracer.cpp:89-93): drawn by the preview, traced under RT_HIP_FLAG_TRACE_BOXES (opt-in)
 	{
 		detail::column<box> value_;
 		detail::column<unsigned> material_;

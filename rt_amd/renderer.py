@@ -293,10 +293,11 @@ class HipRayTracer:
         n_nodes, n_tree, n_always, depth, root = (int(c) for c in counts)
         return {"nodes": nodes[:n_nodes], "order": order[:n_tree], "spheres": spheres[:n_tree], "always": always[:n_always], "bound": bound, "depth": depth, "root": root}
 
-    def kat_closest_hit(self, origins: np.ndarray, directions: np.ndarray, bvh: bool = False, device_build: bool = False):
+    def kat_closest_hit(self, origins: np.ndarray, directions: np.ndarray, bvh: bool = False, device_build: bool = False, boxes: bool = False):
         """Closest hit of each ray against the resident scene: (distance, kind, index, normal).  `bvh`: through the sphere
         hierarchy of RT_HIP_FLAG_BVH (rt_hip_kat_closest_hit_bvh) instead of the linear scan; `device_build`: through the
-        hierarchy the device builder makes (rt_hip_kat_closest_hit_bvh_device)."""
+        hierarchy the device builder makes (rt_hip_kat_closest_hit_bvh_device); `boxes`: RT_HIP_FLAG_TRACE_BOXES' query, the
+        scene's boxes included (rt_hip_kat_closest_hit_boxes; kind 3 = box)."""
         o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
         d = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
         n = len(o)
@@ -306,6 +307,8 @@ class HipRayTracer:
         normal = np.empty((n, 3), dtype=np.float32)
         kat = capi.kat_lib()
         entry = kat.rt_hip_kat_closest_hit_bvh_device if device_build else (kat.rt_hip_kat_closest_hit_bvh if bvh else kat.rt_hip_kat_closest_hit)
+        if boxes:
+            entry = kat.rt_hip_kat_closest_hit_boxes
         capi.check_kat(entry(self._ctx, n, o.ctypes.data, d.ctypes.data, dist.ctypes.data, kind.ctypes.data, index.ctypes.data, normal.ctypes.data))
         return dist, kind, index, normal
 

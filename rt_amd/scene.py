@@ -102,7 +102,7 @@ def scene_from_arrays(
 
     spheres: rows (cx, cy, cz, radius, material); planes: rows (nx, ny, nz, d, material);
     materials: rows (type, r, g, b, a, roughness, reflectivity); boxes: rows (cx, cy, cz, ex, ey, ez, material),
-    drawn by the preview only.
+    drawn by the preview and, under RT_HIP_FLAG_TRACE_BOXES, by the traced frame.
     """
     out = capi.RtHipScene()
     keep = []

@@ -117,9 +117,13 @@ namespace
 		static const uint32_t flags = []
 		{
 			const char* accel = std::getenv("RT_HIP_ACCEL");
+			// RT_HIP_TRACE_BOXES=1 opts in to RT_HIP_FLAG_TRACE_BOXES: the traced frame hits the scene's boxes too (the preview
+			// draws them anyway and ignores the flag; progressive frames refuse it)
+			const char* boxes = std::getenv("RT_HIP_TRACE_BOXES");
+			const uint32_t trace_boxes = (boxes && std::strcmp(boxes, "1") == 0) ? static_cast<uint32_t>(RT_HIP_FLAG_TRACE_BOXES) : static_cast<uint32_t>(RT_HIP_FLAG_NONE);
 			if (accel && std::strcmp(accel, "bvh-device") == 0) // ... and builds the hierarchy on the GPU (RT_HIP_FLAG_BVH_DEVICE_BUILD)
-				return static_cast<uint32_t>(RT_HIP_FLAG_BVH | RT_HIP_FLAG_BVH_DEVICE_BUILD);
-			return (accel && std::strcmp(accel, "bvh") == 0) ? static_cast<uint32_t>(RT_HIP_FLAG_BVH) : static_cast<uint32_t>(RT_HIP_FLAG_NONE);
+				return static_cast<uint32_t>(RT_HIP_FLAG_BVH | RT_HIP_FLAG_BVH_DEVICE_BUILD) | trace_boxes;
+			return ((accel && std::strcmp(accel, "bvh") == 0) ? static_cast<uint32_t>(RT_HIP_FLAG_BVH) : static_cast<uint32_t>(RT_HIP_FLAG_NONE)) | trace_boxes;
 		}();
 		return flags;
 	}

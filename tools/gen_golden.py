@@ -45,6 +45,18 @@ rgba, rgb, stats = oracle.render(rt_amd.Scene.parse(PREVIEW_SCENE).describe(widt
 np.savez_compressed(OUT / "preview_96x54.npz", width=width, height=height, rgba=rgba, rgb=rgb)
 print("preview_96x54", stats)
 
+# RT_HIP_FLAG_TRACE_BOXES: tests/golden/scenes/boxes.toml through the CPU restatement of the box contract
+# (tests/native/box_reference.cpp: the oracle with a test_boxes that hits), under both scatter tables
+from tests import box_reference  # noqa: E402
+
+width, height, spp, bounces, seed = 64, 36, 20, 8, 9
+pod = rt_amd.Scene.load(OUT / "scenes" / "boxes.toml").set_sampling(spp, bounces).describe(width, height)
+rgba, rgb, stats = box_reference.render(pod, width, height, seed=seed)
+rgba_sm, rgb_sm, stats_sm = box_reference.render(pod, width, height, seed=seed, sm_materials=True)
+np.savez_compressed(OUT / "boxes_64x36_spp20.npz", width=width, height=height, spp=spp, max_bounces=bounces, seed=seed, rgba=rgba, rgb=rgb, segments=stats["segments"], rgba_sm=rgba_sm, rgb_sm=rgb_sm,
+                    segments_sm=stats_sm["segments"])
+print("boxes_64x36_spp20", stats, stats_sm)
+
 seed, pixel, sample = 0x0123456789ABCDEF, 987654, 42
 np.savez_compressed(OUT / "random_stream.npz", seed=np.uint64(seed), pixel=pixel, sample=sample, draws=oracle.random(seed, pixel, sample, 256))
 
