@@ -565,6 +565,68 @@ RT_HIP_API rt_hip_status rt_hip_render_progressive(rt_hip_ctx* ctx,
 										rt_hip_stats* stats,
 										rt_hip_progress* out_progress);
 
+/* ---- denoising low-sample frames: first-hit guide buffers and an edge-avoiding a-trous filter ---------------------------- */
+/*
+ * The first passes of a progressive frame are raw Monte-Carlo noise.  These entry points smooth such a frame without blurring
+ * across what the scene itself says is an edge: a GUIDE of the resident scene (first-hit normal, depth, albedo and primitive of
+ * every pixel, from the path tracer's own sample-0 primary ray) steers a 5 x 5 B3-spline a-trous wavelet filter, one launch per
+ * iteration with taps 2^i pixels apart.  The filter is a contract of its own: + - x, correctly rounded division
+ * and compare-and-select in a fixed order, so that the device's result equals a serial CPU restatement bit for bit — it is NOT
+ * the reference's arithmetic (the reference has no denoiser), and a filtered frame is no path tracer's frame.
+ * Additions to ABI 6 (RT_HIP_ABI_VERSION stays 6): a caller that may meet an older library looks them up with dlsym.
+ */
+typedef struct rt_hip_denoise_params
+{
+	uint32_t iterations;	   /* 0 .. 6; 0 = pass-through */
+	uint32_t normal_squarings; /* 0 .. 8: the normal term is max(0, n_p . n_q) squared this many times */
+	float sigma_colour;		   /* width of the colour term at iteration 0; halved with every iteration */
+	float sigma_albedo;		   /* width of the albedo term */
+	float sigma_depth;		   /* width of the depth term, relative to the deeper of the two hits */
+} rt_hip_denoise_params;
+
+/* the defaults a NULL `params` stands for (DESIGN.md §3.8 has the table they were chosen from); pure host code */
+RT_HIP_API rt_hip_status rt_hip_denoise_default_params(rt_hip_denoise_params* out_params);
+
+/*
+ * The guide of the resident scene for a whole width x height frame: 8 words per pixel, row-major —
+ *   nx, ny, nz, depth | ar, ag, ab, id
+ * the hit normal as the tracer computes it (0, 0, 0 for sky), the hit distance (-1 for sky), the attenuation the tracer uses
+ * for the hit (the sky colour of the ray for a miss), and as uint32 bits 0 for sky or 1 + the primitive's index counted
+ * spheres first, then planes, then boxes.  d_guide: DEVICE buffer of 8 * width * height floats, 16-byte aligned.  Asynchronous on `stream`.
+ * Flags: RT_HIP_FLAG_TRACE_BOXES makes the ray hit the scene's boxes too (at most 256, as for a frame); RT_HIP_FLAG_SM_MATERIALS,
+ * RT_HIP_FLAG_BVH, RT_HIP_FLAG_BVH_DEVICE_BUILD and RT_HIP_FLAG_STATS are accepted and change nothing; every other flag is
+ * refused with RT_HIP_UNSUPPORTED and its name.  On a multi-GPU, rank or frame-group context the root member answers.
+ */
+RT_HIP_API rt_hip_status rt_hip_guide_device(rt_hip_ctx* ctx, uint32_t width, uint32_t height, uint32_t flags, float* d_guide, void* stream);
+
+/*
+ * The filter, a pure image operation on DEVICE buffers: d_rgb_in (3 * width * height floats, a frame's float mean) and d_guide
+ * (rt_hip_guide_device's) give d_rgb_out (3 * width * height floats, optional) and d_rgba8_out (width * height packed pixels:
+ * square root, clamp and pack as rt_hip_render finishes a pixel; optional) — not both NULL.  d_rgb_out must not overlap d_rgb_in.
+ * params == NULL: the defaults.  With iterations == 0 d_rgb_out is d_rgb_in bit for bit and d_rgba8_out is what rt_hip_render
+ * packs from that mean.  Between iterations the image lives in two scratch images of the context (12 bytes per pixel each, grown on
+ * demand, freed with it): two calls on one context must not run at the same time on different streams.  Asynchronous on `stream`.
+ */
+RT_HIP_API rt_hip_status rt_hip_denoise_device(rt_hip_ctx* ctx,
+									uint32_t width,
+									uint32_t height,
+									const float* d_rgb_in,
+									const float* d_guide,
+									const rt_hip_denoise_params* params, /* NULL = defaults */
+									float* d_rgb_out,					 /* nullable */
+									uint32_t* d_rgba8_out,				 /* nullable, not both NULL */
+									void* stream);
+
+/*
+ * The accumulation in flight of rt_hip_render_progressive, denoised: mean = accumulator / samples_done, the guide of the
+ * accumulation's own matrix, size and flags (built once per accumulation and kept), the filter, and the result copied into the
+ * caller's plain HOST memory: pixels_rgba8888 (width * height) and, optionally, rgb_f32 (3 * width * height floats).  The float
+ * frame never crosses the bus on its way in.  Works after any successful rt_hip_render_progressive call, finished or not, and
+ * leaves the accumulation alone: the next pass continues as if the call had not happened.  render_ms (optional): device time of
+ * guide + filter.  RT_HIP_INVALID_ARGUMENT ("no accumulation in flight") where there is none; contexts from rt_hip_create only.
+ */
+RT_HIP_API rt_hip_status rt_hip_denoise_progressive(rt_hip_ctx* ctx, const rt_hip_denoise_params* params, uint32_t* pixels_rgba8888, float* rgb_f32, float* render_ms);
+
 /* Drop the page-lock taken under RT_HIP_FLAG_PERSISTENT_FRAME (see there).  Waits for the context's stream first. */
 RT_HIP_API void rt_hip_forget_frame(rt_hip_ctx* ctx);
 

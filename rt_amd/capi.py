@@ -147,6 +147,15 @@ class RtHipProgress(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class RtHipDenoiseParams(C.Structure):
+    """``rt_hip_denoise_params`` (include/rt_hip.h): the a-trous filter's iteration count and the widths of its edge-stopping terms."""
+
+    _fields_ = [("iterations", C.c_uint32), ("normal_squarings", C.c_uint32), ("sigma_colour", C.c_float), ("sigma_albedo", C.c_float), ("sigma_depth", C.c_float)]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 # every symbol include/rt_hip.h declares: (name, restype, argtypes)
 RT_HIP_SYMBOLS = [
     ("rt_hip_abi_version", C.c_uint32, []),
@@ -190,6 +199,10 @@ RT_HIP_SYMBOLS = [
         C.c_int,
         [C.c_void_p, C.POINTER(RtHipScene), C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(RtHipStats), C.POINTER(RtHipProgress)],
     ),
+    ("rt_hip_denoise_default_params", C.c_int, [C.POINTER(RtHipDenoiseParams)]),
+    ("rt_hip_guide_device", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    ("rt_hip_denoise_device", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(RtHipDenoiseParams), C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("rt_hip_denoise_progressive", C.c_int, [C.c_void_p, C.POINTER(RtHipDenoiseParams), C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]),
     ("rt_hip_forget_frame", None, [C.c_void_p]),
     ("rt_hip_live_frame_locks", C.c_uint32, []),
 ]

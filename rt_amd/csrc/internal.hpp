@@ -9,6 +9,8 @@
 //   frame_setup.cpp, launch_plan.cpp   (host compiler, no HIP) what a launch is refused for, its per-frame constants, its plan
 //   passes.hip    a frame in resumable passes: rt_hip_render_progressive (sequencing: progressive.cpp, host compiler; one pass at the
 //                 device level, rt_hip_render_pass_device, is render.hip's)
+//   denoise.hip   the guide-buffer denoiser: its two kernels, rt_hip_guide_device, rt_hip_denoise_device and
+//                 rt_hip_denoise_progressive (parameters: denoise.cpp, host compiler; per-pixel rules: denoise_rules.hpp)
 //   multi.hip     rt_hip_render on several GPUs: stripes, one gather, assemble
 //   group.hip     rt_hip_render as one rank of a frame group (rank processes storing into one shared back buffer)
 //   kernels.hip   the gfx950 kernels (compiled twice: parity contract and RT_HIP_FLAG_FAST arithmetic)
@@ -152,6 +154,32 @@ namespace rt_hip
 		return ms;
 	}
 
+	// what the denoiser keeps on a context (denoise.hip): everything is grown on demand and freed with the context
+	struct denoise_state
+	{
+		device_buffer scratch[2];	  // the image between two iterations: 12 bytes per pixel each, ping-pong
+		device_buffer mean, filtered; // rt_hip_denoise_progressive: accumulator / samples_done, and the filter's float result
+		device_buffer packed;		  // ... and its packed pixels
+		device_buffer guide;		  // ... and the guide of the accumulation in flight, kept while `guide_key` is the accumulation's
+		pinned_buffer staging;		  // the results' landing place on the host
+		frame_key guide_key{};
+		bool have_guide = false;
+		hipEvent_t begin = nullptr, end = nullptr; // device time of guide + filter
+		void release()
+		{
+			for (device_buffer* b : { &scratch[0], &scratch[1], &mean, &filtered, &packed, &guide })
+				b->release();
+			staging.release();
+			for (hipEvent_t* e : { &begin, &end })
+			{
+				if (*e)
+					(void)hipEventDestroy(*e);
+				*e = nullptr;
+			}
+			have_guide = false;
+		}
+	};
+
 	struct frame_delivery; // below: the module-owned frame and the threads that carry it to the caller's buffer
 
 	// (RT_HIP_FLAG_PERSISTENT_FRAME and RT_HIP_FLAG_STATS are rt_hip_render's own: they do not travel to the launch)
@@ -239,6 +267,7 @@ struct rt_hip_ctx
 	uint32_t progressive_passes = 0;		  // passes launched for it so far
 	rt_hip::device_buffer accum;			  // the pixels' running sums: 3 floats per pixel, kept from pass to pass
 	std::vector<uint32_t> progressive_frame;  // the finished frame, kept on the host for calls that come after the last pass
+	rt_hip::denoise_state denoise;			  // the denoiser's scratch images and the kept guide (denoise.hip)
 
 	rt_hip_ctx() = default;
 	rt_hip_ctx(const rt_hip_ctx&) = delete;

@@ -141,6 +141,21 @@ namespace
 		return samples;
 	}
 
+	// RT_HIP_DENOISE=1, next to RT_HIP_PROGRESSIVE: the frames of an UNFINISHED accumulation — the noisy ones a user looks at while the
+	// frame converges — are delivered through the guide-buffer denoiser (rt_hip_denoise_progressive, default parameters); the finished
+	// frame is delivered as it is.  RT_HIP_DENOISE=always (rt_headless --denoise) filters the finished frame as well.  0 = off.
+	uint32_t denoise_mode()
+	{
+		static const uint32_t mode = []
+		{
+			const char* denoise = std::getenv("RT_HIP_DENOISE");
+			if (denoise && std::strcmp(denoise, "always") == 0)
+				return 2u;
+			return (denoise && std::strcmp(denoise, "1") == 0) ? 1u : 0u;
+		}();
+		return mode;
+	}
+
 	// ModeFlags: 0 = mg_ray_tracer's scatter table; RT_HIP_FLAG_SM_MATERIALS = sm_ray_tracer's (dielectrics refract);
 	// RT_HIP_FLAG_PREVIEW = the one-ray-per-pixel preview of src/renderers/rasterizer.cpp
 	template <uint32_t ModeFlags>
@@ -206,8 +221,12 @@ namespace
 				if (const uint32_t pass_samples = progressive_pass_samples())
 				{
 					// (a seed per frame would start the accumulation again on every call: RT_HIP_SEED, or 1, for all of them)
-					if (rt_hip_render_progressive(ctx, &s, pixels.data(), pixels.size().x, pixels.size().y, fixed ? seed : 1u, accel_flags() | ModeFlags, pass_samples, nullptr, nullptr, nullptr) != RT_HIP_OK)
+					rt_hip_progress progress{};
+					if (rt_hip_render_progressive(ctx, &s, pixels.data(), pixels.size().x, pixels.size().y, fixed ? seed : 1u, accel_flags() | ModeFlags, pass_samples, nullptr, nullptr, &progress) != RT_HIP_OK)
 						std::cerr << "error: hip_ray_tracer: " << rt_hip_last_error() << "\n";
+					else if (const uint32_t mode = denoise_mode(); mode == 2u || (mode == 1u && progress.samples_done < progress.samples_total))
+						if (rt_hip_denoise_progressive(ctx, nullptr, pixels.data(), nullptr, nullptr) != RT_HIP_OK) // (on failure the pass's own frame stays)
+							std::cerr << "error: hip_ray_tracer: " << rt_hip_last_error() << "\n";
 					return;
 				}
 			if (rt_hip_render(ctx, &s, pixels.data(), pixels.size().x, pixels.size().y, seed, frame_flags() | accel_flags() | ModeFlags, nullptr, nullptr) != RT_HIP_OK)

@@ -12,6 +12,9 @@
 //   --progressive SAMPLES   the frame in passes of SAMPLES samples per pixel (exported to the renderer as RT_HIP_PROGRESSIVE):
 //                render() is called ceil(spp / SAMPLES) times — every call shows the frame as it stands — and the last frame,
 //                the same as without the option, is the one reported and written (hip renderers only; not together with --frames)
+//   --denoise               with --progressive only: every pass's frame goes through the guide-buffer denoiser (exported to the renderer as
+//                           RT_HIP_DENOISE=always: rt_hip_denoise_progressive after every pass, the last one included), so the frame
+//                           written is the denoised frame of the last pass
 //   --boxes                 the traced frame hits the scene's boxes too (exported to the renderer as RT_HIP_TRACE_BOXES=1: RT_HIP_FLAG_TRACE_BOXES);
 //                           hip renderers only, not with --progressive
 //   --shared-frame NAME --rank R --world N   this process is rank R of N rt_headless processes that render ONE frame
@@ -129,7 +132,7 @@ int main(int argc, char** argv)
 	unsigned width = 800, height = 600, spp = 0, bounces = 0, frames = 1, rank = 0, world = 1, progressive = 0;
 	bool frames_given = false;
 	bool list = false;
-	bool boxes = false;
+	bool boxes = false, denoise = false;
 	// default renderer: the first whose name starts with "hip", else the first registered (reference: first "mg", :350)
 	for (auto& r : renderers::all())
 		if (renderer_name.empty() && r.name.starts_with("hip"))
@@ -184,6 +187,11 @@ int main(int argc, char** argv)
 			}
 			::setenv("RT_HIP_PROGRESSIVE", std::to_string(progressive).c_str(), 1); // (the number as read here, whatever way it was spelled)
 		}
+		else if (arg == "--denoise"sv)
+		{
+			denoise = true;
+			::setenv("RT_HIP_DENOISE", "always", 1); // (read by the plug-in: rt_hip_denoise_progressive after every pass, the finished frame too)
+		}
 		else if (arg == "--boxes"sv)
 		{
 			boxes = true;
@@ -197,7 +205,7 @@ int main(int argc, char** argv)
 			world = static_cast<unsigned>(std::strtoul(value(), nullptr, 10));
 		else if (arg == "--help"sv || arg == "-h"sv)
 		{
-			log("usage: rt_headless [--list] [--scene file.toml] [--renderer name] [--size WxH] [--spp N] [--bounces N] [--seed N] [--frames N] [--out file.ppm] [--progressive SAMPLES] [--boxes] [--shared-frame NAME --rank R --world N]");
+			log("usage: rt_headless [--list] [--scene file.toml] [--renderer name] [--size WxH] [--spp N] [--bounces N] [--seed N] [--frames N] [--out file.ppm] [--progressive SAMPLES] [--denoise] [--boxes] [--shared-frame NAME --rank R --world N]");
 			return 0;
 		}
 		else
@@ -228,6 +236,11 @@ int main(int argc, char** argv)
 	if (boxes && (progressive || std::string_view{ desc->name }.substr(0, 3) != "hip"sv))
 	{
 		error("--boxes traces the scene's boxes in one-shot frames of a hip renderer (not with --progressive, not '", desc->name, "')");
+		return 2;
+	}
+	if (denoise && !progressive)
+	{
+		error("--denoise filters the passes of a progressive frame: it needs --progressive SAMPLES");
 		return 2;
 	}
 	std::unique_ptr<renderer_interface> renderer{ desc->create() };

@@ -19,7 +19,7 @@ import ctypes as C
 import numpy as np
 
 from . import capi
-from .capi import RtHipPartition, RtHipPhases, RtHipProgress, RtHipScene, RtHipStats, check
+from .capi import RtHipDenoiseParams, RtHipPartition, RtHipPhases, RtHipProgress, RtHipScene, RtHipStats, check
 
 
 def local_rows(height: int, rank: int, world: int, stripe_rows: int = capi.RT_HIP_DEFAULT_STRIPE_ROWS) -> int:
@@ -69,6 +69,13 @@ def bvh_build(scene: RtHipScene) -> dict:
     return {"nodes": nodes[:n_nodes], "order": order[:n_tree], "spheres": spheres[:n_tree], "always": always[:n_always], "bound": bound, "depth": depth, "root": root}
 
 
+def denoise_default_params() -> RtHipDenoiseParams:
+    """rt_hip_denoise_default_params: what a NULL `params` stands for (pure host code)."""
+    params = RtHipDenoiseParams()
+    check(capi.hip_lib().rt_hip_denoise_default_params(C.byref(params)))
+    return params
+
+
 def device_count() -> int:
     n = C.c_int()
     check(capi.hip_lib().rt_hip_device_count(C.byref(n)))
@@ -80,6 +87,8 @@ class HipRayTracer:
     scene replicated, row stripes dealt round-robin, one RCCL gather to devices[0], one copy to the host.
     `peer_copy`: move the stripes with hipMemcpyPeerAsync instead of RCCL (allows a device to appear twice: tests).
     `direct_frame`: no gather — every member stores its pixels straight into the caller's page-locked back buffer."""
+
+    _progressive_size = (1, 1)  # (width, height) render_progressive was last asked for
 
     def __init__(self, device: int = 0, devices: list[int] | None = None, peer_copy: bool = False, direct_frame: bool = False, rank: int | None = None, world: int | None = None, unique_id: bytes | None = None):
         """`rank`, `world`, `unique_id`: one rank of a renderer with one process per GPU (rt_hip_create_rank; collective).
@@ -201,7 +210,29 @@ class HipRayTracer:
                 C.byref(progress),
             )
         )
+        self._progressive_size = (width, height)  # (the accumulation in flight: what denoise_progressive sizes its arrays by)
         return rgba, rgb, stats_pod.as_dict() if stats else {}, progress.as_dict()
+
+    # ---- denoising --------------------------------------------------------------------------
+    def guide_device(self, width: int, height: int, d_guide: int, flags: int = 0, stream: int | None = None) -> None:
+        """rt_hip_guide_device: the first-hit guide of the resident scene (normal, depth | albedo, primitive id) into the DEVICE
+        buffer `d_guide`, 8 floats per pixel.  Asynchronous on `stream`."""
+        check(self._lib.rt_hip_guide_device(self._ctx, width, height, flags, d_guide, stream))
+
+    def denoise_device(self, width: int, height: int, d_rgb_in: int, d_guide: int, params: RtHipDenoiseParams | None = None, d_rgb_out: int | None = None, d_rgba8_out: int | None = None, stream: int | None = None) -> None:
+        """rt_hip_denoise_device: the edge-avoiding a-trous filter on DEVICE buffers (`params` None: the defaults).  Asynchronous."""
+        check(self._lib.rt_hip_denoise_device(self._ctx, width, height, d_rgb_in, d_guide, C.byref(params) if params is not None else None, d_rgb_out, d_rgba8_out, stream))
+
+    def denoise_progressive(self, params: RtHipDenoiseParams | None = None, want_rgb: bool = False, size: tuple | None = None):
+        """rt_hip_denoise_progressive: the accumulation in flight of render_progressive, denoised — (rgba8 uint32[H, W], rgb
+        float32[H, W, 3] or None, device milliseconds of guide + filter).  `size`: (width, height) of that accumulation (the
+        frame render_progressive was last asked for); the accumulation itself is left alone."""
+        width, height = size if size is not None else self._progressive_size
+        rgba = np.empty((height, width), dtype=np.uint32)
+        rgb = np.empty((height, width, 3), dtype=np.float32) if want_rgb else None
+        ms = C.c_float()
+        check(self._lib.rt_hip_denoise_progressive(self._ctx, C.byref(params) if params is not None else None, rgba.ctypes.data, rgb.ctypes.data if rgb is not None else None, C.byref(ms)))
+        return rgba, rgb, ms.value
 
     def forget_frame(self) -> None:
         """Drop the page-lock on the back buffer last rendered into with RT_HIP_FLAG_PERSISTENT_FRAME."""
