@@ -16,18 +16,18 @@ HIPFLAGS += -fvisibility=hidden
 # register pairs — moves, and a higher register count.  Measured on the contract-v4 kernels: headline 2.28 -> 2.14 ms,
 # basic + plane 2.74 -> 2.62, tilted camera 2.80 -> 2.62 (profiles/r05/codegen_ab.txt).
 HIPFLAGS += -fno-slp-vectorize
-API_UNITS := context scene frame render passes multi group denoise
-HIP_HDR  := rt_amd/csrc/kernels.hpp rt_amd/csrc/launch_plan.hpp rt_amd/csrc/progressive.hpp rt_amd/csrc/denoise.hpp rt_amd/csrc/denoise_rules.hpp rt_amd/csrc/frame_setup.hpp rt_amd/csrc/contract.hpp rt_amd/csrc/scan.hpp rt_amd/csrc/bvh_scan.hpp rt_amd/csrc/bvh.hpp rt_amd/csrc/bvh_build.hpp rt_amd/csrc/bvh_build_device.hpp rt_amd/csrc/frame_group.hpp rt_amd/csrc/delivery.hpp rt_amd/csrc/internal.hpp include/rt_hip.h
+API_UNITS := context scene frame render passes multi group denoise temporal
+HIP_HDR  := rt_amd/csrc/kernels.hpp rt_amd/csrc/launch_plan.hpp rt_amd/csrc/progressive.hpp rt_amd/csrc/denoise.hpp rt_amd/csrc/denoise_rules.hpp rt_amd/csrc/temporal.hpp rt_amd/csrc/reproject_rules.hpp rt_amd/csrc/centre_ray.hpp rt_amd/csrc/frame_setup.hpp rt_amd/csrc/contract.hpp rt_amd/csrc/scan.hpp rt_amd/csrc/bvh_scan.hpp rt_amd/csrc/bvh.hpp rt_amd/csrc/bvh_build.hpp rt_amd/csrc/bvh_build_device.hpp rt_amd/csrc/frame_group.hpp rt_amd/csrc/delivery.hpp rt_amd/csrc/internal.hpp include/rt_hip.h
 HOST_SRC := rt_amd/host/host_capi.cpp rt_amd/host/scene.cpp rt_amd/host/toml_subset.cpp
 HOST_HDR := $(wildcard rt_amd/host/*.hpp) rt_amd/host/host_capi.h rt_amd/host/named_colours.inc include/rt_hip.h
 
-all: $(LIBDIR)/librt_hip.so $(LIBDIR)/librt_hip_kat.so $(LIBDIR)/librt_host.so rt_amd/bin/rt_headless tests/native/lbvh_reference tests/native/libbox_reference.so tests/native/libdenoise_reference.so oracle
+all: $(LIBDIR)/librt_hip.so $(LIBDIR)/librt_hip_kat.so $(LIBDIR)/librt_host.so rt_amd/bin/rt_headless tests/native/lbvh_reference tests/native/libbox_reference.so tests/native/libdenoise_reference.so tests/native/libreproject_reference.so oracle
 
 # kernels.hip is compiled twice: the parity contract (contraction off), and RT_HIP_FLAG_FAST's arithmetic
 # (-DRT_HIP_FAST_BUILD -ffp-contract=fast: only launch_render_fast comes out of that one)
 FASTFLAGS := $(filter-out -ffp-contract=off,$(HIPFLAGS)) -ffp-contract=fast -DRT_HIP_FAST_BUILD
 OBJDIR   := build/obj$(NAME)
-HIP_OBJS := $(OBJDIR)/kernels.o $(OBJDIR)/kernels_fast.o $(API_UNITS:%=$(OBJDIR)/%.o) $(OBJDIR)/delivery.o $(OBJDIR)/bvh.o $(OBJDIR)/bvh_build.o $(OBJDIR)/launch_plan.o $(OBJDIR)/frame_setup.o $(OBJDIR)/progressive.o $(OBJDIR)/denoise_params.o
+HIP_OBJS := $(OBJDIR)/kernels.o $(OBJDIR)/kernels_fast.o $(API_UNITS:%=$(OBJDIR)/%.o) $(OBJDIR)/delivery.o $(OBJDIR)/bvh.o $(OBJDIR)/bvh_build.o $(OBJDIR)/launch_plan.o $(OBJDIR)/frame_setup.o $(OBJDIR)/progressive.o $(OBJDIR)/denoise_params.o $(OBJDIR)/temporal_params.o
 
 $(OBJDIR)/kernels.o: rt_amd/csrc/kernels.hip $(HIP_HDR)
 	@mkdir -p $(OBJDIR)
@@ -61,6 +61,12 @@ $(OBJDIR)/progressive.o: rt_amd/csrc/progressive.cpp rt_amd/csrc/progressive.hpp
 # the denoiser's parameters (default_denoise_params, check_denoise_params): plain C++17 too, and the same source is built into
 # tests/native/libdenoise_reference.so on the CPU
 $(OBJDIR)/denoise_params.o: rt_amd/csrc/denoise.cpp rt_amd/csrc/denoise.hpp include/rt_hip.h
+	@mkdir -p $(OBJDIR)
+	$(CXX) -std=c++17 -O2 -fPIC -fvisibility=hidden -Wall -Wextra $(DEFS) -c $< -o $@
+
+# temporal accumulation's host-only rules (parameters, forward_view_projection, same_history): plain C++17 too, and the same source is
+# built into tests/native/libreproject_reference.so on the CPU
+$(OBJDIR)/temporal_params.o: rt_amd/csrc/temporal.cpp rt_amd/csrc/temporal.hpp rt_amd/csrc/progressive.hpp include/rt_hip.h
 	@mkdir -p $(OBJDIR)
 	$(CXX) -std=c++17 -O2 -fPIC -fvisibility=hidden -Wall -Wextra $(DEFS) -c $< -o $@
 
@@ -115,6 +121,21 @@ tests/native/libbox_reference.so: tests/native/box_reference.cpp oracle/cpu_ref.
 tests/native/libdenoise_reference.so: tests/native/denoise_reference.cpp rt_amd/csrc/denoise_rules.hpp rt_amd/csrc/denoise.cpp rt_amd/csrc/denoise.hpp oracle/cpu_ref.cpp oracle/cpu_ref.h include/rt_hip.h
 	$(CXX) -O2 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -fno-math-errno -mfma -Wall -Wextra -shared $< rt_amd/csrc/denoise.cpp -o $@ -lpthread
 
+# the CPU restatement of temporal accumulation: the serial loop over rt_amd/csrc/reproject_rules.hpp — the kernel's own
+# text — with the oracle's leaf functions and oracle_primary_ray (it includes oracle/cpu_ref.cpp), and temporal.cpp as it is; g++ alone,
+# the oracle's strict flags; tests/reproject_reference.py binds it
+REPROJECT_REF_SRC := tests/native/reproject_reference.cpp rt_amd/csrc/reproject_rules.hpp rt_amd/csrc/temporal.cpp rt_amd/csrc/temporal.hpp rt_amd/csrc/progressive.hpp oracle/cpu_ref.cpp oracle/cpu_ref.h include/rt_hip.h
+tests/native/libreproject_reference.so: $(REPROJECT_REF_SRC)
+	$(CXX) -O2 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -fno-math-errno -mfma -Wall -Wextra -shared $< rt_amd/csrc/temporal.cpp -o $@ -lpthread
+
+# `make sanitize-temporal`: the same two sources behind a main() of their own (a 70 x 41 frame whose projections leave the frame, a
+# singular matrix, every parameter refusal) under AddressSanitizer and UndefinedBehaviorSanitizer.  CPU only, nothing is loaded into
+# python; the binary goes to build/ and is run at once
+sanitize-temporal: tests/native/reproject_sanitize.cpp $(REPROJECT_REF_SRC)
+	@mkdir -p build
+	$(CXX) -O1 -g -std=c++17 -ffp-contract=off -fno-fast-math -fno-math-errno -mfma -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer $< rt_amd/csrc/temporal.cpp -o build/reproject_sanitize -lpthread
+	build/reproject_sanitize
+
 oracle:
 	$(MAKE) -C oracle
 
@@ -130,7 +151,7 @@ oracle/_ref/soagen_columns: tests/native/soagen_columns.cpp $(LIBDIR)/librt_hip.
 endif
 
 clean:
-	rm -f $(LIBDIR)/*.so rt_amd/bin/rt_headless tests/native/lbvh_reference tests/native/libbox_reference.so tests/native/libdenoise_reference.so
+	rm -f $(LIBDIR)/*.so rt_amd/bin/rt_headless tests/native/lbvh_reference tests/native/libbox_reference.so tests/native/libdenoise_reference.so tests/native/libreproject_reference.so
 	$(MAKE) -C oracle clean
 
-.PHONY: all oracle clean variant
+.PHONY: all oracle clean variant sanitize-temporal

@@ -627,6 +627,90 @@ RT_HIP_API rt_hip_status rt_hip_denoise_device(rt_hip_ctx* ctx,
  */
 RT_HIP_API rt_hip_status rt_hip_denoise_progressive(rt_hip_ctx* ctx, const rt_hip_denoise_params* params, uint32_t* pixels_rgba8888, float* rgb_f32, float* render_ms);
 
+/* ---- temporal accumulation: accumulated frames kept across camera moves ------------------------------------------------- */
+/*
+ * rt_hip_render_progressive starts again whenever the matrix changes: while the camera moves, every frame is a fresh low-sample
+ * frame.  These entry points carry the samples already traced across a move instead.  For every pixel of the current frame the
+ * first hit's world position (from the guide) is projected through the PREVIOUS frame's view-projection, the history accumulated
+ * there is fetched with four bilinear taps, each tap is checked to be the same surface (primitive id, normal, world position), and
+ * the history is blended with the current frame's mean in proportion to the samples each stands for, the history's share capped.
+ * A contract of its own: + - x, correctly rounded division, explicit fma and compare-and-select in a fixed order,
+ * so that the device's result equals a serial CPU restatement bit for bit — it is NOT the reference's arithmetic (the reference
+ * drops to its preview while the camera moves), and a blended frame is no path tracer's frame.  Known limits: the FIRST hit alone
+ * decides validity, so what is seen IN a metal or glass surface lags behind the camera until the cap washes it out; sky pixels
+ * keep no history; the history is a mean with a cap, not a variance-aware filter.
+ * Additions to ABI 6 (RT_HIP_ABI_VERSION stays 6): a caller that may meet an older library looks them up with dlsym.
+ */
+typedef struct rt_hip_temporal_params
+{
+	uint32_t max_history_samples; /* 1 .. 2^20: the most samples a pixel's history may count for in a blend */
+	float position_tolerance;	  /* > 0: a tap is the same surface if it lies within this x the hit distance of the pixel's point */
+	float normal_threshold;		  /* -1 .. 1: ... and its normal's dot product with the pixel's is at least this */
+} rt_hip_temporal_params;
+
+/* the defaults a NULL `params` stands for (DESIGN.md §3.9 has the table they were chosen from); pure host code */
+RT_HIP_API rt_hip_status rt_hip_temporal_default_params(rt_hip_temporal_params* out_params);
+
+/*
+ * One reprojection step on DEVICE buffers.  The current camera is the RESIDENT scene's (as for rt_hip_guide_device): d_guide is
+ * that call's output for this size, d_rgb_in the current frame's float mean, standing for samples_in (1 .. 4096) samples per pixel.
+ * The history is two buffers a previous call wrote — d_prev_rgb (3 words per pixel: the blended mean, never a filtered one) and
+ * d_prev_record (8 words per pixel, 16-byte aligned: px py pz length | nx ny nz id) — made under prev_inverse_view_projection (HOST,
+ * 16 floats); both NULL: no history (the matrix is then not read).  Outputs: d_rgb_out and d_record_out (16-byte aligned), which
+ * must not overlap any input, and optionally the number of pixels that found history (one word, overwritten).  A singular or
+ * non-finite previous matrix is refused with RT_HIP_INVALID_ARGUMENT.  Asynchronous on `stream`; on a multi-GPU, rank or
+ * frame-group context the root member answers.
+ */
+RT_HIP_API rt_hip_status rt_hip_reproject_device(rt_hip_ctx* ctx,
+									uint32_t width,
+									uint32_t height,
+									const float prev_inverse_view_projection[16],
+									const float* d_guide,
+									const float* d_rgb_in,
+									uint32_t samples_in,
+									const float* d_prev_rgb,	 /* nullable, with d_prev_record */
+									const float* d_prev_record,
+									const rt_hip_temporal_params* params, /* NULL = defaults */
+									float* d_rgb_out,
+									float* d_record_out,
+									uint32_t* d_pixels_with_history, /* nullable */
+									void* stream);
+
+typedef struct rt_hip_temporal_info
+{
+	uint32_t frames;			  /* frames blended into this history so far */
+	uint32_t restarted;			  /* 1: this call started a new history */
+	uint32_t pixels_with_history; /* pixels of this frame that found history */
+	uint32_t pixels;			  /* width x height */
+} rt_hip_temporal_info;
+
+/*
+ * Drop-in level: one call is one frame.  The scene is uploaded by fingerprint as in rt_hip_render; the one-shot frame of
+ * samples_per_pixel (1 .. 4096) samples is traced into a device float mean by the launch rt_hip_render_device makes; its guide is
+ * built; the mean is blended with the context's history (two sets of 44 bytes per pixel, ping-pong, grown on demand, freed with the
+ * context); with `filter` the a-trous filter of rt_hip_denoise_device runs on the blended mean (its output never enters the
+ * history); the result is packed as rt_hip_render packs and copied into the caller's plain HOST memory.
+ *   seed      pass a NEW seed every frame: the same seed twice traces the same samples and adds no information.
+ *   The history starts again on any change of the columns' fingerprint, max_bounces, the size, RT_HIP_FLAG_SM_MATERIALS or
+ *   RT_HIP_FLAG_TRACE_BOXES — and not on a change of the matrix, the seed or samples_per_pixel.  It is state of its own: a
+ *   progressive accumulation in flight, the denoiser's kept guide and rt_hip_render's frames are left alone.
+ *   stats     optional: the traced frame; render_ms additionally holds guide, reprojection and filter.
+ * Flags: RT_HIP_FLAG_SM_MATERIALS, RT_HIP_FLAG_BVH, RT_HIP_FLAG_BVH_DEVICE_BUILD, RT_HIP_FLAG_TRACE_BOXES and RT_HIP_FLAG_STATS;
+ * every other flag is refused with RT_HIP_UNSUPPORTED and its name.  Contexts from rt_hip_create only.
+ */
+RT_HIP_API rt_hip_status rt_hip_render_temporal(rt_hip_ctx* ctx,
+									const rt_hip_scene* scene,
+									uint32_t* pixels_rgba8888,
+									uint32_t width,
+									uint32_t height,
+									uint64_t seed,
+									uint32_t flags,
+									const rt_hip_temporal_params* temporal, /* NULL = defaults */
+									const rt_hip_denoise_params* filter,	/* NULL = no spatial filter */
+									float* rgb_f32,							/* nullable */
+									rt_hip_stats* stats,
+									rt_hip_temporal_info* out_info);
+
 /* Drop the page-lock taken under RT_HIP_FLAG_PERSISTENT_FRAME (see there).  Waits for the context's stream first. */
 RT_HIP_API void rt_hip_forget_frame(rt_hip_ctx* ctx);
 

@@ -156,6 +156,24 @@ class RtHipDenoiseParams(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class RtHipTemporalParams(C.Structure):
+    """``rt_hip_temporal_params`` (include/rt_hip.h): the history's cap and what makes a reprojected tap the same surface."""
+
+    _fields_ = [("max_history_samples", C.c_uint32), ("position_tolerance", C.c_float), ("normal_threshold", C.c_float)]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class RtHipTemporalInfo(C.Structure):
+    """``rt_hip_temporal_info`` (include/rt_hip.h): where the history stands after a call of rt_hip_render_temporal."""
+
+    _fields_ = [("frames", C.c_uint32), ("restarted", C.c_uint32), ("pixels_with_history", C.c_uint32), ("pixels", C.c_uint32)]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 # every symbol include/rt_hip.h declares: (name, restype, argtypes)
 RT_HIP_SYMBOLS = [
     ("rt_hip_abi_version", C.c_uint32, []),
@@ -203,6 +221,17 @@ RT_HIP_SYMBOLS = [
     ("rt_hip_guide_device", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     ("rt_hip_denoise_device", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(RtHipDenoiseParams), C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rt_hip_denoise_progressive", C.c_int, [C.c_void_p, C.POINTER(RtHipDenoiseParams), C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]),
+    ("rt_hip_temporal_default_params", C.c_int, [C.POINTER(RtHipTemporalParams)]),
+    (
+        "rt_hip_reproject_device",
+        C.c_int,
+        [C.c_void_p, C.c_uint32, C.c_uint32, c_float_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(RtHipTemporalParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    ),
+    (
+        "rt_hip_render_temporal",
+        C.c_int,
+        [C.c_void_p, C.POINTER(RtHipScene), C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(RtHipTemporalParams), C.POINTER(RtHipDenoiseParams), C.c_void_p, C.POINTER(RtHipStats), C.POINTER(RtHipTemporalInfo)],
+    ),
     ("rt_hip_forget_frame", None, [C.c_void_p]),
     ("rt_hip_live_frame_locks", C.c_uint32, []),
 ]

@@ -441,6 +441,7 @@ extern "C" void rt_hip_destroy(rt_hip_ctx* ctx)
 	ctx->pixel_done.release();
 	ctx->accum.release();
 	ctx->denoise.release();
+	ctx->temporal.release();
 	ctx->counters.release();
 	ctx->frame_rgb.release();
 	ctx->staging_rgb.release();

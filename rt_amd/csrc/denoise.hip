@@ -10,6 +10,7 @@
 #include "internal.hpp"
 #include "scan.hpp"
 #include "denoise.hpp"
+#include "centre_ray.hpp"
 
 namespace rt_hip
 {
@@ -33,9 +34,8 @@ namespace rt_hip
 namespace
 {
 	// ---- guide_frame: one thread per pixel, the path tracer's sample-0 primary ray, one closest-hit query ----------------------
-	// The ray is the one the render kernels build for sample 0 (kernels.hip, "restart: primary ray"): through the pixel centre — the
-	// jitter's numerators are both 2^23 — in the frame's camera form, with the constants make_frame_params derives.  Restated here
-	// because the render kernels keep it inside their loop; tests/test_gpu_denoise.py holds it to oracle_primary_ray.
+	// The ray is centre_ray.hpp's: the one the render kernels build for sample 0, through the pixel centre (reproject_frame of
+	// temporal.hip builds the same one).
 	// The query is the tracer's (scan.hpp): the 0.001 rule, ties to the lower index, select(spheres, planes) and — under
 	// RT_HIP_FLAG_TRACE_BOXES only — select(boxes, ...).  A linear scan over the resident tables: every lane of a wave walks the same
 	// primitive, so the reads are wave-uniform (scalar loads), as in the preview; one query per pixel needs no more.
@@ -45,45 +45,8 @@ namespace
 		const uint32_t y = blockIdx.y * (block_threads / 64u) + (threadIdx.x >> 6);
 		const bool alive = x < p.width && y < p.height;
 		const float fx = static_cast<float>(alive ? x : 0u), fy = static_cast<float>(alive ? y : 0u); // (a lane outside the frame traces pixel (0, 0) and stores nothing)
-		const float jx = 0x1.0p23f, jy = 0x1.0p23f;
-
-		vec3 origin, toward;
-		if (p.pinhole) // (wave-uniform: a kernel argument)
-		{
-			const vec3 base = { fma(p.ray_d1[0], fx, fma(p.ray_d2[0], fy, p.ray_d0[0])), fma(p.ray_d1[1], fx, fma(p.ray_d2[1], fy, p.ray_d0[1])), fma(p.ray_d1[2], fx, fma(p.ray_d2[2], fy, p.ray_d0[2])) };
-			toward = { fma(p.ray_j1[0], jx, fma(p.ray_j2[0], jy, base.x)), fma(p.ray_j1[1], jx, fma(p.ray_j2[1], jy, base.y)), fma(p.ray_j1[2], jx, fma(p.ray_j2[2], jy, base.z)) };
-			origin = { p.ray_eye[0] + toward.x, p.ray_eye[1] + toward.y, p.ray_eye[2] + toward.z };
-		}
-		else if (p.eye_form)
-		{
-			const vec3 base = { fma(p.eye_q1[0], fx, fma(p.eye_q2[0], fy, p.eye_q0[0])), fma(p.eye_q1[1], fx, fma(p.eye_q2[1], fy, p.eye_q0[1])), fma(p.eye_q1[2], fx, fma(p.eye_q2[2], fy, p.eye_q0[2])) };
-			const float base_w = fma(p.eye_w1, fx, fma(p.eye_w2, fy, p.eye_w0));
-			toward = { fma(p.eye_jq1[0], jx, fma(p.eye_jq2[0], jy, base.x)), fma(p.eye_jq1[1], jx, fma(p.eye_jq2[1], jy, base.y)), fma(p.eye_jq1[2], jx, fma(p.eye_jq2[2], jy, base.z)) };
-			const float ws = fma(p.eye_jw1, jx, fma(p.eye_jw2, jy, base_w));
-			// (rcp_rn is the correctly rounded reciprocal for EVERY argument: the plain form's rcp_in_band gives the same bits inside its band)
-			const float inv = rcp_rn(ws);
-			origin = { fma(toward.x, inv, p.eye_e[0]), fma(toward.y, inv, p.eye_e[1]), fma(toward.z, inv, p.eye_e[2]) };
-			if (p.eye_form != 2u && ws * (ws + p.eye_zws) < 0.0f) // the guarded form: near and far points on different sides of w = 0
-				toward = { -toward.x, -toward.y, -toward.z };
-		}
-		else
-		{
-			const float px = fma(jx, random_scale, fx), py = fma(jy, random_scale, fy);
-			const float ndc_x = fma(px, p.sx, -1.0f), ndc_y = fma(py, p.neg_sy, 1.0f);
-			float N[4], F[4];
-#pragma unroll
-			for (int r = 0; r < 4; r++)
-			{
-				N[r] = fma(p.mx[r], ndc_x, fma(p.my[r], ndc_y, p.k_near[r]));
-				F[r] = fma(p.mx[r], ndc_x, fma(p.my[r], ndc_y, p.k_far[r]));
-			}
-			const float inv_wn = rcp_rn(N[3]);
-			origin = { N[0] * inv_wn, N[1] * inv_wn, N[2] * inv_wn };
-			toward = { fma(F[0], N[3], -(N[0] * F[3])), fma(F[1], N[3], -(N[1] * F[3])), fma(F[2], N[3], -(N[2] * F[3])) };
-			if (N[3] * F[3] < 0.0f)
-				toward = { -toward.x, -toward.y, -toward.z };
-		}
-		const vec3 dir = toward * inv_sqrt_rn(dot(toward, toward));
+		vec3 origin, dir;
+		centre_ray(p, fx, fy, origin, dir);
 
 		candidate spheres = { 0.0f, 0u, false }, planes = { 0.0f, 0u, false }, boxes = { 0.0f, 0u, false };
 		scan_lds<true>(spheres, origin, dir, s.primitive_geometry, s.n_spheres, 0u); // (any float4 table with wave-uniform addresses, not LDS only)
@@ -210,8 +173,18 @@ namespace
 			mean[i] = sums[i] / n;
 	}
 
-	constexpr uint32_t max_frame_side = 1u << 15; // (a pixel's coordinates are int32 in the rules; rt's window is far below)
+	// `params`, or the defaults; refused with the field's name
+	rt_hip_status resolve_params(const char* who, const rt_hip_denoise_params* params, rt_hip_denoise_params& out)
+	{
+		out = params ? *params : default_denoise_params();
+		const denoise_check checked = check_denoise_params(out);
+		if (checked.status)
+			return fail(checked.status, "%s: %s", who, checked.message);
+		return ok();
+	}
+} // namespace (this file's own: the kernels and resolve_params)
 
+	// ---- the host helpers temporal.hip uses too: namespace rt_hip, declared in internal.hpp -------------------------------------------
 	const char* refused_guide_flag(uint32_t flags)
 	{
 		static const struct
@@ -235,20 +208,26 @@ namespace
 		return (flags & ~known) ? "unknown flag bits" : nullptr;
 	}
 
-	bool overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
+	bool buffers_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
 	{
 		const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
 		return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
 	}
 
-	// the guide of `ctx`'s resident scene seen through `matrix` (everything checked by the caller; ctx->device is current)
-	rt_hip_status launch_guide(rt_hip_ctx* ctx, uint32_t width, uint32_t height, const float* matrix, bool trace_boxes, float* d_guide, hipStream_t stream)
+	// the constants centre_ray() reads for a whole width x height frame seen through `matrix`
+	frame_params centre_frame_params(uint32_t width, uint32_t height, const float* matrix)
 	{
 		frame_request wanted{};
 		wanted.width = width, wanted.height = height, wanted.partition = { 0u, 1u, RT_HIP_DEFAULT_STRIPE_ROWS };
 		wanted.samples_per_pixel = 1u, wanted.max_bounces = 1u, wanted.seed = 0u, wanted.whole_frame_buffers = false; // (the centre ray draws nothing)
 		std::copy(matrix, matrix + 16, wanted.inverse_view_projection);
-		const frame_params f = make_frame_params(wanted);
+		return make_frame_params(wanted);
+	}
+
+	// the guide of `ctx`'s resident scene seen through `matrix` (everything checked by the caller; ctx->device is current)
+	rt_hip_status launch_guide(rt_hip_ctx* ctx, uint32_t width, uint32_t height, const float* matrix, bool trace_boxes, float* d_guide, hipStream_t stream)
+	{
+		const frame_params f = centre_frame_params(width, height, matrix);
 		const dim3 grid((width + 63u) / 64u, (height + block_threads / 64u - 1u) / (block_threads / 64u));
 		hipLaunchKernelGGL(guide_frame, grid, dim3(block_threads), 0, stream, f, ctx->scene, trace_boxes ? 1u : 0u, reinterpret_cast<float4*>(d_guide));
 		RT_HIP_TRY(hipGetLastError());
@@ -290,17 +269,7 @@ namespace
 		return ok();
 	}
 
-	// `params`, or the defaults; refused with the field's name
-	rt_hip_status resolve_params(const char* who, const rt_hip_denoise_params* params, rt_hip_denoise_params& out)
-	{
-		out = params ? *params : default_denoise_params();
-		const denoise_check checked = check_denoise_params(out);
-		if (checked.status)
-			return fail(checked.status, "%s: %s", who, checked.message);
-		return ok();
-	}
-}
-}
+} // namespace rt_hip
 
 using namespace rt_hip;
 
@@ -358,7 +327,7 @@ extern "C" rt_hip_status rt_hip_denoise_device(rt_hip_ctx* ctx,
 	if (reinterpret_cast<uintptr_t>(d_guide) % 16u)
 		return fail(RT_HIP_INVALID_ARGUMENT, "rt_hip_denoise_device: d_guide is not 16-byte aligned (two float4s per pixel)");
 	const size_t rgb_bytes = static_cast<size_t>(width) * height * 3u * sizeof(float);
-	if (d_rgb_out && overlap(d_rgb_in, rgb_bytes, d_rgb_out, rgb_bytes))
+	if (d_rgb_out && buffers_overlap(d_rgb_in, rgb_bytes, d_rgb_out, rgb_bytes))
 		return fail(RT_HIP_INVALID_ARGUMENT, "rt_hip_denoise_device: d_rgb_out overlaps d_rgb_in (every pixel reads its neighbours' input)");
 	try
 	{

@@ -11,6 +11,8 @@
 //                 device level, rt_hip_render_pass_device, is render.hip's)
 //   denoise.hip   the guide-buffer denoiser: its two kernels, rt_hip_guide_device, rt_hip_denoise_device and
 //                 rt_hip_denoise_progressive (parameters: denoise.cpp, host compiler; per-pixel rules: denoise_rules.hpp)
+//   temporal.hip  temporal accumulation: reproject_frame, rt_hip_reproject_device and the drop-in rt_hip_render_temporal
+//                 (parameters, the forward matrix, same_history: temporal.cpp, host compiler; per-pixel rule: reproject_rules.hpp)
 //   multi.hip     rt_hip_render on several GPUs: stripes, one gather, assemble
 //   group.hip     rt_hip_render as one rank of a frame group (rank processes storing into one shared back buffer)
 //   kernels.hip   the gfx950 kernels (compiled twice: parity contract and RT_HIP_FLAG_FAST arithmetic)
@@ -180,6 +182,32 @@ namespace rt_hip
 		}
 	};
 
+	// what temporal accumulation keeps on a context (temporal.hip): everything is grown on demand and freed with the context
+	struct temporal_state
+	{
+		device_buffer rgb[2], record[2]; // the history, ping-pong: 12 + 32 bytes per pixel a set
+		device_buffer traced, guide;	 // the frame's traced float mean and its guide
+		device_buffer filtered, packed;	 // the spatial filter's float result, and the packed pixels
+		device_buffer found;			 // one word: the pixels that found history
+		pinned_buffer staging;			 // the results' landing place on the host
+		bool have_history = false;		 // set `current` holds a history made under `key`
+		uint32_t current = 0;
+		uint32_t frames = 0;			 // frames blended into it so far
+		frame_key key{};
+		hipEvent_t end = nullptr;		 // behind guide + reprojection + filter (frames that keep stats)
+		void release()
+		{
+			for (device_buffer* b : { &rgb[0], &rgb[1], &record[0], &record[1], &traced, &guide, &filtered, &packed, &found })
+				b->release();
+			staging.release();
+			if (end)
+				(void)hipEventDestroy(end);
+			end = nullptr;
+			have_history = false;
+			frames = 0;
+		}
+	};
+
 	struct frame_delivery; // below: the module-owned frame and the threads that carry it to the caller's buffer
 
 	// (RT_HIP_FLAG_PERSISTENT_FRAME and RT_HIP_FLAG_STATS are rt_hip_render's own: they do not travel to the launch)
@@ -268,6 +296,7 @@ struct rt_hip_ctx
 	rt_hip::device_buffer accum;			  // the pixels' running sums: 3 floats per pixel, kept from pass to pass
 	std::vector<uint32_t> progressive_frame;  // the finished frame, kept on the host for calls that come after the last pass
 	rt_hip::denoise_state denoise;			  // the denoiser's scratch images and the kept guide (denoise.hip)
+	rt_hip::temporal_state temporal;		  // the history of rt_hip_render_temporal (temporal.hip)
 
 	rt_hip_ctx() = default;
 	rt_hip_ctx(const rt_hip_ctx&) = delete;
@@ -327,6 +356,18 @@ namespace rt_hip
 	rt_hip_status fetch_member_stats(rt_hip_ctx* ctx);
 	rt_hip_stats stats_of_group_rank(const rt_hip_ctx* ctx, uint32_t rank);
 	void sum_group_stats(const rt_hip_ctx* ctx, rt_hip_stats* out);
+
+	// ---- denoise.hip (what temporal.hip uses of it) ----
+	constexpr uint32_t max_frame_side = 1u << 15; // (a pixel's coordinates are int32 in the rules; rt's window is far below)
+	// the name of a flag the guide does not take ("unknown flag bits" for a bit without a name); NULL: all accepted
+	const char* refused_guide_flag(uint32_t flags);
+	bool buffers_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes);
+	// the constants centre_ray() (centre_ray.hpp) reads for a whole width x height frame seen through `matrix`
+	frame_params centre_frame_params(uint32_t width, uint32_t height, const float* matrix);
+	// the guide of the resident scene seen through `matrix`, and the a-trous filter, on device buffers: everything checked by the caller,
+	// ctx->device current
+	rt_hip_status launch_guide(rt_hip_ctx* ctx, uint32_t width, uint32_t height, const float* matrix, bool trace_boxes, float* d_guide, hipStream_t stream);
+	rt_hip_status launch_filter(rt_hip_ctx* ctx, uint32_t width, uint32_t height, const float* d_in, const float* d_guide, const rt_hip_denoise_params& params, float* d_out, uint32_t* d_rgba, hipStream_t stream);
 
 	// ---- multi.hip / group.hip ----
 	rt_hip_status render_multi(rt_hip_ctx* root, const rt_hip_scene* scene, uint32_t* pixels_rgba8888, uint32_t width, uint32_t height, uint64_t seed, uint32_t flags, float* rgb_f32, rt_hip_stats* stats, std::chrono::steady_clock::time_point entered);

@@ -156,6 +156,27 @@ namespace
 		return mode;
 	}
 
+	// RT_HIP_TEMPORAL=1 makes every render() ONE FRAME of temporal accumulation (rt_hip_render_temporal): the frame is traced whole, as
+	// without the variable, and blended with the history the context keeps ACROSS camera moves — what RT_HIP_PROGRESSIVE cannot do,
+	// which starts again whenever the matrix changes.  With RT_HIP_DENOISE=1 or always the blended frame also goes through the a-trous
+	// filter at its defaults.  Every frame gets a seed of its own: the frame's number, or RT_HIP_SEED + the frame's number when the seed
+	// is pinned — reproducible, yet no two frames trace the same samples.  Where RT_HIP_PROGRESSIVE is set it wins.  (Not for the preview.)
+	bool temporal_frames()
+	{
+		static const bool on = []
+		{
+			const char* temporal = std::getenv("RT_HIP_TEMPORAL");
+			const bool wanted = temporal && std::strcmp(temporal, "1") == 0;
+			if (wanted && progressive_pass_samples())
+			{
+				std::cerr << "error: hip_ray_tracer: RT_HIP_TEMPORAL is ignored: RT_HIP_PROGRESSIVE is set and wins\n";
+				return false;
+			}
+			return wanted;
+		}();
+		return on;
+	}
+
 	// ModeFlags: 0 = mg_ray_tracer's scatter table; RT_HIP_FLAG_SM_MATERIALS = sm_ray_tracer's (dielectrics refract);
 	// RT_HIP_FLAG_PREVIEW = the one-ray-per-pixel preview of src/renderers/rasterizer.cpp
 	template <uint32_t ModeFlags>
@@ -164,6 +185,7 @@ namespace
 		rt_hip_ctx* ctx = nullptr;
 		bool failed_to_create = false;
 		uint64_t frame_number = 0;
+		bool temporal_unsupported = false; // RT_HIP_TEMPORAL on a renderer of several GPUs: refused once, then whole frames as without it
 
 		~hip_renderer() noexcept override { rt_hip_destroy(ctx); }
 
@@ -217,6 +239,28 @@ namespace
 			const char* fixed = std::getenv("RT_HIP_SEED");
 			const uint64_t seed = fixed ? std::strtoull(fixed, nullptr, 0) : ++frame_number;
 
+			if constexpr (ModeFlags != RT_HIP_FLAG_PREVIEW)
+				if (temporal_frames())
+				{
+					const uint64_t frame_seed = fixed ? std::strtoull(fixed, nullptr, 0) + ++frame_number : seed; // (unpinned: `seed` is ++frame_number already)
+					rt_hip_denoise_params filter{};
+					const bool filtered = denoise_mode() != 0u && rt_hip_denoise_default_params(&filter) == RT_HIP_OK;
+					const rt_hip_status st = temporal_unsupported ? RT_HIP_UNSUPPORTED : rt_hip_render_temporal(ctx, &s, pixels.data(), pixels.size().x, pixels.size().y, frame_seed, accel_flags() | ModeFlags, nullptr, filtered ? &filter : nullptr, nullptr, nullptr, nullptr);
+					if (st == RT_HIP_OK)
+						return;
+					if (st != RT_HIP_UNSUPPORTED)
+					{
+						std::cerr << "error: hip_ray_tracer: " << rt_hip_last_error() << "\n";
+						return;
+					}
+					// a multi-GPU or frame-group renderer: said once, and from here on every frame is rt_hip_render's (below), with the seed this frame got
+					if (!temporal_unsupported)
+						std::cerr << "error: hip_ray_tracer: " << rt_hip_last_error() << ": RT_HIP_TEMPORAL is ignored for this renderer\n";
+					temporal_unsupported = true;
+					if (rt_hip_render(ctx, &s, pixels.data(), pixels.size().x, pixels.size().y, frame_seed, frame_flags() | accel_flags() | ModeFlags, nullptr, nullptr) != RT_HIP_OK)
+						std::cerr << "error: hip_ray_tracer: " << rt_hip_last_error() << "\n";
+					return;
+				}
 			if constexpr (ModeFlags != RT_HIP_FLAG_PREVIEW)
 				if (const uint32_t pass_samples = progressive_pass_samples())
 				{

@@ -12,11 +12,16 @@
 //   --progressive SAMPLES   the frame in passes of SAMPLES samples per pixel (exported to the renderer as RT_HIP_PROGRESSIVE):
 //                render() is called ceil(spp / SAMPLES) times — every call shows the frame as it stands — and the last frame,
 //                the same as without the option, is the one reported and written (hip renderers only; not together with --frames)
-//   --denoise               with --progressive only: every pass's frame goes through the guide-buffer denoiser (exported to the renderer as
+//   --denoise               with --progressive (or --temporal, see there): every pass's frame goes through the guide-buffer denoiser (exported to the renderer as
 //                           RT_HIP_DENOISE=always: rt_hip_denoise_progressive after every pass, the last one included), so the frame
 //                           written is the denoised frame of the last pass
 //   --boxes                 the traced frame hits the scene's boxes too (exported to the renderer as RT_HIP_TRACE_BOXES=1: RT_HIP_FLAG_TRACE_BOXES);
 //                           hip renderers only, not with --progressive
+//   --temporal              every frame is one frame of temporal accumulation (exported to the renderer as RT_HIP_TEMPORAL=1:
+//                           rt_hip_render_temporal): traced whole with a seed of its own and blended with the history kept across camera
+//                           moves; with --denoise the blended frame goes through the a-trous filter too.  Hip renderers only, not with
+//                           --progressive; with --frames N the last frame is the one written
+//   --dolly DX,DY,DZ        the camera moves by that much in world space before every frame after the first (camera::pose)
 //   --shared-frame NAME --rank R --world N   this process is rank R of N rt_headless processes that render ONE frame
 //                together (one per GPU: RT_HIP_DEVICE picks this one's): the back buffer is every process's mapping of the
 //                POSIX shared-memory object /NAME_frame (rank 0 creates it) and the plug-in joins the frame group
@@ -132,7 +137,8 @@ int main(int argc, char** argv)
 	unsigned width = 800, height = 600, spp = 0, bounces = 0, frames = 1, rank = 0, world = 1, progressive = 0;
 	bool frames_given = false;
 	bool list = false;
-	bool boxes = false, denoise = false;
+	bool boxes = false, denoise = false, temporal = false, dolly = false;
+	float dolly_by[3] = { 0.0f, 0.0f, 0.0f };
 	// default renderer: the first whose name starts with "hip", else the first registered (reference: first "mg", :350)
 	for (auto& r : renderers::all())
 		if (renderer_name.empty() && r.name.starts_with("hip"))
@@ -197,6 +203,21 @@ int main(int argc, char** argv)
 			boxes = true;
 			::setenv("RT_HIP_TRACE_BOXES", "1", 1); // (read by the plug-in: RT_HIP_FLAG_TRACE_BOXES, the traced frame hits the scene's boxes)
 		}
+		else if (arg == "--temporal"sv)
+		{
+			temporal = true;
+			::setenv("RT_HIP_TEMPORAL", "1", 1); // (read by the plug-in: every render() is one rt_hip_render_temporal frame)
+		}
+		else if (arg == "--dolly"sv)
+		{
+			char trailing = 0;
+			if (std::sscanf(value(), "%f,%f,%f%c", &dolly_by[0], &dolly_by[1], &dolly_by[2], &trailing) != 3)
+			{
+				error("--dolly expects DX,DY,DZ");
+				return 2;
+			}
+			dolly = true;
+		}
 		else if (arg == "--shared-frame"sv)
 			shared_name = value();
 		else if (arg == "--rank"sv)
@@ -205,7 +226,7 @@ int main(int argc, char** argv)
 			world = static_cast<unsigned>(std::strtoul(value(), nullptr, 10));
 		else if (arg == "--help"sv || arg == "-h"sv)
 		{
-			log("usage: rt_headless [--list] [--scene file.toml] [--renderer name] [--size WxH] [--spp N] [--bounces N] [--seed N] [--frames N] [--out file.ppm] [--progressive SAMPLES] [--denoise] [--boxes] [--shared-frame NAME --rank R --world N]");
+			log("usage: rt_headless [--list] [--scene file.toml] [--renderer name] [--size WxH] [--spp N] [--bounces N] [--seed N] [--frames N] [--out file.ppm] [--progressive SAMPLES] [--denoise] [--boxes] [--temporal] [--dolly DX,DY,DZ] [--shared-frame NAME --rank R --world N]");
 			return 0;
 		}
 		else
@@ -238,9 +259,14 @@ int main(int argc, char** argv)
 		error("--boxes traces the scene's boxes in one-shot frames of a hip renderer (not with --progressive, not '", desc->name, "')");
 		return 2;
 	}
-	if (denoise && !progressive)
+	if (temporal && (progressive || std::string_view{ desc->name }.substr(0, 3) != "hip"sv))
 	{
-		error("--denoise filters the passes of a progressive frame: it needs --progressive SAMPLES");
+		error("--temporal blends whole frames of a hip renderer (not with --progressive, not '", desc->name, "')");
+		return 2;
+	}
+	if (denoise && !progressive && !temporal)
+	{
+		error("--denoise filters the passes of a progressive frame: it needs --progressive SAMPLES (or --temporal)");
 		return 2;
 	}
 	std::unique_ptr<renderer_interface> renderer{ desc->create() };
@@ -296,6 +322,8 @@ int main(int argc, char** argv)
 	double seconds = 0.0;
 	for (unsigned f = 0; f < (frames ? frames : 1u); f++)
 	{
+		if (dolly && f)
+			scene.camera.pose(scene.camera.position() + vec3{ dolly_by[0], dolly_by[1], dolly_by[2] }, scene.camera.rotation());
 		if (rank == 0)
 			pixels.clear(0x000000FFu); // reference src/main.cpp:318 (the other ranks of a shared frame leave it alone)
 		const auto t0 = std::chrono::steady_clock::now();

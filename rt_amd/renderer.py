@@ -19,7 +19,7 @@ import ctypes as C
 import numpy as np
 
 from . import capi
-from .capi import RtHipDenoiseParams, RtHipPartition, RtHipPhases, RtHipProgress, RtHipScene, RtHipStats, check
+from .capi import RtHipDenoiseParams, RtHipPartition, RtHipPhases, RtHipProgress, RtHipScene, RtHipStats, RtHipTemporalInfo, RtHipTemporalParams, check
 
 
 def local_rows(height: int, rank: int, world: int, stripe_rows: int = capi.RT_HIP_DEFAULT_STRIPE_ROWS) -> int:
@@ -73,6 +73,13 @@ def denoise_default_params() -> RtHipDenoiseParams:
     """rt_hip_denoise_default_params: what a NULL `params` stands for (pure host code)."""
     params = RtHipDenoiseParams()
     check(capi.hip_lib().rt_hip_denoise_default_params(C.byref(params)))
+    return params
+
+
+def temporal_default_params() -> RtHipTemporalParams:
+    """rt_hip_temporal_default_params: what a NULL `temporal` stands for (pure host code)."""
+    params = RtHipTemporalParams()
+    check(capi.hip_lib().rt_hip_temporal_default_params(C.byref(params)))
     return params
 
 
@@ -233,6 +240,25 @@ class HipRayTracer:
         ms = C.c_float()
         check(self._lib.rt_hip_denoise_progressive(self._ctx, C.byref(params) if params is not None else None, rgba.ctypes.data, rgb.ctypes.data if rgb is not None else None, C.byref(ms)))
         return rgba, rgb, ms.value
+
+    # ---- temporal accumulation ---------------------------------------------------------------
+    def reproject_device(self, width: int, height: int, prev_matrix, d_guide: int, d_rgb_in: int, samples_in: int, d_prev_rgb: int | None, d_prev_record: int | None, params: RtHipTemporalParams | None, d_rgb_out: int, d_record_out: int,
+                         d_pixels_with_history: int | None = None, stream: int | None = None) -> None:
+        """rt_hip_reproject_device: one reprojection step on DEVICE buffers; the current camera is the resident scene's, `prev_matrix`
+        (16 floats, or None without a history) the one the history was made under.  Asynchronous on `stream`."""
+        matrix = (C.c_float * 16)(*[float(v) for v in np.asarray(prev_matrix, dtype=np.float32).reshape(-1)]) if prev_matrix is not None else None
+        check(self._lib.rt_hip_reproject_device(self._ctx, width, height, matrix, d_guide, d_rgb_in, samples_in, d_prev_rgb, d_prev_record, C.byref(params) if params is not None else None, d_rgb_out, d_record_out, d_pixels_with_history, stream))
+
+    def render_temporal(self, scene: RtHipScene, width: int, height: int, seed: int = 1, flags: int = 0, temporal: RtHipTemporalParams | None = None, filter: RtHipDenoiseParams | None = None, want_rgb: bool = False, stats: bool = True):
+        """rt_hip_render_temporal: one frame blended into the context's history — (rgba8 uint32[H, W], rgb float32[H, W, 3] or None,
+        stats dict, info dict: frames, restarted, pixels_with_history, pixels).  Pass a new `seed` every frame.  `filter`: the
+        a-trous filter's parameters for the delivered frame (None: no spatial filter)."""
+        stats_pod, info = RtHipStats(), RtHipTemporalInfo()
+        rgba = np.empty((height, width), dtype=np.uint32)
+        rgb = np.empty((height, width, 3), dtype=np.float32) if want_rgb else None
+        check(self._lib.rt_hip_render_temporal(self._ctx, C.byref(scene), rgba.ctypes.data, width, height, seed, flags, C.byref(temporal) if temporal is not None else None, C.byref(filter) if filter is not None else None,
+                                               rgb.ctypes.data if rgb is not None else None, C.byref(stats_pod) if stats else None, C.byref(info)))
+        return rgba, rgb, stats_pod.as_dict() if stats else {}, info.as_dict()
 
     def forget_frame(self) -> None:
         """Drop the page-lock on the back buffer last rendered into with RT_HIP_FLAG_PERSISTENT_FRAME."""
