@@ -17,7 +17,7 @@ HIPFLAGS += -fvisibility=hidden
 # basic + plane 2.74 -> 2.62, tilted camera 2.80 -> 2.62 (profiles/r05/codegen_ab.txt).
 HIPFLAGS += -fno-slp-vectorize
 API_UNITS := context scene frame render passes multi group denoise temporal
-HIP_HDR  := rt_amd/csrc/kernels.hpp rt_amd/csrc/launch_plan.hpp rt_amd/csrc/progressive.hpp rt_amd/csrc/denoise.hpp rt_amd/csrc/denoise_rules.hpp rt_amd/csrc/temporal.hpp rt_amd/csrc/reproject_rules.hpp rt_amd/csrc/centre_ray.hpp rt_amd/csrc/frame_setup.hpp rt_amd/csrc/contract.hpp rt_amd/csrc/scan.hpp rt_amd/csrc/bvh_scan.hpp rt_amd/csrc/bvh.hpp rt_amd/csrc/bvh_build.hpp rt_amd/csrc/bvh_build_device.hpp rt_amd/csrc/frame_group.hpp rt_amd/csrc/delivery.hpp rt_amd/csrc/internal.hpp include/rt_hip.h
+HIP_HDR  := rt_amd/csrc/kernels.hpp rt_amd/csrc/launch_plan.hpp rt_amd/csrc/progressive.hpp rt_amd/csrc/denoise.hpp rt_amd/csrc/denoise_rules.hpp rt_amd/csrc/temporal.hpp rt_amd/csrc/reproject_rules.hpp rt_amd/csrc/centre_ray.hpp rt_amd/csrc/frame_setup.hpp rt_amd/csrc/contract.hpp rt_amd/csrc/scan.hpp rt_amd/csrc/bvh_scan.hpp rt_amd/csrc/bvh.hpp rt_amd/csrc/box_bvh.hpp rt_amd/csrc/box_bvh_scan.hpp rt_amd/csrc/bvh_build.hpp rt_amd/csrc/bvh_build_device.hpp rt_amd/csrc/frame_group.hpp rt_amd/csrc/delivery.hpp rt_amd/csrc/internal.hpp include/rt_hip.h
 HOST_SRC := rt_amd/host/host_capi.cpp rt_amd/host/scene.cpp rt_amd/host/toml_subset.cpp
 HOST_HDR := $(wildcard rt_amd/host/*.hpp) rt_amd/host/host_capi.h rt_amd/host/named_colours.inc include/rt_hip.h
 
@@ -27,7 +27,7 @@ all: $(LIBDIR)/librt_hip.so $(LIBDIR)/librt_hip_kat.so $(LIBDIR)/librt_host.so r
 # (-DRT_HIP_FAST_BUILD -ffp-contract=fast: only launch_render_fast comes out of that one)
 FASTFLAGS := $(filter-out -ffp-contract=off,$(HIPFLAGS)) -ffp-contract=fast -DRT_HIP_FAST_BUILD
 OBJDIR   := build/obj$(NAME)
-HIP_OBJS := $(OBJDIR)/kernels.o $(OBJDIR)/kernels_fast.o $(API_UNITS:%=$(OBJDIR)/%.o) $(OBJDIR)/delivery.o $(OBJDIR)/bvh.o $(OBJDIR)/bvh_build.o $(OBJDIR)/launch_plan.o $(OBJDIR)/frame_setup.o $(OBJDIR)/progressive.o $(OBJDIR)/denoise_params.o $(OBJDIR)/temporal_params.o
+HIP_OBJS := $(OBJDIR)/kernels.o $(OBJDIR)/kernels_fast.o $(API_UNITS:%=$(OBJDIR)/%.o) $(OBJDIR)/delivery.o $(OBJDIR)/bvh.o $(OBJDIR)/box_bvh.o $(OBJDIR)/bvh_build.o $(OBJDIR)/launch_plan.o $(OBJDIR)/frame_setup.o $(OBJDIR)/progressive.o $(OBJDIR)/denoise_params.o $(OBJDIR)/temporal_params.o
 
 $(OBJDIR)/kernels.o: rt_amd/csrc/kernels.hip $(HIP_HDR)
 	@mkdir -p $(OBJDIR)
@@ -44,6 +44,10 @@ $(OBJDIR)/delivery.o: rt_amd/csrc/delivery.cpp rt_amd/csrc/delivery.hpp
 	$(CXX) -std=c++17 -O2 -fPIC -fvisibility=hidden -Wall -Wextra -c $< -o $@
 # the sphere hierarchy's builder (RT_HIP_FLAG_BVH): plain C++17, linked into the product and into the test-only library
 $(OBJDIR)/bvh.o: rt_amd/csrc/bvh.cpp rt_amd/csrc/bvh.hpp
+	@mkdir -p $(OBJDIR)
+	$(CXX) -std=c++17 -O2 -fPIC -fvisibility=hidden -Wall -Wextra -c $< -o $@
+# ... and the box hierarchy's (RT_HIP_FLAG_BOX_BVH): the same on both counts
+$(OBJDIR)/box_bvh.o: rt_amd/csrc/box_bvh.cpp rt_amd/csrc/box_bvh.hpp rt_amd/csrc/bvh.hpp
 	@mkdir -p $(OBJDIR)
 	$(CXX) -std=c++17 -O2 -fPIC -fvisibility=hidden -Wall -Wextra -c $< -o $@
 
@@ -85,8 +89,8 @@ $(LIBDIR)/librt_hip.so: $(HIP_OBJS)
 
 # test-only: the known-answer entry points of include/rt_hip_kat.h (never shipped; loads next to librt_hip.so)
 # (with its own copies of both builders of the sphere hierarchy: librt_hip.so exports neither)
-$(LIBDIR)/librt_hip_kat.so: $(OBJDIR)/kat.o $(OBJDIR)/bvh.o $(OBJDIR)/bvh_build.o $(LIBDIR)/librt_hip.so
-	$(HIPCC) --offload-arch=gfx950 -fPIC -shared -o $@ $(OBJDIR)/kat.o $(OBJDIR)/bvh.o $(OBJDIR)/bvh_build.o -L$(LIBDIR) -lrt_hip -Wl,-rpath,'$$ORIGIN' -L/opt/rocm/lib -lrccl
+$(LIBDIR)/librt_hip_kat.so: $(OBJDIR)/kat.o $(OBJDIR)/bvh.o $(OBJDIR)/box_bvh.o $(OBJDIR)/bvh_build.o $(LIBDIR)/librt_hip.so
+	$(HIPCC) --offload-arch=gfx950 -fPIC -shared -o $@ $(OBJDIR)/kat.o $(OBJDIR)/bvh.o $(OBJDIR)/box_bvh.o $(OBJDIR)/bvh_build.o -L$(LIBDIR) -lrt_hip -Wl,-rpath,'$$ORIGIN' -L/opt/rocm/lib -lrccl
 $(OBJDIR)/kat.o: include/rt_hip_kat.h
 
 $(LIBDIR)/librt_host.so: $(HOST_SRC) $(HOST_HDR)
@@ -136,6 +140,15 @@ sanitize-temporal: tests/native/reproject_sanitize.cpp $(REPROJECT_REF_SRC)
 	$(CXX) -O1 -g -std=c++17 -ffp-contract=off -fno-fast-math -fno-math-errno -mfma -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer $< rt_amd/csrc/temporal.cpp -o build/reproject_sanitize -lpthread
 	build/reproject_sanitize
 
+# `make sanitize-box-bvh`: the box hierarchy's host builder behind a main() of its own — the counts, the identical boxes, the depth-24
+# chain, lo > hi, NaN and infinite corners of tests/test_box_bvh_build.py, each tree checked for coverage, exact unions and depth —
+# under AddressSanitizer and UndefinedBehaviorSanitizer.  CPU only, nothing is loaded into python; the binary goes to build/ and is
+# run at once
+sanitize-box-bvh: tests/native/box_bvh_sanitize.cpp rt_amd/csrc/box_bvh.cpp rt_amd/csrc/box_bvh.hpp rt_amd/csrc/bvh.hpp
+	@mkdir -p build
+	$(CXX) -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer $< rt_amd/csrc/box_bvh.cpp -o build/box_bvh_sanitize
+	build/box_bvh_sanitize
+
 oracle:
 	$(MAKE) -C oracle
 
@@ -154,4 +167,4 @@ clean:
 	rm -f $(LIBDIR)/*.so rt_amd/bin/rt_headless tests/native/lbvh_reference tests/native/libbox_reference.so tests/native/libdenoise_reference.so tests/native/libreproject_reference.so
 	$(MAKE) -C oracle clean
 
-.PHONY: all oracle clean variant sanitize-temporal
+.PHONY: all oracle clean variant sanitize-temporal sanitize-box-bvh

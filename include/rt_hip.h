@@ -254,12 +254,28 @@ enum
 	 * rt_hip_render_device, on every kind of context.  With n_boxes == 0 it changes nothing at all; ignored with
 	 * RT_HIP_FLAG_PREVIEW, which draws boxes already.  Refused (RT_HIP_UNSUPPORTED, the message names the flag) with
 	 * RT_HIP_FLAG_FAST, RT_HIP_FLAG_FORCE_TILED, _FORCE_RESIDENT, _FORCE_STREAMED and RT_HIP_FLAG_FORCE_HALF_CHUNKS, by both
-	 * progressive entry points, for more than 256 boxes (a linear scan from LDS; no hierarchy over boxes) and for a frame whose
+	 * progressive entry points, for more than 256 boxes (a linear scan from LDS; the hierarchy over boxes is RT_HIP_FLAG_BOX_BVH's) and for a frame whose
 	 * tables and chunk sums exceed a workgroup's LDS.  Known limit: a ray refracted INTO a box starts on its face, and where its
 	 * entry distance comes out as a tiny positive number the 0.001 rule rejects the box and the exit face is not found (the
 	 * reference's sphere test has the same weakness).  A library older than this flag refuses the bit (unknown flag bits): that
 	 * is how a caller finds out whether it is there. */
-	RT_HIP_FLAG_TRACE_BOXES = 1u << 13
+	RT_HIP_FLAG_TRACE_BOXES = 1u << 13,
+	/* OPT-IN, modifies RT_HIP_FLAG_TRACE_BOXES: the closest-hit query reaches the boxes through a HIERARCHY (a binned-SAH binary tree
+	 * over the boxes' extents, built on the host, walked per lane on the sphere hierarchy's LDS stack) instead of the linear scan
+	 * from LDS, and the 256-box cap does not apply: the cap is the tree's, 2^26 boxes.  The PROMISE: the frame, the float mean and
+	 * `segments` are bit for bit those of the box contract — the same slab arithmetic on every box reached, ties
+	 * to the lower index, a box wins a tie against a sphere or a plane, the same face normal; a node is skipped only where no box
+	 * inside it can give an accepted distance, which for boxes needs no padding at all.  A ray with a zero,
+	 * subnormal or non-finite direction component, or a non-finite origin, scans the boxes linearly instead.  The frame is planned
+	 * onto the hierarchy kernel whatever the sphere count (the sphere tree is built as for RT_HIP_FLAG_BVH; zero spheres work):
+	 * kernel_variant reports RT_HIP_KERNEL_BVH.  rt_hip_stats is unchanged, box tests stay uncounted.  The tree is built at the
+	 * first such frame after the scene's columns changed (counted in `upload_ms`), kept while they stay the same, and freed with
+	 * the context.  With n_boxes == 0 it changes nothing at all; ignored with RT_HIP_FLAG_PREVIEW.  Refused (RT_HIP_UNSUPPORTED,
+	 * the message names the flag) without RT_HIP_FLAG_TRACE_BOXES, wherever RT_HIP_FLAG_TRACE_BOXES is refused, and by
+	 * rt_hip_render_temporal, rt_hip_denoise_progressive and rt_hip_guide_device, whose guide kernel keeps its linear scan.  Nothing
+	 * is promised about speed (DESIGN.md §3.10 has the measured table).  A library older than this flag refuses the bit (unknown
+	 * flag bits). */
+	RT_HIP_FLAG_BOX_BVH = 1u << 14
 };
 
 typedef struct rt_hip_ctx rt_hip_ctx;

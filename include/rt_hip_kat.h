@@ -94,6 +94,29 @@ RT_HIP_API rt_hip_status rt_hip_kat_closest_hit_boxes(rt_hip_ctx* ctx,
 											   uint32_t* out_index,
 											   float* out_normal);
 
+/* Host only (no context, no GPU): the box hierarchy RT_HIP_FLAG_BOX_BVH builds for `scene` (rt_amd/csrc/box_bvh.cpp), from the pairs
+ * the upload derives (corners = center -/+ extents, the material index as bits in the fourth word of the first).  out_counts[5] =
+ * { inner nodes, boxes in the tree, boxes in the always list, depth, root link }, the nodes and links laid out as
+ * rt_hip_kat_bvh_build's.  Every other output may be NULL; each is sized for the worst case, n = scene->n_boxes:
+ *   out_nodes   16 floats per node (at most n);             out_order   n: the scene index of each leaf slot;
+ *   out_corners 8n: the two float4s of each leaf slot;      out_always  n: scene indices outside the tree, ascending. */
+RT_HIP_API rt_hip_status rt_hip_kat_box_bvh_build(const rt_hip_scene* scene, uint32_t out_counts[5], float* out_nodes, uint32_t* out_order, float* out_corners, uint32_t* out_always);
+
+/* rt_hip_kat_closest_hit_boxes with the boxes reached through RT_HIP_FLAG_BOX_BVH's traversal (the render kernel's own code:
+ * rt_amd/csrc/box_bvh_scan.hpp, its fall-back to the linear scan included) over a hierarchy built for the resident scene as the
+ * render path builds it.  Any number of boxes.  Must equal tests/native/box_reference.cpp bit for bit. */
+RT_HIP_API rt_hip_status rt_hip_kat_closest_hit_boxes_bvh(rt_hip_ctx* ctx,
+												   uint32_t n,
+												   const float* origins,
+												   const float* directions,
+												   float* out_distance,
+												   uint32_t* out_kind,
+												   uint32_t* out_index,
+												   float* out_normal);
+
+/* How many box hierarchies `ctx` has built on the host so far: a frame that reuses the cached tree leaves it as it was. */
+RT_HIP_API rt_hip_status rt_hip_kat_box_bvh_builds(rt_hip_ctx* ctx, uint64_t* out_builds);
+
 /* out_sqrt[i] = sqrtf(a[i]), out_div[i] = a[i] / b[i] as the device computes them (must be correctly rounded). */
 RT_HIP_API rt_hip_status rt_hip_kat_sqrt_div(rt_hip_ctx* ctx, uint32_t n, const float* a, const float* b, float* out_sqrt, float* out_div);
 

@@ -31,6 +31,7 @@ RT_HIP_FLAG_FORCE_WHOLE_CHUNKS = 1 << 9
 RT_HIP_FLAG_BVH = 1 << 10  # spheres through a bounding volume hierarchy: same frame, same segments (include/rt_hip.h)
 RT_HIP_FLAG_BVH_DEVICE_BUILD = 1 << 11  # with RT_HIP_FLAG_BVH: the hierarchy is built on the GPU (rt_amd/csrc/bvh_build.hip), same frame
 RT_HIP_FLAG_TRACE_BOXES = 1 << 13  # the traced frame hits the scene's boxes too; bit 12 is unassigned
+RT_HIP_FLAG_BOX_BVH = 1 << 14  # with RT_HIP_FLAG_TRACE_BOXES: the boxes through a hierarchy of their own, no 256-box cap, same frame
 RT_HIP_MULTI_PEER_COPY = 1 << 0
 RT_HIP_MULTI_DIRECT_FRAME = 1 << 1
 RT_HIP_TRANSPORT_NONE, RT_HIP_TRANSPORT_RCCL_GATHER, RT_HIP_TRANSPORT_PEER_COPY, RT_HIP_TRANSPORT_DIRECT_FRAME = 0, 1, 2, 3
@@ -246,6 +247,9 @@ RT_HIP_KAT_SYMBOLS = [
     ("rt_hip_kat_bvh_build_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rt_hip_kat_closest_hit_bvh_device", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rt_hip_kat_closest_hit_boxes", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("rt_hip_kat_closest_hit_boxes_bvh", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("rt_hip_kat_box_bvh_build", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("rt_hip_kat_box_bvh_builds", C.c_int, [C.c_void_p, C.c_void_p]),
     ("rt_hip_kat_sqrt_div", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rt_hip_kat_exhaustive_math", C.c_int, [C.c_void_p, C.POINTER(C.c_uint64 * 3), C.POINTER(C.c_uint32 * 3)]),
 ]

@@ -436,6 +436,7 @@ extern "C" void rt_hip_destroy(rt_hip_ctx* ctx)
 	ctx->scene_columns.release();
 	ctx->bvh_block.release();
 	ctx->bvh_scratch.release();
+	ctx->box_bvh_block.release();
 	ctx->scene_staging.release();
 	ctx->item_sums.release();
 	ctx->pixel_done.release();

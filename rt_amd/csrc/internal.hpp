@@ -211,7 +211,7 @@ namespace rt_hip
 	struct frame_delivery; // below: the module-owned frame and the threads that carry it to the caller's buffer
 
 	// (RT_HIP_FLAG_PERSISTENT_FRAME and RT_HIP_FLAG_STATS are rt_hip_render's own: they do not travel to the launch)
-	constexpr uint32_t render_flag_mask = RT_HIP_FLAG_FORCE_TILED | RT_HIP_FLAG_FORCE_RESIDENT | RT_HIP_FLAG_SM_MATERIALS | RT_HIP_FLAG_PREVIEW | RT_HIP_FLAG_FORCE_STREAMED | RT_HIP_FLAG_FAST | RT_HIP_FLAG_FORCE_HALF_CHUNKS | RT_HIP_FLAG_FORCE_WHOLE_CHUNKS | RT_HIP_FLAG_BVH | RT_HIP_FLAG_BVH_DEVICE_BUILD | RT_HIP_FLAG_TRACE_BOXES;
+	constexpr uint32_t render_flag_mask = RT_HIP_FLAG_FORCE_TILED | RT_HIP_FLAG_FORCE_RESIDENT | RT_HIP_FLAG_SM_MATERIALS | RT_HIP_FLAG_PREVIEW | RT_HIP_FLAG_FORCE_STREAMED | RT_HIP_FLAG_FAST | RT_HIP_FLAG_FORCE_HALF_CHUNKS | RT_HIP_FLAG_FORCE_WHOLE_CHUNKS | RT_HIP_FLAG_BVH | RT_HIP_FLAG_BVH_DEVICE_BUILD | RT_HIP_FLAG_TRACE_BOXES | RT_HIP_FLAG_BOX_BVH;
 
 }
 
@@ -276,6 +276,16 @@ struct rt_hip_ctx
 	const rt_hip::device_bvh* bvh_descriptor = nullptr; // ... its first bytes: what the BVH kernel is handed (rolling_buffers::bvh)
 	bool bvh_device_built = false;		 // ... and which builder made it: bvh_build.hip (RT_HIP_FLAG_BVH_DEVICE_BUILD) or bvh.cpp
 	rt_hip::device_buffer bvh_scratch;	 // the device builder's keys, ping-pong buffers and level queues
+	// RT_HIP_FLAG_BOX_BVH (scene.hip, ensure_box_bvh): a copy of the sphere hierarchy's descriptor, the box hierarchy's descriptor
+	// box_bvh_descriptor_offset bytes behind it, then nodes, leaf-ordered corners, their indices, the always list.  What the
+	// scan_bvh_boxtree build is handed in rolling_buffers::bvh's place.
+	rt_hip::device_buffer box_bvh_block;
+	uint64_t box_columns_print = 0;		 // fingerprint of the resident box_bounds pairs (make_resident)
+	uint64_t box_bvh_print = 0;			 // ... of the pairs the tree in box_bvh_block was built from
+	uint32_t box_bvh_count = 0;			 // ... and how many they were
+	bool box_bvh_built = false;
+	uint64_t box_bvh_sphere_stamp = 0;	 // which sphere hierarchy the copied descriptor describes (0 = none): 2 * bvh_built_for + bvh_device_built
+	uint64_t box_bvh_builds = 0;		 // host builds so far (the known-answer library reads it: tests/test_gpu_box_bvh.py)
 	size_t scene_bytes = 0;				 // size of the resident block
 	// Opt-in (RT_HIP_FLAG_PERSISTENT_FRAME, frame groups): the CALLER's buffer, page-locked and mapped into the GPU's address
 	// space while it keeps arriving at the same address: the kernel renders straight into it.  The caller then owes the
@@ -338,6 +348,10 @@ namespace rt_hip
 	// RT_HIP_FLAG_BVH: the resident scene's sphere hierarchy (scene.hip).  device_build: RT_HIP_FLAG_BVH_DEVICE_BUILD — built by
 	// bvh_build.hip on `stream`, the stream the frame is about to be launched on; wait: the frame keeps stats, upload_ms is to hold the build
 	rt_hip_status ensure_bvh(rt_hip_ctx* ctx, bool device_build, hipStream_t stream, bool wait);
+	// RT_HIP_FLAG_BOX_BVH: make ctx->box_bvh_block hold the box hierarchy of the resident scene — built on the host (box_bvh.cpp) at
+	// the first such frame after the box columns' fingerprint changed, its time added to upload_ms — behind a copy of the CURRENT
+	// sphere hierarchy's descriptor (ensure_bvh has run), refreshed on `stream` whenever that hierarchy was rebuilt
+	rt_hip_status ensure_box_bvh(rt_hip_ctx* ctx, hipStream_t stream);
 
 	// ---- render.hip ----
 	// whole_frame_buffers: d_rgba8 / d_rgb_f32 are the whole width x height frame and every pixel goes to its image row

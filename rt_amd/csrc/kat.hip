@@ -12,6 +12,7 @@
 #include "internal.hpp"
 #include "scan.hpp"
 #include "bvh_scan.hpp"
+#include "box_bvh_scan.hpp"
 #include "bvh_build.hpp"
 #include "bvh_build_device.hpp"
 
@@ -178,6 +179,75 @@ namespace
 		}
 	}
 
+	// RT_HIP_FLAG_BOX_BVH's query: spheres and planes as above (the linear scans), the boxes — any number — through the render kernel's own
+	// traversal (box_bvh_scan.hpp) with its fall-back to the linear scan over the pairs in memory, the three-way selection, the face rule
+	__global__ __launch_bounds__(block_threads) void kat_closest_hit_box_tree(const device_scene s,
+																				  uint32_t n,
+																				  const float* __restrict__ origins,
+																				  const float* __restrict__ directions,
+																				  float* __restrict__ out_distance,
+																				  uint32_t* __restrict__ out_kind,
+																				  uint32_t* __restrict__ out_index,
+																				  float* __restrict__ out_normal,
+																				  const device_box_bvh tree)
+	{
+		__shared__ float4 tile[tile_primitives];
+		__shared__ uint32_t stacks[bvh_max_depth * block_threads];
+		const uint32_t i = blockIdx.x * block_threads + threadIdx.x;
+		const bool alive = i < n;
+		vec3 o = { 0, 0, 0 }, d = { 0, 0, 1 };
+		if (alive)
+		{
+			o = { origins[i * 3], origins[i * 3 + 1], origins[i * 3 + 2] };
+			d = { directions[i * 3], directions[i * 3 + 1], directions[i * 3 + 2] };
+		}
+		candidate planes = { 0.0f, 0u, false };
+		candidate spheres = { 0.0f, 0u, false };
+		for (uint32_t first = 0; first < s.n_planes; first += tile_primitives)
+		{
+			const uint32_t count = min(tile_primitives, s.n_planes - first);
+			__syncthreads();
+			stage_planes(tile, s, first, count);
+			__syncthreads();
+			if (alive)
+				scan_lds<false>(planes, o, d, tile, count, first);
+		}
+		for (uint32_t first = 0; first < s.n_spheres; first += tile_primitives)
+		{
+			const uint32_t count = min(tile_primitives, s.n_spheres - first);
+			__syncthreads();
+			stage_spheres(tile, s, first, count);
+			__syncthreads();
+			if (alive)
+				scan_lds<true>(spheres, o, d, tile, count, first);
+		}
+		if (alive)
+		{
+			candidate boxes = { 0.0f, 0u, false };
+			const vec3 inv = box_reciprocals(d);
+			if (!bvh_boxes(boxes, o, inv, tree, s.box_bounds, stacks + threadIdx.x))
+			{
+				boxes = { 0.0f, 0u, false }; // what the render kernel does too: the linear scan decides
+				scan_boxes(boxes, o, inv, s.box_bounds, s.n_boxes);
+			}
+			float distance;
+			uint32_t index;
+			vec3 normal;
+			float4 shading;
+			uint32_t scatter;
+			const uint32_t kind = select_hit(spheres, planes, boxes, distance, index);
+			fetch_hit<false>(s, s.box_bounds, o, d, inv, kind, distance, index, normal, shading, scatter);
+			if (!kind)
+				normal = { 0.0f, 0.0f, 0.0f };
+			out_distance[i] = distance;
+			out_kind[i] = kind;
+			out_index[i] = kind ? index : 0u;
+			out_normal[i * 3 + 0] = normal.x;
+			out_normal[i * 3 + 1] = normal.y;
+			out_normal[i * 3 + 2] = normal.z;
+		}
+	}
+
 	__global__ void kat_sqrt_div(uint32_t n, const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ out_sqrt, float* __restrict__ out_div)
 	{
 		const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -255,6 +325,12 @@ static void launch_kat_closest_hit(bool bvh,
 		hipLaunchKernelGGL(kat_closest_hit<false>, grid, dim3(block_threads), 0, stream, scene, n, d_origins, d_directions, d_distance, d_kind, d_index, d_normal, tree);
 }
 
+static void launch_kat_closest_hit_box_tree(const device_scene& scene, const device_box_bvh& tree, uint32_t n, const float* d_origins, const float* d_directions, float* d_distance, uint32_t* d_kind, uint32_t* d_index, float* d_normal, hipStream_t stream)
+{
+	const dim3 grid((n + block_threads - 1) / block_threads);
+	hipLaunchKernelGGL(kat_closest_hit_box_tree, grid, dim3(block_threads), 0, stream, scene, n, d_origins, d_directions, d_distance, d_kind, d_index, d_normal, tree);
+}
+
 static void launch_kat_sqrt_div(uint32_t n, const float* d_a, const float* d_b, float* d_sqrt, float* d_div, hipStream_t stream)
 {
 	const dim3 grid((n + block_threads - 1) / block_threads);
@@ -290,7 +366,8 @@ extern "C" rt_hip_status rt_hip_kat_random(rt_hip_ctx* ctx, uint64_t seed, uint3
 	return RT_HIP_OK;
 }
 
-// bvh: 0 = the linear scan, 1 = the host builder's hierarchy, 2 = the device builder's, 3 = the linear scan with the scene's boxes
+// bvh: 0 = the linear scan, 1 = the host builder's hierarchy, 2 = the device builder's, 3 = the linear scan with the scene's boxes,
+// 4 = the linear scan with the scene's boxes through THEIR hierarchy (RT_HIP_FLAG_BOX_BVH)
 static rt_hip_status closest_hit(int bvh,
 								 rt_hip_ctx* ctx,
 								 uint32_t n,
@@ -301,10 +378,10 @@ static rt_hip_status closest_hit(int bvh,
 								 uint32_t* out_index,
 								 float* out_normal)
 {
-	const bool boxes = bvh == 3;
-	if (boxes)
+	const bool boxes = bvh == 3, box_tree = bvh == 4;
+	if (boxes || box_tree)
 		bvh = 0;
-	const char* const name = boxes ? "rt_hip_kat_closest_hit_boxes" : (bvh == 2 ? "rt_hip_kat_closest_hit_bvh_device" : (bvh ? "rt_hip_kat_closest_hit_bvh" : "rt_hip_kat_closest_hit"));
+	const char* const name = box_tree ? "rt_hip_kat_closest_hit_boxes_bvh" : boxes ? "rt_hip_kat_closest_hit_boxes" : (bvh == 2 ? "rt_hip_kat_closest_hit_bvh_device" : (bvh ? "rt_hip_kat_closest_hit_bvh" : "rt_hip_kat_closest_hit"));
 	if (!ctx || !n || !origins || !directions || !out_distance || !out_kind || !out_index || !out_normal)
 		return kat_fail(RT_HIP_INVALID_ARGUMENT, "%s: invalid argument", name);
 	if (!ctx->have_scene)
@@ -364,6 +441,36 @@ static rt_hip_status closest_hit(int bvh,
 		tree_desc.n_always = static_cast<uint32_t>(tree.always.size());
 		tree_desc.cx = tree.centre[0], tree_desc.cy = tree.centre[1], tree_desc.cz = tree.centre[2], tree_desc.radius = tree.radius;
 	}
+	device_box_bvh box_desc{};
+	if (box_tree)
+	{
+		// the box hierarchy of the resident scene, built as the render path builds it (scene.hip, ensure_box_bvh): from the pairs on the device
+		const uint32_t count = scene.n_boxes;
+		std::vector<float> bounds(static_cast<size_t>(count) * 8);
+		if (count)
+			RT_HIP_KAT_TRY(hipMemcpy(bounds.data(), scene.box_bounds, static_cast<size_t>(count) * 2u * sizeof(float4), hipMemcpyDeviceToHost));
+		box_bvh_host tree;
+		std::string why;
+		if (!build_box_bvh(bounds.data(), count, tree, why))
+			return kat_fail(RT_HIP_UNSUPPORTED, "%s: %s", name, why.c_str());
+		const size_t nodes_bytes = tree.nodes.size() * 4, corners_bytes = tree.corners.size() * 4, order_bytes = tree.order.size() * 4, always_bytes = tree.always.size() * 4;
+		const size_t total = nodes_bytes + corners_bytes + order_bytes + always_bytes + 16;
+		RT_HIP_KAT_TRY(tree_block.reserve(total));
+		unsigned char* const h = tree_block.host.as<unsigned char>();
+		std::memcpy(h, tree.nodes.data(), nodes_bytes);
+		std::memcpy(h + nodes_bytes, tree.corners.data(), corners_bytes);
+		std::memcpy(h + nodes_bytes + corners_bytes, tree.order.data(), order_bytes);
+		std::memcpy(h + nodes_bytes + corners_bytes + order_bytes, tree.always.data(), always_bytes);
+		RT_HIP_KAT_TRY(hipMemcpy(tree_block.device.ptr, h, total, hipMemcpyHostToDevice));
+		const unsigned char* const d = tree_block.device.as<unsigned char>();
+		box_desc.nodes = reinterpret_cast<const float4*>(d);
+		box_desc.corners = reinterpret_cast<const float4*>(d + nodes_bytes);
+		box_desc.order = reinterpret_cast<const uint32_t*>(d + nodes_bytes + corners_bytes);
+		box_desc.always = reinterpret_cast<const uint32_t*>(d + nodes_bytes + corners_bytes + order_bytes);
+		box_desc.root = tree.root;
+		box_desc.n_tree = static_cast<uint32_t>(tree.order.size());
+		box_desc.n_always = static_cast<uint32_t>(tree.always.size());
+	}
 	const size_t vec_bytes = static_cast<size_t>(n) * 3 * sizeof(float);
 	const size_t scalar_bytes = static_cast<size_t>(n) * sizeof(float);
 	scratch in, out;
@@ -378,7 +485,10 @@ static rt_hip_status closest_hit(int bvh,
 	uint32_t* d_kind = reinterpret_cast<uint32_t*>(d_out + scalar_bytes);
 	uint32_t* d_index = reinterpret_cast<uint32_t*>(d_out + 2 * scalar_bytes);
 	float* d_normal = reinterpret_cast<float*>(d_out + 3 * scalar_bytes);
-	launch_kat_closest_hit(bvh != 0, boxes, scene, tree_desc, n, reinterpret_cast<const float*>(d_in), reinterpret_cast<const float*>(d_in + vec_bytes), d_distance, d_kind, d_index, d_normal, nullptr);
+	if (box_tree)
+		launch_kat_closest_hit_box_tree(scene, box_desc, n, reinterpret_cast<const float*>(d_in), reinterpret_cast<const float*>(d_in + vec_bytes), d_distance, d_kind, d_index, d_normal, nullptr);
+	else
+		launch_kat_closest_hit(bvh != 0, boxes, scene, tree_desc, n, reinterpret_cast<const float*>(d_in), reinterpret_cast<const float*>(d_in + vec_bytes), d_distance, d_kind, d_index, d_normal, nullptr);
 	RT_HIP_KAT_TRY(hipGetLastError());
 	RT_HIP_KAT_TRY(hipMemcpy(out.host.ptr, out.device.ptr, vec_bytes + 3 * scalar_bytes, hipMemcpyDeviceToHost));
 	const unsigned char* const h_out = out.host.as<unsigned char>();
@@ -423,6 +533,62 @@ extern "C" rt_hip_status rt_hip_kat_closest_hit_boxes(rt_hip_ctx* ctx,
 													  float* out_normal)
 {
 	return closest_hit(3, ctx, n, origins, directions, out_distance, out_kind, out_index, out_normal);
+}
+
+extern "C" rt_hip_status rt_hip_kat_closest_hit_boxes_bvh(rt_hip_ctx* ctx,
+															  uint32_t n,
+															  const float* origins,
+															  const float* directions,
+															  float* out_distance,
+															  uint32_t* out_kind,
+															  uint32_t* out_index,
+															  float* out_normal)
+{
+	return closest_hit(4, ctx, n, origins, directions, out_distance, out_kind, out_index, out_normal);
+}
+
+extern "C" rt_hip_status rt_hip_kat_box_bvh_builds(rt_hip_ctx* ctx, uint64_t* out_builds)
+{
+	if (!ctx || !out_builds)
+		return kat_fail(RT_HIP_INVALID_ARGUMENT, "rt_hip_kat_box_bvh_builds: NULL argument");
+	*out_builds = ctx->box_bvh_builds;
+	return RT_HIP_OK;
+}
+
+extern "C" rt_hip_status rt_hip_kat_box_bvh_build(const rt_hip_scene* scene, uint32_t out_counts[5], float* out_nodes, uint32_t* out_order, float* out_corners, uint32_t* out_always)
+{
+	if (!scene || !out_counts)
+		return kat_fail(RT_HIP_INVALID_ARGUMENT, "rt_hip_kat_box_bvh_build: NULL argument");
+	const uint32_t n = scene->n_boxes;
+	if (n && (!scene->box_center_x || !scene->box_center_y || !scene->box_center_z || !scene->box_extents_x || !scene->box_extents_y || !scene->box_extents_z || !scene->box_material))
+		return kat_fail(RT_HIP_INVALID_ARGUMENT, "rt_hip_kat_box_bvh_build: NULL box column");
+	// the pairs as the upload derives them (scene.hip, build_image): corners = center -/+ extents, the material index riding in the spare lane
+	std::vector<float> bounds(static_cast<size_t>(n) * 8, 0.0f);
+	for (uint32_t i = 0; i < n; i++)
+	{
+		float* const b = &bounds[static_cast<size_t>(i) * 8];
+		b[0] = scene->box_center_x[i] - scene->box_extents_x[i], b[1] = scene->box_center_y[i] - scene->box_extents_y[i], b[2] = scene->box_center_z[i] - scene->box_extents_z[i];
+		b[4] = scene->box_center_x[i] + scene->box_extents_x[i], b[5] = scene->box_center_y[i] + scene->box_extents_y[i], b[6] = scene->box_center_z[i] + scene->box_extents_z[i];
+		std::memcpy(&b[3], &scene->box_material[i], 4);
+	}
+	box_bvh_host tree;
+	std::string why;
+	if (!build_box_bvh(bounds.data(), n, tree, why))
+		return kat_fail(RT_HIP_UNSUPPORTED, "rt_hip_kat_box_bvh_build: %s", why.c_str());
+	out_counts[0] = static_cast<uint32_t>(tree.nodes.size() / 16);
+	out_counts[1] = static_cast<uint32_t>(tree.order.size());
+	out_counts[2] = static_cast<uint32_t>(tree.always.size());
+	out_counts[3] = tree.depth;
+	out_counts[4] = tree.root;
+	if (out_nodes)
+		std::memcpy(out_nodes, tree.nodes.data(), tree.nodes.size() * 4);
+	if (out_order)
+		std::memcpy(out_order, tree.order.data(), tree.order.size() * 4);
+	if (out_corners)
+		std::memcpy(out_corners, tree.corners.data(), tree.corners.size() * 4);
+	if (out_always)
+		std::memcpy(out_always, tree.always.data(), tree.always.size() * 4);
+	return RT_HIP_OK;
 }
 
 extern "C" rt_hip_status rt_hip_kat_closest_hit_bvh_device(rt_hip_ctx* ctx,

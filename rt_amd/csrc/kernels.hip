@@ -44,6 +44,7 @@
 #include "contract.hpp"
 #include "scan.hpp"
 #include "bvh_scan.hpp"
+#include "box_bvh_scan.hpp"
 
 #ifdef RT_HIP_FAST_BUILD
 #define render_queue render_queue_fast
@@ -451,6 +452,10 @@ namespace rt_hip
 		// scan code like the pass builds — scan_resident_boxes, scan_bvh_boxes — so that every other instantiation keeps its symbol and its
 		// instructions; the box count and the table's pointer are device_scene's.  (Staged rather than read through scalar loads: the
 		// scalar-load build's scalar registers are spoken for by its two groups of four spheres, and 8 KiB of LDS cost no occupancy here.)
+		// BOXTREE (RT_HIP_FLAG_BOX_BVH; the hierarchy kernel only): scan_bvh_boxtree, a box build that stages nothing — the boxes are
+		// reached through a hierarchy of their own (box_bvh_scan.hpp), walked per lane on the stack the sphere traversal has finished with; its
+		// descriptor lies behind the sphere hierarchy's, where item_sums points, so no argument is added.  A lane the traversal does not take
+		// (a zero or non-finite component) scans s.box_bounds in memory; the winning box's corners are read there too.
 		template <int SCAN, bool SM, bool HALF = false, int NP = 0, bool GC = false>
 		__global__ __launch_bounds__(block_threads, waves_per_simd(scan_of(SCAN), NP)) void render_queue(const frame_params p,
 																	  const queue_params q,
@@ -467,6 +472,7 @@ namespace rt_hip
 			constexpr int NS = scan_of(SCAN);
 			constexpr bool PASS = scan_is_pass(SCAN);
 			constexpr bool BOXES = scan_has_boxes(SCAN);
+			constexpr bool BOXTREE = scan_has_box_tree(SCAN);
 			static_assert(!PASS || !HALF, "passes are built for whole chunks only");
 			static_assert(!BOXES || !HALF, "the box builds are built for whole chunks only");
 			extern __shared__ float4 lds[];
@@ -484,7 +490,7 @@ namespace rt_hip
 			uint32_t table_float4s = NS > 0 ? small_table_float4s : (RESIDENT ? lds_spheres + s.n_planes : (NS == scan_tiled ? tile_primitives : (BVH ? bvh_stack_float4s : 0u)));
 			// [BOXES] the boxes' corners behind that table (launch_plan.cpp: at most box_max_count, and the whole within a workgroup's LDS)
 			float4* const lds_boxes = lds + table_float4s;
-			if constexpr (BOXES)
+			if constexpr (BOXES && !BOXTREE)
 				table_float4s += 2u * s.n_boxes;
 			if (NS > 0)
 			{
@@ -505,7 +511,7 @@ namespace rt_hip
 				for (uint32_t i = threadIdx.x; i < lds_spheres + s.n_planes; i += block_threads)
 					lds[i] = s.primitive_geometry[(s.n_spheres - lds_spheres) + i];
 			}
-			if constexpr (BOXES)
+			if constexpr (BOXES && !BOXTREE)
 			{
 				for (uint32_t i = threadIdx.x; i < 2u * s.n_boxes; i += block_threads)
 					lds_boxes[i] = s.box_bounds[i];
@@ -524,6 +530,10 @@ namespace rt_hip
 			device_bvh bvh{};
 			if constexpr (BVH)
 				bvh = *reinterpret_cast<const device_bvh*>(item_sums);
+			// [BOXTREE] ... and the boxes' hierarchy, whose descriptor lies behind it
+			device_box_bvh box_tree{};
+			if constexpr (BOXTREE)
+				box_tree = *reinterpret_cast<const device_box_bvh*>(reinterpret_cast<const unsigned char*>(item_sums) + box_bvh_descriptor_offset);
 			// the camera form a scalar-register kernel is built for: the pinhole form, or (GC) the eye form.  A matrix without a
 			// finite eye (an orthographic frustum: nothing rt's camera can produce) takes the LDS-resident kernel, which carries all
 			// three forms — together with seven spheres their scalars do not fit the scalar registers, and hipcc then reloads the
@@ -1027,7 +1037,20 @@ namespace rt_hip
 						else
 							scan_lds<true>(spheres, st.origin, st.dir, primitives, s.n_spheres, 0);
 						uint32_t index;
-						if constexpr (BOXES)
+						if constexpr (BOXTREE)
+						{
+							candidate boxes = { 0.0f, 0u, false };
+							const vec3 inv = box_reciprocals(st.dir);
+							// (the lane's stack again: the sphere traversal above has returned)
+							if (!bvh_boxes(boxes, st.origin, inv, box_tree, s.box_bounds, reinterpret_cast<uint32_t*>(lds) + threadIdx.x))
+							{
+								boxes = { 0.0f, 0u, false }; // a zero, subnormal or non-finite component: the linear scan decides
+								scan_boxes(boxes, st.origin, inv, s.box_bounds, s.n_boxes);
+							}
+							kind = select_hit(spheres, planes, boxes, distance, index);
+							fetch_hit<SM>(s, s.box_bounds, st.origin, st.dir, inv, kind, distance, index, normal, shading, scatter_kind);
+						}
+						else if constexpr (BOXES)
 						{
 							candidate boxes = { 0.0f, 0u, false };
 							const vec3 inv = box_reciprocals(st.dir);
@@ -1658,6 +1681,13 @@ namespace rt_hip
 			{
 				if (plan.build.boxes) // (RT_HIP_FLAG_TRACE_BOXES with at least one box: whole chunks, never a pass — the plan's and the API's rules)
 				{
+					if constexpr (NS == scan_bvh)
+						if (plan.build.box_tree) // (RT_HIP_FLAG_BOX_BVH: rolling.bvh is then the pair of descriptors, render.hip)
+						{
+							hipLaunchKernelGGL((render_queue<scan_bvh_boxtree, SM, false, NP, GC>), grid, dim3(block_threads), plan.lds_bytes, a.stream, a.frame, plan.queue, a.small, a.scene, a.scene.primitive_geometry, a.d_rgba8, a.d_rgb_f32, a.d_counters,
+											   item_sums, a.rolling.pixel_done);
+							return;
+						}
 					constexpr int box_scan = NS == scan_bvh ? scan_bvh_boxes : scan_resident_boxes;
 					hipLaunchKernelGGL((render_queue<box_scan, SM, false, NP, GC>), grid, dim3(block_threads), plan.lds_bytes, a.stream, a.frame, plan.queue, a.small, a.scene, a.scene.primitive_geometry, a.d_rgba8, a.d_rgb_f32, a.d_counters, item_sums,
 									   a.rolling.pixel_done);

@@ -206,12 +206,18 @@ namespace rt_hip
 		const bool boxes = (request.flags & RT_HIP_FLAG_TRACE_BOXES) && request.n_boxes != 0u;
 		if (boxes)
 			kernel = (kernel == RT_HIP_KERNEL_BVH || kernel == RT_HIP_KERNEL_STREAMED) ? RT_HIP_KERNEL_BVH : RT_HIP_KERNEL_RESIDENT;
+		// RT_HIP_FLAG_BOX_BVH: the boxes through their own hierarchy, which walks the hierarchy kernel's per-lane stacks — that kernel
+		// whatever the sphere count (its sphere tree may be empty)
+		const bool box_tree = boxes && (request.flags & RT_HIP_FLAG_BOX_BVH);
+		if (box_tree)
+			kernel = RT_HIP_KERNEL_BVH;
 		plan.variant = pixels ? kernel : static_cast<uint32_t>(RT_HIP_KERNEL_NONE);
 		const bool big_scene = plan.big_scene = kernel == RT_HIP_KERNEL_TILED || kernel == RT_HIP_KERNEL_STREAMED;
 		const queue_params queue = plan.queue = choose_queue(pass ? request.pass_samples : request.samples_per_pixel, request.width, request.local_rows, big_scene, request.host_frame, (pass || boxes) ? 0 : half_chunk_choice(request.flags),
 															 request.n_spheres + request.n_planes, kernel == RT_HIP_KERNEL_STREAMED && request.n_spheres >= sparse_launch_min_spheres);
 		plan.build.pass = pass;
 		plan.build.boxes = boxes;
+		plan.build.box_tree = box_tree;
 		plan.first_chunk = pass ? request.pass_first_sample / sample_chunk : 0u;
 
 		// small scenes: one wave per tile, four tiles side by side per workgroup.  Big scenes: a persistent launch — what
@@ -262,7 +268,13 @@ namespace rt_hip
 				plan.table_bytes = tile_primitives * float4_bytes;
 				break;
 		}
-		if (boxes)
+		if (box_tree)
+		{
+			// nothing is staged: the stacks alone, and no cap on the count (the tree's own is the builder's to refuse)
+			if (plan.table_bytes + plan.slot_bytes > workgroup_lds_bytes)
+				std::snprintf(plan.refusal, sizeof(plan.refusal), "RT_HIP_FLAG_BOX_BVH: %zu bytes of stacks and %zu of chunk sums do not fit a workgroup's %zu bytes of LDS", plan.table_bytes, plan.slot_bytes, workgroup_lds_bytes);
+		}
+		else if (boxes)
 		{
 			// the boxes' corners behind the scan's own table: the planes (and LDS-scanned spheres) of the resident kernel, the hierarchy kernel's stacks
 			plan.table_bytes += static_cast<size_t>(request.n_boxes) * 2u * float4_bytes;

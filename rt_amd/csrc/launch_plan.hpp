@@ -93,7 +93,7 @@ namespace rt_hip
 	constexpr uint32_t bvh_stack_float4s = 24u * 256u / 4u; // the BVH kernel's LDS traversal stacks: bvh_max_depth words per thread (bvh.hpp, kernels.hip)
 	constexpr uint32_t tile_primitives = 1024;		   // primitives per LDS tile in the tiled kernel
 	// RT_HIP_FLAG_TRACE_BOXES: the box builds scan the boxes linearly from LDS, two float4s each (the corners), staged behind the scan's own
-	// table — 8 KiB at the most; a hierarchy over boxes is not built
+	// table — 8 KiB at the most.  (RT_HIP_FLAG_BOX_BVH's frames reach the boxes through a hierarchy instead and know no such cap.)
 	constexpr uint32_t box_max_count = 256;
 	constexpr size_t workgroup_lds_bytes = 64u * 1024u; // what one workgroup may ask for
 
@@ -116,13 +116,17 @@ namespace rt_hip
 		// the BOX builds of the same two scans (kernel_build::boxes; RT_HIP_FLAG_TRACE_BOXES): the scene's boxes staged into LDS behind
 		// the scan's own table and scanned after spheres and planes
 		scan_resident_boxes = -7,
-		scan_bvh_boxes = -8
+		scan_bvh_boxes = -8,
+		// RT_HIP_FLAG_BOX_BVH (kernel_build::box_tree): the hierarchy kernel with the boxes reached through a hierarchy of their own
+		// (box_bvh_scan.hpp) on the same per-lane stacks — nothing staged into LDS, no cap of box_max_count
+		scan_bvh_boxtree = -9
 	};
 	constexpr bool scan_is_pass(int code) { return code == scan_resident_pass || code == scan_bvh_pass; }
-	constexpr bool scan_has_boxes(int code) { return code == scan_resident_boxes || code == scan_bvh_boxes; }
+	constexpr bool scan_has_boxes(int code) { return code == scan_resident_boxes || code == scan_bvh_boxes || code == scan_bvh_boxtree; }
+	constexpr bool scan_has_box_tree(int code) { return code == scan_bvh_boxtree; }
 	constexpr int scan_of(int code) // the scan a build's code stands for
 	{
-		return (code == scan_resident_pass || code == scan_resident_boxes) ? static_cast<int>(scan_resident) : ((code == scan_bvh_pass || code == scan_bvh_boxes) ? static_cast<int>(scan_bvh) : code);
+		return (code == scan_resident_pass || code == scan_resident_boxes) ? static_cast<int>(scan_resident) : ((code == scan_bvh_pass || code == scan_bvh_boxes || code == scan_bvh_boxtree) ? static_cast<int>(scan_bvh) : code);
 	}
 	// the rolling kernels are launched persistent: as many workgroups as the device keeps resident (launch_cache, kernels.hpp)
 	constexpr bool scan_is_persistent(int scan) { return scan == scan_tiled || scan == scan_streamed || scan == scan_streamed_dense; }
@@ -150,7 +154,8 @@ namespace rt_hip
 		// Both 0: a frame in one launch, planned as it always was.
 		uint32_t pass_first_sample = 0, pass_samples = 0;
 		// RT_HIP_FLAG_TRACE_BOXES: the resident scene's boxes (device_scene::n_boxes).  Without the flag, or with none, a frame is planned
-		// as it always was, field for field.
+		// as it always was, field for field.  With RT_HIP_FLAG_BOX_BVH too (and at least one box) the frame is planned onto the hierarchy
+		// kernel's scan_bvh_boxtree build whatever the sphere count, with the stacks as its only table.
 		uint32_t n_boxes = 0;
 	};
 
@@ -164,6 +169,7 @@ namespace rt_hip
 		bool sm_table;		  // SM: RT_HIP_FLAG_SM_MATERIALS
 		bool pass;			  // one pass of a progressive frame: the scan's PASS build (scan_resident_pass / scan_bvh_pass; `scan` stays the scan proper)
 		bool boxes;			  // RT_HIP_FLAG_TRACE_BOXES with at least one box: the scan's BOX build (scan_resident_boxes / scan_bvh_boxes)
+		bool box_tree;		  // ... and RT_HIP_FLAG_BOX_BVH: the hierarchy kernel's scan_bvh_boxtree build (`boxes` is set too)
 	};
 
 	struct launch_plan
@@ -182,7 +188,7 @@ namespace rt_hip
 		int persistent_slot; // index into launch_cache::persistent, or -1: not a persistent launch
 		int per_cu_cap;		 // persistent launches: workgroups per CU at most
 		uint32_t first_chunk; // a pass: the chunk of every pixel its items start at (queue.chunks is the PASS's chunk count); else 0
-		// a frame with traced boxes that is NOT launched (RT_HIP_UNSUPPORTED with this text): more than box_max_count boxes, or tables and
+		// a frame with traced boxes that is NOT launched (RT_HIP_UNSUPPORTED with this text): more than box_max_count boxes without a tree, or tables and
 		// chunk sums beyond a workgroup's LDS.  Empty: the plan stands.
 		char refusal[160];
 	};

@@ -138,6 +138,12 @@ rt_hip_status render_device(rt_hip_ctx* ctx, uint32_t width, uint32_t height, ui
 			RT_HIP_TRY(hipSetDevice(ctx->device));
 			rolling.bvh = bvh = ctx->bvh_descriptor;
 		}
+		if (plan.build.box_tree) // RT_HIP_FLAG_BOX_BVH: the box hierarchy's descriptor travels behind (a copy of) the sphere hierarchy's
+		{
+			if (const rt_hip_status st = ensure_box_bvh(ctx, s))
+				return st;
+			rolling.bvh = ctx->box_bvh_block.as<const device_bvh>();
+		}
 		if (pass)
 			rolling.accum = pass->d_accum;
 		// big scenes: they meet in HBM, 16 bytes per chunk (or per sample) of this rank's rows

@@ -6,6 +6,8 @@
 // whose split float columns none of its renderers reads.
 #include "internal.hpp"
 #include "bvh.hpp"
+#include "box_bvh.hpp"
+#include "box_bvh_scan.hpp"
 #include "bvh_build.hpp"
 #include "bvh_build_device.hpp"
 
@@ -299,6 +301,15 @@ namespace rt_hip
 			ctx->scene_fingerprint = r.print;
 			ctx->scene_bytes = L.total;
 			ctx->scene_uploads++; // (a sphere hierarchy built for the previous scene is stale from here on: ensure_bvh)
+			// ... and a box hierarchy only if the box pairs themselves changed (ensure_box_bvh): FNV-1a over their words
+			uint64_t box_print = 0xcbf29ce484222325ull ^ s.n_boxes;
+			for (size_t k = 0; k < static_cast<size_t>(s.n_boxes) * 8u; k++)
+			{
+				uint32_t word;
+				std::memcpy(&word, r.image + L.box_bounds + k * 4u, 4);
+				box_print = (box_print ^ word) * 0x100000001b3ull;
+			}
+			ctx->box_columns_print = box_print;
 			ctx->small = r.small;
 			ctx->small_sm = r.small_sm;
 
@@ -426,6 +437,65 @@ namespace rt_hip
 		ctx->bvh_built_for = ctx->scene_uploads;
 		ctx->bvh_device_built = false;
 		ctx->stats.upload_ms += static_cast<float>(seconds_since(t0) * 1e3);
+		return ok();
+	}
+
+	rt_hip_status ensure_box_bvh(rt_hip_ctx* ctx, hipStream_t stream)
+	{
+		RT_HIP_TRY(hipSetDevice(ctx->device));
+		const uint32_t n = ctx->scene.n_boxes;
+		if (!(ctx->box_bvh_built && ctx->box_bvh_print == ctx->box_columns_print && ctx->box_bvh_count == n))
+		{
+			const auto t0 = std::chrono::steady_clock::now();
+			RT_HIP_TRY(hipDeviceSynchronize()); // a previous frame may still be reading the old tree
+			ctx->box_bvh_built = false;
+			ctx->box_bvh_sphere_stamp = 0;
+			// from the pairs read back from the device: the very floats the linear box builds read
+			std::vector<float> bounds(static_cast<size_t>(n) * 8);
+			if (n)
+				RT_HIP_TRY(hipMemcpy(bounds.data(), ctx->scene.box_bounds, static_cast<size_t>(n) * 2u * sizeof(float4), hipMemcpyDeviceToHost));
+			box_bvh_host tree;
+			std::string why;
+			if (!build_box_bvh(bounds.data(), n, tree, why))
+				return fail(RT_HIP_UNSUPPORTED, "RT_HIP_FLAG_BOX_BVH: %s", why.c_str());
+			// one block: the two descriptors the kernel reads first, nodes, leaf-ordered corners, their scene indices, the always
+			// list (256-byte aligned starts)
+			const auto aligned = [](size_t bytes) { return (bytes + 255u) & ~static_cast<size_t>(255u); };
+			const size_t nodes_at = aligned(box_bvh_descriptor_offset + sizeof(device_box_bvh)), corners_at = nodes_at + aligned(tree.nodes.size() * 4), order_at = corners_at + aligned(tree.corners.size() * 4);
+			const size_t always_at = order_at + aligned(tree.order.size() * 4), total = always_at + aligned(tree.always.size() * 4);
+			std::vector<unsigned char> image(total, 0);
+			std::memcpy(image.data() + nodes_at, tree.nodes.data(), tree.nodes.size() * 4);
+			std::memcpy(image.data() + corners_at, tree.corners.data(), tree.corners.size() * 4);
+			std::memcpy(image.data() + order_at, tree.order.data(), tree.order.size() * 4);
+			std::memcpy(image.data() + always_at, tree.always.data(), tree.always.size() * 4);
+			RT_HIP_TRY(ctx->box_bvh_block.reserve(image.size()));
+			unsigned char* const base = ctx->box_bvh_block.as<unsigned char>();
+			device_box_bvh b{};
+			b.nodes = reinterpret_cast<const float4*>(base + nodes_at);
+			b.corners = reinterpret_cast<const float4*>(base + corners_at);
+			b.order = reinterpret_cast<const uint32_t*>(base + order_at);
+			b.always = reinterpret_cast<const uint32_t*>(base + always_at);
+			b.root = tree.root;
+			b.n_tree = static_cast<uint32_t>(tree.order.size());
+			b.n_always = static_cast<uint32_t>(tree.always.size());
+			std::memcpy(image.data() + box_bvh_descriptor_offset, &b, sizeof(b));
+			RT_HIP_TRY(hipMemcpy(ctx->box_bvh_block.ptr, image.data(), image.size(), hipMemcpyHostToDevice));
+			ctx->box_bvh_print = ctx->box_columns_print;
+			ctx->box_bvh_count = n;
+			ctx->box_bvh_built = true;
+			ctx->box_bvh_builds++;
+			ctx->stats.upload_ms += static_cast<float>(seconds_since(t0) * 1e3);
+		}
+		// the sphere hierarchy's descriptor in front, as the kernel expects it where item_sums points (stream-ordered: after a device
+		// build enqueued on `stream`, and after whatever frame of this stream still reads the old copy)
+		const uint64_t stamp = 2u * ctx->bvh_built_for + (ctx->bvh_device_built ? 1u : 0u);
+		if (!ctx->bvh_descriptor || !ctx->bvh_built_for)
+			return fail(RT_HIP_RUNTIME_ERROR, "RT_HIP_FLAG_BOX_BVH: no sphere hierarchy to travel with");
+		if (ctx->box_bvh_sphere_stamp != stamp)
+		{
+			RT_HIP_TRY(hipMemcpyAsync(ctx->box_bvh_block.ptr, ctx->bvh_descriptor, sizeof(device_bvh), hipMemcpyDeviceToDevice, stream));
+			ctx->box_bvh_sphere_stamp = stamp;
+		}
 		return ok();
 	}
 }

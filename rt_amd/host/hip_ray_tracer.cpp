@@ -119,7 +119,11 @@ namespace
 			// RT_HIP_TRACE_BOXES=1 opts in to RT_HIP_FLAG_TRACE_BOXES: the traced frame hits the scene's boxes too (the preview
 			// draws them anyway and ignores the flag; progressive frames refuse it)
 			const char* boxes = std::getenv("RT_HIP_TRACE_BOXES");
-			const uint32_t trace_boxes = (boxes && std::strcmp(boxes, "1") == 0) ? static_cast<uint32_t>(RT_HIP_FLAG_TRACE_BOXES) : static_cast<uint32_t>(RT_HIP_FLAG_NONE);
+			// RT_HIP_BOX_BVH=1, next to it, opts in to RT_HIP_FLAG_BOX_BVH: the boxes through a hierarchy of their own, any number of them,
+			// the same frame bit for bit (without RT_HIP_TRACE_BOXES=1 the module refuses the flag by name; so do temporal frames)
+			const char* box_bvh = std::getenv("RT_HIP_BOX_BVH");
+			const uint32_t trace_boxes = ((boxes && std::strcmp(boxes, "1") == 0) ? static_cast<uint32_t>(RT_HIP_FLAG_TRACE_BOXES) : static_cast<uint32_t>(RT_HIP_FLAG_NONE))
+										 | ((box_bvh && std::strcmp(box_bvh, "1") == 0) ? static_cast<uint32_t>(RT_HIP_FLAG_BOX_BVH) : static_cast<uint32_t>(RT_HIP_FLAG_NONE));
 			if (accel && std::strcmp(accel, "bvh-device") == 0) // ... and builds the hierarchy on the GPU (RT_HIP_FLAG_BVH_DEVICE_BUILD)
 				return static_cast<uint32_t>(RT_HIP_FLAG_BVH | RT_HIP_FLAG_BVH_DEVICE_BUILD) | trace_boxes;
 			return ((accel && std::strcmp(accel, "bvh") == 0) ? static_cast<uint32_t>(RT_HIP_FLAG_BVH) : static_cast<uint32_t>(RT_HIP_FLAG_NONE)) | trace_boxes;

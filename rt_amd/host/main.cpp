@@ -17,6 +17,9 @@
 //                           written is the denoised frame of the last pass
 //   --boxes                 the traced frame hits the scene's boxes too (exported to the renderer as RT_HIP_TRACE_BOXES=1: RT_HIP_FLAG_TRACE_BOXES);
 //                           hip renderers only, not with --progressive
+//   --box-bvh               with --boxes: the boxes are reached through a hierarchy of their own, any number of them, the same frame bit for
+//                           bit (exported to the renderer as RT_HIP_BOX_BVH=1: RT_HIP_FLAG_BOX_BVH); implies nothing on its own and is
+//                           refused without --boxes, and with --temporal
 //   --temporal              every frame is one frame of temporal accumulation (exported to the renderer as RT_HIP_TEMPORAL=1:
 //                           rt_hip_render_temporal): traced whole with a seed of its own and blended with the history kept across camera
 //                           moves; with --denoise the blended frame goes through the a-trous filter too.  Hip renderers only, not with
@@ -137,7 +140,7 @@ int main(int argc, char** argv)
 	unsigned width = 800, height = 600, spp = 0, bounces = 0, frames = 1, rank = 0, world = 1, progressive = 0;
 	bool frames_given = false;
 	bool list = false;
-	bool boxes = false, denoise = false, temporal = false, dolly = false;
+	bool boxes = false, box_bvh = false, denoise = false, temporal = false, dolly = false;
 	float dolly_by[3] = { 0.0f, 0.0f, 0.0f };
 	// default renderer: the first whose name starts with "hip", else the first registered (reference: first "mg", :350)
 	for (auto& r : renderers::all())
@@ -203,6 +206,11 @@ int main(int argc, char** argv)
 			boxes = true;
 			::setenv("RT_HIP_TRACE_BOXES", "1", 1); // (read by the plug-in: RT_HIP_FLAG_TRACE_BOXES, the traced frame hits the scene's boxes)
 		}
+		else if (arg == "--box-bvh"sv)
+		{
+			box_bvh = true;
+			::setenv("RT_HIP_BOX_BVH", "1", 1); // (read by the plug-in: RT_HIP_FLAG_BOX_BVH, the boxes through their own hierarchy)
+		}
 		else if (arg == "--temporal"sv)
 		{
 			temporal = true;
@@ -226,7 +234,7 @@ int main(int argc, char** argv)
 			world = static_cast<unsigned>(std::strtoul(value(), nullptr, 10));
 		else if (arg == "--help"sv || arg == "-h"sv)
 		{
-			log("usage: rt_headless [--list] [--scene file.toml] [--renderer name] [--size WxH] [--spp N] [--bounces N] [--seed N] [--frames N] [--out file.ppm] [--progressive SAMPLES] [--denoise] [--boxes] [--temporal] [--dolly DX,DY,DZ] [--shared-frame NAME --rank R --world N]");
+			log("usage: rt_headless [--list] [--scene file.toml] [--renderer name] [--size WxH] [--spp N] [--bounces N] [--seed N] [--frames N] [--out file.ppm] [--progressive SAMPLES] [--denoise] [--boxes [--box-bvh]] [--temporal] [--dolly DX,DY,DZ] [--shared-frame NAME --rank R --world N]");
 			return 0;
 		}
 		else
@@ -257,6 +265,11 @@ int main(int argc, char** argv)
 	if (boxes && (progressive || std::string_view{ desc->name }.substr(0, 3) != "hip"sv))
 	{
 		error("--boxes traces the scene's boxes in one-shot frames of a hip renderer (not with --progressive, not '", desc->name, "')");
+		return 2;
+	}
+	if (box_bvh && (!boxes || temporal))
+	{
+		error("--box-bvh says how --boxes reaches the scene's boxes: it needs --boxes, and temporal frames keep the linear scan (not with --temporal)");
 		return 2;
 	}
 	if (temporal && (progressive || std::string_view{ desc->name }.substr(0, 3) != "hip"sv))

@@ -69,6 +69,20 @@ def bvh_build(scene: RtHipScene) -> dict:
     return {"nodes": nodes[:n_nodes], "order": order[:n_tree], "spheres": spheres[:n_tree], "always": always[:n_always], "bound": bound, "depth": depth, "root": root}
 
 
+def box_bvh_build(scene: RtHipScene) -> dict:
+    """The box hierarchy RT_HIP_FLAG_BOX_BVH builds for `scene`, built on the host (rt_hip_kat_box_bvh_build; no GPU needed):
+    nodes float32[N, 16] (links as bits in words 3 and 7), order / always uint32, corners float32[T, 8] (leaf order), depth, root."""
+    n = max(int(scene.n_boxes), 1)
+    counts = np.zeros(5, dtype=np.uint32)
+    nodes = np.zeros((n, 16), dtype=np.float32)
+    order = np.zeros(n, dtype=np.uint32)
+    corners = np.zeros((n, 8), dtype=np.float32)
+    always = np.zeros(n, dtype=np.uint32)
+    capi.check_kat(capi.kat_lib().rt_hip_kat_box_bvh_build(C.byref(scene), counts.ctypes.data, nodes.ctypes.data, order.ctypes.data, corners.ctypes.data, always.ctypes.data))
+    n_nodes, n_tree, n_always, depth, root = (int(c) for c in counts)
+    return {"nodes": nodes[:n_nodes], "order": order[:n_tree], "corners": corners[:n_tree], "always": always[:n_always], "depth": depth, "root": root}
+
+
 def denoise_default_params() -> RtHipDenoiseParams:
     """rt_hip_denoise_default_params: what a NULL `params` stands for (pure host code)."""
     params = RtHipDenoiseParams()
@@ -350,11 +364,18 @@ class HipRayTracer:
         n_nodes, n_tree, n_always, depth, root = (int(c) for c in counts)
         return {"nodes": nodes[:n_nodes], "order": order[:n_tree], "spheres": spheres[:n_tree], "always": always[:n_always], "bound": bound, "depth": depth, "root": root}
 
-    def kat_closest_hit(self, origins: np.ndarray, directions: np.ndarray, bvh: bool = False, device_build: bool = False, boxes: bool = False):
+    def kat_box_bvh_builds(self) -> int:
+        """How many box hierarchies (RT_HIP_FLAG_BOX_BVH) this context has built on the host so far (rt_hip_kat_box_bvh_builds)."""
+        builds = C.c_uint64(0)
+        capi.check_kat(capi.kat_lib().rt_hip_kat_box_bvh_builds(self._ctx, C.byref(builds)))
+        return int(builds.value)
+
+    def kat_closest_hit(self, origins: np.ndarray, directions: np.ndarray, bvh: bool = False, device_build: bool = False, boxes: bool = False, box_bvh: bool = False):
         """Closest hit of each ray against the resident scene: (distance, kind, index, normal).  `bvh`: through the sphere
         hierarchy of RT_HIP_FLAG_BVH (rt_hip_kat_closest_hit_bvh) instead of the linear scan; `device_build`: through the
         hierarchy the device builder makes (rt_hip_kat_closest_hit_bvh_device); `boxes`: RT_HIP_FLAG_TRACE_BOXES' query, the
-        scene's boxes included (rt_hip_kat_closest_hit_boxes; kind 3 = box)."""
+        scene's boxes included (rt_hip_kat_closest_hit_boxes; kind 3 = box); `box_bvh`: the same with the boxes reached through
+        RT_HIP_FLAG_BOX_BVH's hierarchy, any number of them (rt_hip_kat_closest_hit_boxes_bvh)."""
         o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
         d = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
         n = len(o)
@@ -366,6 +387,8 @@ class HipRayTracer:
         entry = kat.rt_hip_kat_closest_hit_bvh_device if device_build else (kat.rt_hip_kat_closest_hit_bvh if bvh else kat.rt_hip_kat_closest_hit)
         if boxes:
             entry = kat.rt_hip_kat_closest_hit_boxes
+        if box_bvh:
+            entry = kat.rt_hip_kat_closest_hit_boxes_bvh
         capi.check_kat(entry(self._ctx, n, o.ctypes.data, d.ctypes.data, dist.ctypes.data, kind.ctypes.data, index.ctypes.data, normal.ctypes.data))
         return dist, kind, index, normal
 
