@@ -727,6 +727,142 @@ RT_HIP_API rt_hip_status rt_hip_render_temporal(rt_hip_ctx* ctx,
 									rt_hip_stats* stats,
 									rt_hip_temporal_info* out_info);
 
+/* ---- adaptive sampling: passes that stop converged pixels ---------------------------------------------------------------- */
+/*
+ * rt_hip_render_progressive gives every pixel the same number of samples.  An ADAPTIVE accumulation is a progressive accumulation
+ * whose passes trace the pixels that are still ACTIVE only: after every whole pass each active pixel's luminance statistics over
+ * its passes are updated, and a pixel STOPS once it and its eight neighbours inside the frame have converged (standard error of
+ * the passes' mean luminance within threshold x (mean + floor), at least min_samples samples, at least two passes).  A stopped
+ * pixel is never traced again; the accumulation is complete when no pixel is active or the cap — the scene's samples_per_pixel,
+ * at most 2^20 — is reached.  The last pass traces what is left up to the cap; a short one counts its samples and judges nobody.
+ * THE PROMISE: pixel (x, y) of the float mean and of the packed frame is, BIT FOR BIT, the one-shot frame's
+ * pixel at samples_per_pixel = n(x, y), where n is the sample map the call returns — a pixel's value is a left fold over 16-sample
+ * chunk sums and a sample's random window does not depend on the sample count, per pixel as per frame.  The stop rule itself is a
+ * contract of its own (+ - x, correctly rounded division, compare-and-select in a fixed order, a NaN never converges): the device's
+ * decisions equal a serial CPU restatement bit for bit.  It is NOT the reference's (the reference has no adaptive sampling).
+ * KNOWN LIMIT: a feature that a pixel's first min_samples samples never found is not found later either — the usual bias of
+ * variance-driven stopping; the 3 x 3 condition narrows it around silhouettes and does not remove it.
+ * The defaults were taken from a CPU simulation on oracle frames, not from a GPU run; DESIGN.md §3.11 says what has been measured
+ * on the device, and nothing here promises a speed-up beyond what it says.
+ * Additions to ABI 6 (RT_HIP_ABI_VERSION stays 6): a caller that may meet an older library looks them up with dlsym.
+ * Flags: those of the passes — RT_HIP_FLAG_SM_MATERIALS, RT_HIP_FLAG_BVH, RT_HIP_FLAG_BVH_DEVICE_BUILD, RT_HIP_FLAG_STATS; every
+ * other flag (RT_HIP_FLAG_FAST and the box flags among them) is refused with RT_HIP_UNSUPPORTED and its name.  Whole images only:
+ * no partition, no multi-GPU, rank or frame-group context at the drop-in level.
+ */
+typedef struct rt_hip_adaptive_params
+{
+	float threshold;	  /* finite, >= 0: the relative standard error a pixel converges at; default 0.03 */
+	float floor;		  /* finite, >= 0: added to the mean luminance, so that dark pixels converge too; default 0.01 */
+	uint32_t min_samples; /* >= 2 x the pass size; above the cap nothing stops and the frame is the progressive frame; default 32 */
+} rt_hip_adaptive_params;
+
+/* the defaults a NULL `params` stands for; pure host code */
+RT_HIP_API rt_hip_status rt_hip_adaptive_default_params(rt_hip_adaptive_params* out_params);
+
+/*
+ * The update step alone, a pure per-pixel operation on DEVICE buffers of a whole width x height frame (row-major, laid out like the
+ * float mean): after a pass of pass_samples samples (a multiple of 16 — or, with whole_pass == 0, whatever the short last pass
+ * traced) whose own fold is in d_pass_sum (3 floats per pixel) and whose running sums are in d_accum (3 floats per pixel),
+ * d_moments (2 floats per pixel: S1, S2) and d_state (one word per pixel: samples held in bits 0-30, "stopped" in bit 31) are
+ * brought up to date and EVERY pixel, stopped or not, is finished from d_accum and its own sample count into d_rgba8_out (and
+ * d_rgb_out, 3 floats per pixel).  first_pass != 0: d_moments and d_state are written and not read.  d_active_pixels (one word,
+ * overwritten): the pixels still active after the step.  A stopped pixel's words are left as they are.  Needs no scene.
+ * Asynchronous on `stream`; on a multi-GPU, rank or frame-group context the root member answers.  The new words travel through a
+ * scratch image of the context (12 bytes per pixel, grown on demand, freed with it), which rt_hip_adaptive_pass_device and
+ * rt_hip_render_adaptive use too: the adaptive calls of one context must be ordered on ONE stream (or by the caller), never run at the
+ * same time on different streams.
+ */
+RT_HIP_API rt_hip_status rt_hip_adaptive_update_device(rt_hip_ctx* ctx,
+									uint32_t width,
+									uint32_t height,
+									uint32_t pass_samples,
+									uint32_t first_pass,
+									uint32_t whole_pass,
+									const rt_hip_adaptive_params* params, /* NULL = defaults */
+									const float* d_accum,
+									const float* d_pass_sum,
+									float* d_moments,
+									uint32_t* d_state,
+									uint32_t* d_rgba8_out,
+									float* d_rgb_out,		   /* nullable */
+									uint32_t* d_active_pixels, /* nullable */
+									void* stream);
+
+/*
+ * One adaptive pass on the resident scene, whole image: samples [first_sample, first_sample + n_samples) of every ACTIVE pixel
+ * (render), then the update step.  first_sample is a multiple of 16; n_samples is the accumulation's pass size (a multiple of 16),
+ * or less in the last pass, which ends on the scene's samples_per_pixel.  first_sample == 0 starts an accumulation: nothing of
+ * d_block is read, and it need not be cleared.
+ *   Whether a pass is WHOLE (the pixels are judged after it) is not an argument: a pass is taken as whole when n_samples is a
+ *   multiple of 16 that divides first_sample — true of every pass of the accumulation's size — and as the short last pass otherwise.
+ *   LIMITATION: a short last pass that happens to be whole chunks dividing first_sample (pass size 32, cap 48: the last pass is
+ *   [32, 48)) is judged as a whole pass of ITS size.  The pixels are unaffected — the cap has been reached, nothing is traced again —
+ *   but the stopped bits and d_active_pixels it leaves are not the contract's.  A caller who reads them keeps the cap a multiple of
+ *   the pass size; rt_hip_render_adaptive knows its pass size and has no such case.
+ *   d_block   DEVICE buffer of 9 x width x height words, the caller's to keep from pass to pass, P = width x height:
+ *               words [0, 3P)   accum     the running sums, exactly rt_hip_render_pass_device's accumulator
+ *               words [3P, 4P)  state     uint32
+ *               words [4P, 7P)  pass_sum  scratch, rewritten by every pass for the pixels it traced
+ *               words [7P, 9P)  moments   S1, S2
+ *   d_rgba8, d_rgb_f32 (nullable), d_active_pixels (nullable): as rt_hip_adaptive_update_device's outputs.
+ */
+RT_HIP_API rt_hip_status rt_hip_adaptive_pass_device(rt_hip_ctx* ctx,
+									uint32_t width,
+									uint32_t height,
+									uint64_t seed,
+									uint32_t flags,
+									uint32_t first_sample,
+									uint32_t n_samples,
+									const rt_hip_adaptive_params* params, /* NULL = defaults */
+									float* d_block,
+									uint32_t* d_rgba8,
+									float* d_rgb_f32,		   /* nullable */
+									uint32_t* d_active_pixels, /* nullable */
+									void* stream);
+
+typedef struct rt_hip_adaptive_info
+{
+	uint32_t samples_done;	 /* samples an ACTIVE pixel holds after this call (the most any pixel holds) */
+	uint32_t samples_total;	 /* the cap: the scene's samples_per_pixel */
+	uint32_t passes;		 /* passes launched for this accumulation so far */
+	uint32_t restarted;		 /* 1: this call started a new accumulation */
+	uint32_t active_pixels;	 /* pixels still active after this call */
+	uint32_t pixels;		 /* width x height */
+	uint64_t samples_traced; /* over all passes so far: the sum of the sample map */
+	uint32_t complete;		 /* 1: no pixel is active or the cap is reached; later calls launch nothing */
+} rt_hip_adaptive_info;
+
+/*
+ * Drop-in level: one call is one adaptive pass, delivered as rt_hip_render_progressive delivers.  pass_samples is rounded up to a
+ * multiple of 16 (0 = 16).  The accumulation starts again if anything the frame depends on differs from the call before — what
+ * rt_hip_render_progressive looks at, and besides the parameters' bit patterns and pass_samples.  Its state belongs to the context
+ * (36 bytes per pixel, grown on demand, freed with it) and is separate from the progressive accumulation, the denoiser's kept
+ * guide and the temporal history.  Denoising it in place is not offered: pass rgb_f32 through rt_hip_denoise_device.
+ *   A call on a COMPLETE accumulation launches nothing: it delivers the kept frame again and reports stats of zero work.
+ *   sample_counts  optional: width x height uint32, the map n(x, y)
+ *   stats          optional: THIS PASS — primary_samples = pixels that were active x the pass's samples, segments = the pass's
+ */
+RT_HIP_API rt_hip_status rt_hip_render_adaptive(rt_hip_ctx* ctx,
+									const rt_hip_scene* scene,
+									uint32_t* pixels_rgba8888,
+									uint32_t width,
+									uint32_t height,
+									uint64_t seed,
+									uint32_t flags,
+									uint32_t pass_samples,
+									const rt_hip_adaptive_params* params, /* NULL = defaults */
+									float* rgb_f32,						  /* nullable */
+									uint32_t* sample_counts,			  /* nullable */
+									rt_hip_stats* stats,
+									rt_hip_adaptive_info* out_info);
+
+/*
+ * Where the most recent successful rt_hip_render_adaptive call of THIS PROCESS (any context, any thread) left its accumulation: what a
+ * driver that reaches the module only through a plug-in's render() asks to learn whether the accumulation is complete (rt_headless
+ * --adaptive).  RT_HIP_INVALID_ARGUMENT before the first such call.  Pure host code, safe to call from any thread.
+ */
+RT_HIP_API rt_hip_status rt_hip_adaptive_last_info(rt_hip_adaptive_info* out_info);
+
 /* Drop the page-lock taken under RT_HIP_FLAG_PERSISTENT_FRAME (see there).  Waits for the context's stream first. */
 RT_HIP_API void rt_hip_forget_frame(rt_hip_ctx* ctx);
 

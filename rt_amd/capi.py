@@ -175,6 +175,25 @@ class RtHipTemporalInfo(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class RtHipAdaptiveParams(C.Structure):
+    """``rt_hip_adaptive_params`` (include/rt_hip.h): when a pixel of an adaptive accumulation has converged."""
+
+    _fields_ = [("threshold", C.c_float), ("floor", C.c_float), ("min_samples", C.c_uint32)]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class RtHipAdaptiveInfo(C.Structure):
+    """``rt_hip_adaptive_info`` (include/rt_hip.h): where an adaptive accumulation stands after a call of rt_hip_render_adaptive."""
+
+    _fields_ = [("samples_done", C.c_uint32), ("samples_total", C.c_uint32), ("passes", C.c_uint32), ("restarted", C.c_uint32), ("active_pixels", C.c_uint32), ("pixels", C.c_uint32), ("samples_traced", C.c_uint64),
+                ("complete", C.c_uint32)]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 # every symbol include/rt_hip.h declares: (name, restype, argtypes)
 RT_HIP_SYMBOLS = [
     ("rt_hip_abi_version", C.c_uint32, []),
@@ -233,6 +252,23 @@ RT_HIP_SYMBOLS = [
         C.c_int,
         [C.c_void_p, C.POINTER(RtHipScene), C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(RtHipTemporalParams), C.POINTER(RtHipDenoiseParams), C.c_void_p, C.POINTER(RtHipStats), C.POINTER(RtHipTemporalInfo)],
     ),
+    ("rt_hip_adaptive_default_params", C.c_int, [C.POINTER(RtHipAdaptiveParams)]),
+    (
+        "rt_hip_adaptive_update_device",
+        C.c_int,
+        [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(RtHipAdaptiveParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    ),
+    (
+        "rt_hip_adaptive_pass_device",
+        C.c_int,
+        [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(RtHipAdaptiveParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    ),
+    (
+        "rt_hip_render_adaptive",
+        C.c_int,
+        [C.c_void_p, C.POINTER(RtHipScene), C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(RtHipAdaptiveParams), C.c_void_p, C.c_void_p, C.POINTER(RtHipStats), C.POINTER(RtHipAdaptiveInfo)],
+    ),
+    ("rt_hip_adaptive_last_info", C.c_int, [C.POINTER(RtHipAdaptiveInfo)]),
     ("rt_hip_forget_frame", None, [C.c_void_p]),
     ("rt_hip_live_frame_locks", C.c_uint32, []),
 ]

@@ -443,6 +443,7 @@ extern "C" void rt_hip_destroy(rt_hip_ctx* ctx)
 	ctx->accum.release();
 	ctx->denoise.release();
 	ctx->temporal.release();
+	ctx->adaptive.release();
 	ctx->counters.release();
 	ctx->frame_rgb.release();
 	ctx->staging_rgb.release();

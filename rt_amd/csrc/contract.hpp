@@ -420,4 +420,9 @@ namespace rt_hip
 		const uint32_t b = static_cast<uint32_t>(clamp01(c.z) * 255.99999f);
 		return (r << 24u) | (g << 16u) | (b << 8u) | 255u;
 	}
+
+	// mg_ray_tracer.cpp:195-200 — what a pixel's sum over n samples becomes: the mean (the float frame's pixel) and, packed, its square
+	// root ("gamma").  The render kernels' finish_pixel and the adaptive update (adaptive.hip) finish a pixel with these two.
+	__device__ __forceinline__ vec3 pixel_mean(vec3 colour, float n) { return { colour.x / n, colour.y / n, colour.z / n }; }
+	__device__ __forceinline__ uint32_t pack_mean(vec3 mean) { return pack_rgba8888({ __builtin_sqrtf(mean.x), __builtin_sqrtf(mean.y), __builtin_sqrtf(mean.z) }); }
 }

@@ -11,6 +11,8 @@
 //                 device level, rt_hip_render_pass_device, is render.hip's)
 //   denoise.hip   the guide-buffer denoiser: its two kernels, rt_hip_guide_device, rt_hip_denoise_device and
 //                 rt_hip_denoise_progressive (parameters: denoise.cpp, host compiler; per-pixel rules: denoise_rules.hpp)
+//   adaptive.hip  adaptive sampling: adaptive_update, rt_hip_adaptive_update_device, rt_hip_adaptive_pass_device and the drop-in
+//                 rt_hip_render_adaptive (parameters, sequencing: adaptive.cpp, host compiler; per-pixel rules: adaptive_rules.hpp)
 //   temporal.hip  temporal accumulation: reproject_frame, rt_hip_reproject_device and the drop-in rt_hip_render_temporal
 //                 (parameters, the forward matrix, same_history: temporal.cpp, host compiler; per-pixel rule: reproject_rules.hpp)
 //   multi.hip     rt_hip_render on several GPUs: stripes, one gather, assemble
@@ -28,6 +30,7 @@
 #include "frame_group.hpp"
 #include "kernels.hpp"
 #include "progressive.hpp"
+#include "adaptive.hpp"
 
 #include <rccl/rccl.h>
 
@@ -208,6 +211,29 @@ namespace rt_hip
 		}
 	};
 
+	// what adaptive sampling keeps on a context (adaptive.hip): everything is grown on demand and freed with the context
+	struct adaptive_accumulation
+	{
+		adaptive_state state;		 // the accumulation in flight (adaptive.hpp)
+		device_buffer block;		 // accum, state, pass_sum, moments: 36 bytes per pixel (rt_hip.h, rt_hip_adaptive_pass_device)
+		device_buffer active;		 // one word: the pixels still active after the last pass
+		device_buffer scratch;		 // the update kernel's output words on their way back (12 bytes per pixel; the device-level call's too)
+		pinned_buffer staging;		 // the results' landing place on the host
+		std::vector<uint32_t> frame; // the complete frame, kept on the host for calls that come after it
+		hipEvent_t end = nullptr;	 // behind the update (passes that keep stats)
+		void release()
+		{
+			for (device_buffer* b : { &block, &active, &scratch })
+				b->release();
+			staging.release();
+			if (end)
+				(void)hipEventDestroy(end);
+			end = nullptr;
+			state = adaptive_state{};
+			frame.clear();
+		}
+	};
+
 	struct frame_delivery; // below: the module-owned frame and the threads that carry it to the caller's buffer
 
 	// (RT_HIP_FLAG_PERSISTENT_FRAME and RT_HIP_FLAG_STATS are rt_hip_render's own: they do not travel to the launch)
@@ -307,6 +333,7 @@ struct rt_hip_ctx
 	std::vector<uint32_t> progressive_frame;  // the finished frame, kept on the host for calls that come after the last pass
 	rt_hip::denoise_state denoise;			  // the denoiser's scratch images and the kept guide (denoise.hip)
 	rt_hip::temporal_state temporal;		  // the history of rt_hip_render_temporal (temporal.hip)
+	rt_hip::adaptive_accumulation adaptive;	  // the accumulation of rt_hip_render_adaptive (adaptive.hip)
 
 	rt_hip_ctx() = default;
 	rt_hip_ctx(const rt_hip_ctx&) = delete;
@@ -364,6 +391,7 @@ namespace rt_hip
 	{
 		uint32_t first_sample, n_samples; // whole chunks, or up to the scene's samples_per_pixel (checked by the caller)
 		float* d_accum;					  // the pixels' running sums, laid out like d_rgb_f32
+		bool adaptive = false;			  // an adaptive pass (adaptive.hip): d_accum is the whole block — accum, state, pass_sum, moments — and no pixel is stored
 	};
 	rt_hip_status render_device(rt_hip_ctx* ctx, uint32_t width, uint32_t height, uint64_t seed, uint32_t flags, const rt_hip_partition* part, uint32_t* d_rgba8, float* d_rgb_f32, void* stream, bool whole_frame_buffers, bool keep_stats, bool host_frame,
 								const render_pass* pass = nullptr);

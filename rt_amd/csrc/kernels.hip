@@ -244,8 +244,7 @@ namespace rt_hip
 		// :195-200 — mean, sqrt "gamma", pack, store
 		__device__ __forceinline__ void finish_pixel(vec3 colour, const frame_params& p, uint32_t lx, uint32_t ly, uint32_t* out_rgba, float* out_rgb)
 		{
-			const float n = static_cast<float>(p.samples_per_pixel);
-			const vec3 mean = { colour.x / n, colour.y / n, colour.z / n };
+			const vec3 mean = pixel_mean(colour, static_cast<float>(p.samples_per_pixel));
 			const size_t o = static_cast<size_t>(output_row(ly, p)) * p.width + lx;
 			if (out_rgb)
 			{
@@ -257,7 +256,7 @@ namespace rt_hip
 			// (rt_hip_render) the pixels then cross PCIe while the rest of the frame is still being traced; an ordinary store
 			// would sit in L2 until the end-of-kernel write-back and put the whole 8 MB transfer behind the kernel
 			// (measured: + 0.10-0.14 ms per frame, profiles/r02/frame_store_ab.txt).  For a frame in HBM it costs nothing.
-			__hip_atomic_store(&out_rgba[o], pack_rgba8888({ __builtin_sqrtf(mean.x), __builtin_sqrtf(mean.y), __builtin_sqrtf(mean.z) }), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+			__hip_atomic_store(&out_rgba[o], pack_mean(mean), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 		}
 
 		// `segments` = the wave's count (wave-uniform: kept in a scalar register, one popcount of the tracing lanes per trip)
@@ -446,6 +445,14 @@ namespace rt_hip
 		// argument, of which NS below is the scan proper — so that every other instantiation keeps its symbol, and with it its place in the
 		// listings the unchanged-kernels check compares (tools/kernel_listing_diff.py).  Neither the accumulator nor first_chunk is an argument
 		// of its own: they travel in words these builds do not read (rolling_buffers::accum, kernels.hpp).
+		// ADAPT (adaptive sampling; scan_resident_adapt, scan_bvh_adapt): a PASS build whose pixels carry a state word — samples
+		// held, and "stopped" in bit 31.  Before its first trip the wave ballots its tile's state words into ONE wave-uniform stop mask (a tile
+		// holds at most 64 pixels: launch_plan.cpp); an item of a stopped pixel is empty, like an item of a pixel outside the frame, and the
+		// fold neither reads nor writes such a pixel; a wave whose in-frame pixels have all stopped leaves at once.  An active pixel folds as
+		// PASS does and stores the pass's OWN fold besides (pass_sum: c0, + c1, ... in chunk order — not a difference of running sums).  These
+		// builds finish no pixel: adaptive_update (adaptive.hip) does that for the whole frame.  State words and pass sums lie in one block
+		// behind the accumulator (rt_hip.h, rt_hip_adaptive_pass_device: accum, state, pass_sum, moments), at offsets frame_params gives: no
+		// argument is added.  The first pass (first_chunk == 0) reads no word of the block.
 		// BOXES (RT_HIP_FLAG_TRACE_BOXES; the same two kernels, whole chunks only): the query also scans the scene's boxes — staged
 		// ONCE per workgroup into LDS behind the scan's own table (the resident kernel's primitives, the hierarchy kernel's stacks), two float4s
 		// each, read with wave-uniform addresses after spheres and planes, no votes — and selects among three candidates (scan.hpp).  Named by
@@ -471,6 +478,7 @@ namespace rt_hip
 		{
 			constexpr int NS = scan_of(SCAN);
 			constexpr bool PASS = scan_is_pass(SCAN);
+			constexpr bool ADAPT = scan_is_adaptive(SCAN);
 			constexpr bool BOXES = scan_has_boxes(SCAN);
 			constexpr bool BOXTREE = scan_has_box_tree(SCAN);
 			static_assert(!PASS || !HALF, "passes are built for whole chunks only");
@@ -562,6 +570,24 @@ namespace rt_hip
 			const uint32_t tile_x0 = (blockIdx.x * 4u + wave) * tile_w;
 			const uint32_t tile_y0 = (gridDim.y - 1u - blockIdx.y) * tile_h;
 			uint32_t next_item = 0; // wave-uniform queue head
+			// [ADAPT] bit i: pixel i of this wave's tile has stopped — not traced, not folded (wave-uniform: one ballot of the tile's state words)
+			unsigned long long tile_stopped = 0;
+			float* pass_sums = nullptr;
+			if constexpr (ADAPT)
+			{
+				const size_t frame_pixels = static_cast<size_t>(p.width) * p.height;
+				const uint32_t* const pixel_state = reinterpret_cast<const uint32_t*>(accum + 3u * frame_pixels);
+				pass_sums = accum + 4u * frame_pixels;
+				const uint32_t lx = tile_x0 + (lane & (tile_w - 1u));
+				const uint32_t ly = tile_y0 + (lane >> q.tile_w_log2);
+				const bool in_frame = lane < (1u << q.pixels_log2) && lx < p.width && ly < p.local_rows;
+				bool stopped = false;
+				if (first_chunk && in_frame) // (the first pass reads nothing: every pixel is active)
+					stopped = (pixel_state[static_cast<size_t>(output_row(ly, p)) * p.width + lx] & 0x80000000u) != 0u;
+				tile_stopped = __builtin_amdgcn_ballot_w64(stopped);
+				if ((__builtin_amdgcn_ballot_w64(in_frame) & ~tile_stopped) == 0) // nothing to trace, nothing to fold (no barrier follows in these kernels)
+					return;
+			}
 
 			// rolling items: the launch-wide sequence, the block this wave is handing out, the block drawn ahead
 			// rolling + HALF: a pixel is cut into items of q.item_samples consecutive samples, whatever the chunks are
@@ -601,6 +627,39 @@ namespace rt_hip
 			// all items of a tile are in: fold the chunk sums of each pixel in chunk order and write it (:195-200)
 			const auto fold_tile = [&](const float* sums, uint32_t x0, uint32_t y0)
 			{
+				if constexpr (ADAPT)
+				{
+					// The adaptive builds' fold, in a block of its own so that every other build's text stays what it was.  Per value — a
+					// channel of a pixel where the tile has at most 16 pixels (lane = channel * P + pixel), else a pixel's three — the running sum
+					// goes on as PASS's does and the pass's OWN fold (c0, + c1, ... in chunk order) is stored next to it; a stopped pixel is
+					// neither read nor written; no pixel is finished.
+					const bool by_channel = (3u << q.pixels_log2) <= 64u; // wave-uniform
+					const uint32_t pixel = by_channel ? lane & ((1u << q.pixels_log2) - 1u) : lane;
+					const uint32_t first_channel = by_channel ? lane >> q.pixels_log2 : 0u;
+					const uint32_t channels = by_channel ? (first_channel < 3u ? 1u : 0u) : 3u;
+					const uint32_t lx = x0 + (pixel & (tile_w - 1u));
+					const uint32_t ly = y0 + (pixel >> q.tile_w_log2);
+					if (pixel < (1u << q.pixels_log2) && lx < p.width && ly < p.local_rows && !((tile_stopped >> pixel) & 1ull))
+					{
+						const size_t at_pixel = (static_cast<size_t>(output_row(ly, p)) * p.width + lx) * 3u;
+						for (uint32_t k = 0; k < channels; k++)
+						{
+							const uint32_t channel = first_channel + k;
+							const float c0 = sums[pixel * 3u + channel];
+							float own = c0;
+							float sum = first_chunk ? accum[at_pixel + channel] + c0 : c0;
+							for (uint32_t c = 1; c < q.chunks; c++)
+							{
+								const float next = sums[((c << q.pixels_log2) + pixel) * 3u + channel];
+								sum = sum + next;
+								own = own + next;
+							}
+							accum[at_pixel + channel] = sum;
+							pass_sums[at_pixel + channel] = own;
+						}
+					}
+					return;
+				}
 				if (!ROLLING && (3u << q.pixels_log2) <= 64u) // wave-uniform
 				{
 					// Small tiles (<= 16 pixels: from 113 samples per pixel upwards) are folded one CHANNEL per lane — lane
@@ -1146,7 +1205,13 @@ namespace rt_hip
 					const uint32_t chunk = item >> q.pixels_log2;
 					const uint32_t lx = x0 + (pixel & (tile_w - 1u));
 					const uint32_t ly = y0 + (pixel >> q.tile_w_log2);
-					if (lx < p.width && ly < p.local_rows)
+					if constexpr (ADAPT)
+					{
+						if (lx < p.width && ly < p.local_rows && !((tile_stopped >> pixel) & 1ull))
+							start_item(lx, ly, chunk);
+						// else: outside the frame, or a stopped pixel — the item is empty, ask again next trip
+					}
+					else if (lx < p.width && ly < p.local_rows)
 						start_item(lx, ly, chunk);
 					// else: a pixel outside the frame — the item is empty, ask again next trip
 				};
@@ -1691,6 +1756,15 @@ namespace rt_hip
 					constexpr int box_scan = NS == scan_bvh ? scan_bvh_boxes : scan_resident_boxes;
 					hipLaunchKernelGGL((render_queue<box_scan, SM, false, NP, GC>), grid, dim3(block_threads), plan.lds_bytes, a.stream, a.frame, plan.queue, a.small, a.scene, a.scene.primitive_geometry, a.d_rgba8, a.d_rgb_f32, a.d_counters, item_sums,
 									   a.rolling.pixel_done);
+					return;
+				}
+				if (plan.build.adaptive) // (an adaptive pass: as the pass below; rolling.accum is the block of accumulator, state words, pass sums and moments)
+				{
+					constexpr int adapt_scan = NS == scan_bvh ? scan_bvh_adapt : scan_resident_adapt;
+					queue_params queue = plan.queue;
+					queue.block_items = plan.first_chunk;
+					hipLaunchKernelGGL((render_queue<adapt_scan, SM, false, NP, GC>), grid, dim3(block_threads), plan.lds_bytes, a.stream, a.frame, queue, a.small, a.scene, a.scene.primitive_geometry, a.d_rgba8, a.d_rgb_f32, a.d_counters, item_sums,
+									   reinterpret_cast<uint32_t*>(a.rolling.accum));
 					return;
 				}
 				if (plan.build.pass) // (a pass of a progressive frame: first_chunk and the accumulator in the words these kernels do not read)

@@ -213,9 +213,24 @@ namespace rt_hip
 			kernel = RT_HIP_KERNEL_BVH;
 		plan.variant = pixels ? kernel : static_cast<uint32_t>(RT_HIP_KERNEL_NONE);
 		const bool big_scene = plan.big_scene = kernel == RT_HIP_KERNEL_TILED || kernel == RT_HIP_KERNEL_STREAMED;
-		const queue_params queue = plan.queue = choose_queue(pass ? request.pass_samples : request.samples_per_pixel, request.width, request.local_rows, big_scene, request.host_frame, (pass || boxes) ? 0 : half_chunk_choice(request.flags),
+		queue_params queue = choose_queue(pass ? request.pass_samples : request.samples_per_pixel, request.width, request.local_rows, big_scene, request.host_frame, (pass || boxes) ? 0 : half_chunk_choice(request.flags),
 															 request.n_spheres + request.n_planes, kernel == RT_HIP_KERNEL_STREAMED && request.n_spheres >= sparse_launch_min_spheres);
+		// An adaptive pass: the wave's stop mask is one ballot of its tile's state words — a tile of at most 64 pixels.  choose_queue cuts
+		// 128-pixel tiles for one-chunk passes of frames beyond 6M pixels only; those are halved here (the short side first, as it would).
+		const bool adaptive = pass && request.adaptive;
+		if (adaptive && (1u << queue.pixels_log2) > adaptive_max_tile_pixels)
+		{
+			queue.pixels_log2 = 6u;
+			queue.tile_w_log2 = std::min(queue.tile_w_log2, 4u); // (64 pixels: 8 x 8, or 16 x 4 for a page-locked frame)
+			if (!request.host_frame)
+				queue.tile_w_log2 = 3u;
+			const uint32_t tile_w = 1u << queue.tile_w_log2, tile_h = (1u << queue.pixels_log2) >> queue.tile_w_log2;
+			queue.tiles_x = (request.width + tile_w - 1u) / tile_w;
+			queue.tiles_y = (request.local_rows + tile_h - 1u) / tile_h;
+		}
+		plan.queue = queue;
 		plan.build.pass = pass;
+		plan.build.adaptive = adaptive;
 		plan.build.boxes = boxes;
 		plan.build.box_tree = box_tree;
 		plan.first_chunk = pass ? request.pass_first_sample / sample_chunk : 0u;

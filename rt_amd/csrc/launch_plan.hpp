@@ -119,14 +119,21 @@ namespace rt_hip
 		scan_bvh_boxes = -8,
 		// RT_HIP_FLAG_BOX_BVH (kernel_build::box_tree): the hierarchy kernel with the boxes reached through a hierarchy of their own
 		// (box_bvh_scan.hpp) on the same per-lane stacks — nothing staged into LDS, no cap of box_max_count
-		scan_bvh_boxtree = -9
+		scan_bvh_boxtree = -9,
+		// the ADAPTIVE builds of the two pass builds (kernel_build::adaptive): a pass that reads the pixels' state words,
+		// traces and folds the active pixels only, stores the pass's own fold next to the running sum and finishes no pixel
+		scan_resident_adapt = -10,
+		scan_bvh_adapt = -11
 	};
-	constexpr bool scan_is_pass(int code) { return code == scan_resident_pass || code == scan_bvh_pass; }
+	constexpr bool scan_is_adaptive(int code) { return code == scan_resident_adapt || code == scan_bvh_adapt; }
+	constexpr bool scan_is_pass(int code) { return code == scan_resident_pass || code == scan_bvh_pass || scan_is_adaptive(code); }
 	constexpr bool scan_has_boxes(int code) { return code == scan_resident_boxes || code == scan_bvh_boxes || code == scan_bvh_boxtree; }
 	constexpr bool scan_has_box_tree(int code) { return code == scan_bvh_boxtree; }
 	constexpr int scan_of(int code) // the scan a build's code stands for
 	{
-		return (code == scan_resident_pass || code == scan_resident_boxes) ? static_cast<int>(scan_resident) : ((code == scan_bvh_pass || code == scan_bvh_boxes || code == scan_bvh_boxtree) ? static_cast<int>(scan_bvh) : code);
+		return (code == scan_resident_pass || code == scan_resident_boxes || code == scan_resident_adapt)
+				   ? static_cast<int>(scan_resident)
+				   : ((code == scan_bvh_pass || code == scan_bvh_boxes || code == scan_bvh_boxtree || code == scan_bvh_adapt) ? static_cast<int>(scan_bvh) : code);
 	}
 	// the rolling kernels are launched persistent: as many workgroups as the device keeps resident (launch_cache, kernels.hpp)
 	constexpr bool scan_is_persistent(int scan) { return scan == scan_tiled || scan == scan_streamed || scan == scan_streamed_dense; }
@@ -157,7 +164,11 @@ namespace rt_hip
 		// as it always was, field for field.  With RT_HIP_FLAG_BOX_BVH too (and at least one box) the frame is planned onto the hierarchy
 		// kernel's scan_bvh_boxtree build whatever the sphere count, with the stacks as its only table.
 		uint32_t n_boxes = 0;
+		// An ADAPTIVE pass (set by the adaptive entry points only, with pass_samples != 0): the pass's adaptive build, whose
+		// waves ballot their tile's state words into ONE 64-bit stop mask — so a tile holds at most adaptive_max_tile_pixels pixels.
+		bool adaptive = false;
 	};
+	constexpr uint32_t adaptive_max_tile_pixels = 64;
 
 	// the instantiation render_queue<scan, sm_table, sub_chunk_items, planes, general_camera>
 	struct kernel_build
@@ -170,6 +181,7 @@ namespace rt_hip
 		bool pass;			  // one pass of a progressive frame: the scan's PASS build (scan_resident_pass / scan_bvh_pass; `scan` stays the scan proper)
 		bool boxes;			  // RT_HIP_FLAG_TRACE_BOXES with at least one box: the scan's BOX build (scan_resident_boxes / scan_bvh_boxes)
 		bool box_tree;		  // ... and RT_HIP_FLAG_BOX_BVH: the hierarchy kernel's scan_bvh_boxtree build (`boxes` is set too)
+		bool adaptive;		  // an adaptive pass: the scan's ADAPT build (scan_resident_adapt / scan_bvh_adapt; implies `pass`)
 	};
 
 	struct launch_plan

@@ -119,7 +119,7 @@ rt_hip_status render_device(rt_hip_ctx* ctx, uint32_t width, uint32_t height, ui
 		request.n_spheres = ctx->scene.n_spheres, request.n_planes = ctx->scene.n_planes, request.planes_tame = ctx->scene.planes_tame != 0;
 		request.width = width, request.local_rows = f.local_rows, request.samples_per_pixel = pass ? ctx->samples_per_pixel : f.samples_per_pixel;
 		if (pass)
-			request.pass_first_sample = pass->first_sample, request.pass_samples = pass->n_samples;
+			request.pass_first_sample = pass->first_sample, request.pass_samples = pass->n_samples, request.adaptive = pass->adaptive;
 		request.camera = camera_form_of(f);
 		request.flags = flags, request.host_frame = host_frame, request.fast_arithmetic = (flags & RT_HIP_FLAG_FAST) != 0;
 		request.n_boxes = ctx->scene.n_boxes;

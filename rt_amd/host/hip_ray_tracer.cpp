@@ -181,6 +181,31 @@ namespace
 		return on;
 	}
 
+	// RT_HIP_ADAPTIVE=<threshold> makes render() one PASS of an ADAPTIVE accumulation (rt_hip_render_adaptive): passes of RT_HIP_PROGRESSIVE
+	// samples (16 where that is unset) over the pixels that have not converged yet, until none is left or the scene's samples_per_pixel
+	// are in.  The threshold replaces the default parameters' (the other two stay; min_samples is at least two passes).  Where it is set
+	// it wins over RT_HIP_PROGRESSIVE alone and over RT_HIP_TEMPORAL.  A driver that wants to know where the accumulation stands asks the
+	// module (rt_hip_adaptive_last_info), as rt_headless --adaptive does.  A renderer of several GPUs refuses adaptive passes: that is said
+	// once, and its frames are rt_hip_render's.  A negative or unreadable value, or none: off.  (Not for the preview.)
+	float adaptive_threshold()
+	{
+		static const float threshold = []
+		{
+			const char* adaptive = std::getenv("RT_HIP_ADAPTIVE");
+			if (!adaptive || !*adaptive)
+				return -1.0f;
+			char* end = nullptr;
+			const float value = std::strtof(adaptive, &end);
+			if (end == adaptive || *end || !(value >= 0.0f))
+			{
+				std::cerr << "error: hip_ray_tracer: RT_HIP_ADAPTIVE='" << adaptive << "' is not a threshold >= 0: ignored\n";
+				return -1.0f;
+			}
+			return value;
+		}();
+		return threshold;
+	}
+
 	// ModeFlags: 0 = mg_ray_tracer's scatter table; RT_HIP_FLAG_SM_MATERIALS = sm_ray_tracer's (dielectrics refract);
 	// RT_HIP_FLAG_PREVIEW = the one-ray-per-pixel preview of src/renderers/rasterizer.cpp
 	template <uint32_t ModeFlags>
@@ -190,6 +215,7 @@ namespace
 		bool failed_to_create = false;
 		uint64_t frame_number = 0;
 		bool temporal_unsupported = false; // RT_HIP_TEMPORAL on a renderer of several GPUs: refused once, then whole frames as without it
+		bool adaptive_unsupported = false; // RT_HIP_ADAPTIVE on such a renderer: likewise
 
 		~hip_renderer() noexcept override { rt_hip_destroy(ctx); }
 
@@ -243,6 +269,31 @@ namespace
 			const char* fixed = std::getenv("RT_HIP_SEED");
 			const uint64_t seed = fixed ? std::strtoull(fixed, nullptr, 0) : ++frame_number;
 
+			if constexpr (ModeFlags != RT_HIP_FLAG_PREVIEW)
+				if (const float threshold = adaptive_threshold(); threshold >= 0.0f && !adaptive_unsupported)
+				{
+					// (a seed per frame would start the accumulation again on every call: RT_HIP_SEED, or 1, for all of them)
+					const uint32_t pass_samples = progressive_pass_samples() ? progressive_pass_samples() : 16u;
+					rt_hip_adaptive_params params{};
+					if (rt_hip_adaptive_default_params(&params) == RT_HIP_OK)
+					{
+						params.threshold = threshold;
+						const uint64_t two_passes = 2u * ((static_cast<uint64_t>(pass_samples) + 15u) / 16u * 16u);
+						if (params.min_samples < two_passes && two_passes <= 0xFFFFFFFFull)
+							params.min_samples = static_cast<uint32_t>(two_passes);
+					}
+					const rt_hip_status st = rt_hip_render_adaptive(ctx, &s, pixels.data(), pixels.size().x, pixels.size().y, fixed ? seed : 1u, accel_flags() | ModeFlags, pass_samples, &params, nullptr, nullptr, nullptr, nullptr);
+					if (st == RT_HIP_OK)
+						return;
+					if (st != RT_HIP_UNSUPPORTED)
+					{
+						std::cerr << "error: hip_ray_tracer: " << rt_hip_last_error() << "\n";
+						return;
+					}
+					// a multi-GPU or frame-group renderer (or a flag adaptive passes do not take): said once, and from here on every frame is rt_hip_render's (below)
+					std::cerr << "error: hip_ray_tracer: " << rt_hip_last_error() << ": RT_HIP_ADAPTIVE is ignored for this renderer\n";
+					adaptive_unsupported = true;
+				}
 			if constexpr (ModeFlags != RT_HIP_FLAG_PREVIEW)
 				if (temporal_frames())
 				{

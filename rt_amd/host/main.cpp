@@ -24,6 +24,10 @@
 //                           rt_hip_render_temporal): traced whole with a seed of its own and blended with the history kept across camera
 //                           moves; with --denoise the blended frame goes through the a-trous filter too.  Hip renderers only, not with
 //                           --progressive; with --frames N the last frame is the one written
+//   --adaptive THRESHOLD    adaptive sampling (exported to the renderer as RT_HIP_ADAPTIVE=THRESHOLD: rt_hip_render_adaptive): passes of
+//                           16 samples — or of --progressive SAMPLES — over the pixels that have not converged yet; render() is called
+//                           until the accumulation is complete, the last frame is written, and the samples traced are printed against
+//                           pixels x spp.  Hip renderers only; not with --frames, --temporal, --boxes or --denoise
 //   --dolly DX,DY,DZ        the camera moves by that much in world space before every frame after the first (camera::pose)
 //   --shared-frame NAME --rank R --world N   this process is rank R of N rt_headless processes that render ONE frame
 //                together (one per GPU: RT_HIP_DEVICE picks this one's): the back buffer is every process's mapping of the
@@ -32,6 +36,7 @@
 // It renders through renderer_interface::render exactly as window::loop does (src/window.cpp:213-217 via
 // src/main.cpp:315-321): clear to opaque black, then render(scene, pixels, threads).
 #include "renderer.hpp"
+#include "../../include/rt_hip.h" // (rt_hip_adaptive_last_info, rt_hip_live_frame_locks: what --adaptive asks the module itself)
 
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -140,7 +145,7 @@ int main(int argc, char** argv)
 	unsigned width = 800, height = 600, spp = 0, bounces = 0, frames = 1, rank = 0, world = 1, progressive = 0;
 	bool frames_given = false;
 	bool list = false;
-	bool boxes = false, box_bvh = false, denoise = false, temporal = false, dolly = false;
+	bool boxes = false, box_bvh = false, denoise = false, temporal = false, dolly = false, adaptive = false;
 	float dolly_by[3] = { 0.0f, 0.0f, 0.0f };
 	// default renderer: the first whose name starts with "hip", else the first registered (reference: first "mg", :350)
 	for (auto& r : renderers::all())
@@ -216,6 +221,19 @@ int main(int argc, char** argv)
 			temporal = true;
 			::setenv("RT_HIP_TEMPORAL", "1", 1); // (read by the plug-in: every render() is one rt_hip_render_temporal frame)
 		}
+		else if (arg == "--adaptive"sv)
+		{
+			const char* const threshold = value();
+			char* end = nullptr;
+			const float parsed = std::strtof(threshold, &end);
+			if (end == threshold || *end || !(parsed >= 0.0f) || parsed > 3.0e38f)
+			{
+				error("--adaptive expects the threshold (a finite number >= 0)");
+				return 2;
+			}
+			adaptive = true;
+			::setenv("RT_HIP_ADAPTIVE", threshold, 1); // (read by the plug-in: every render() is one rt_hip_render_adaptive pass)
+		}
 		else if (arg == "--dolly"sv)
 		{
 			char trailing = 0;
@@ -234,7 +252,7 @@ int main(int argc, char** argv)
 			world = static_cast<unsigned>(std::strtoul(value(), nullptr, 10));
 		else if (arg == "--help"sv || arg == "-h"sv)
 		{
-			log("usage: rt_headless [--list] [--scene file.toml] [--renderer name] [--size WxH] [--spp N] [--bounces N] [--seed N] [--frames N] [--out file.ppm] [--progressive SAMPLES] [--denoise] [--boxes [--box-bvh]] [--temporal] [--dolly DX,DY,DZ] [--shared-frame NAME --rank R --world N]");
+			log("usage: rt_headless [--list] [--scene file.toml] [--renderer name] [--size WxH] [--spp N] [--bounces N] [--seed N] [--frames N] [--out file.ppm] [--progressive SAMPLES] [--denoise] [--boxes [--box-bvh]] [--temporal] [--adaptive THRESHOLD] [--dolly DX,DY,DZ] [--shared-frame NAME --rank R --world N]");
 			return 0;
 		}
 		else
@@ -260,6 +278,11 @@ int main(int argc, char** argv)
 	if (progressive && (frames_given || std::string_view{ desc->name }.substr(0, 3) != "hip"sv))
 	{
 		error("--progressive sets the number of frames itself (not with --frames) and needs a hip renderer, not '", desc->name, "'");
+		return 2;
+	}
+	if (adaptive && (frames_given || temporal || boxes || denoise || std::string_view{ desc->name }.substr(0, 3) != "hip"sv))
+	{
+		error("--adaptive runs the passes of an adaptive accumulation of a hip renderer until it is complete (not with --frames, --temporal, --boxes or --denoise, not '", desc->name, "')");
 		return 2;
 	}
 	if (boxes && (progressive || std::string_view{ desc->name }.substr(0, 3) != "hip"sv))
@@ -305,6 +328,8 @@ int main(int argc, char** argv)
 		const unsigned pass = (progressive + 15u) / 16u * 16u; // (passes are whole chunks of 16 samples: rt_hip_render_progressive rounds up)
 		frames = (scene.samples_per_pixel + pass - 1u) / pass;
 	}
+	else if (adaptive)
+		frames = (scene.samples_per_pixel + 15u) / 16u; // (at most: the loop below ends with the accumulation)
 
 	image frame;
 	image_view pixels;
@@ -342,6 +367,25 @@ int main(int argc, char** argv)
 		const auto t0 = std::chrono::steady_clock::now();
 		renderer->render(scene, pixels, threads);
 		seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+		if (adaptive)
+		{
+			// where the accumulation stands: the module's own word on the pass render() has just delivered
+			rt_hip_adaptive_info info{};
+			if (rt_hip_adaptive_last_info(&info) != RT_HIP_OK)
+			{
+				error("--adaptive: the renderer did not deliver an adaptive pass (", rt_hip_last_error(), ")");
+				return 1;
+			}
+			const unsigned complete = info.complete, passes = info.passes, count = info.pixels, total = info.samples_total;
+			const unsigned long long traced = info.samples_traced;
+			if (complete)
+			{
+				const double budget = static_cast<double>(count) * total;
+				std::printf("adaptive: complete after %u passes: samples_traced %llu of pixels x spp = %.0f (%.1f %%)\n", passes, traced, budget, budget > 0.0 ? 100.0 * static_cast<double>(traced) / budget : 0.0);
+				std::printf("adaptive: live frame locks %u\n", rt_hip_live_frame_locks()); // (page-locks on this process's frame buffers: none are taken)
+				break;
+			}
+		}
 	}
 	const double rays = static_cast<double>(width) * height * scene.samples_per_pixel;
 	std::printf("%ux%u, %u spp, max_bounces %u: %.3f ms per frame (render() wall clock incl. upload and read-back), %.1f Mrays/s\n",

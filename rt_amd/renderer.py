@@ -19,7 +19,7 @@ import ctypes as C
 import numpy as np
 
 from . import capi
-from .capi import RtHipDenoiseParams, RtHipPartition, RtHipPhases, RtHipProgress, RtHipScene, RtHipStats, RtHipTemporalInfo, RtHipTemporalParams, check
+from .capi import RtHipAdaptiveInfo, RtHipAdaptiveParams, RtHipDenoiseParams, RtHipPartition, RtHipPhases, RtHipProgress, RtHipScene, RtHipStats, RtHipTemporalInfo, RtHipTemporalParams, check
 
 
 def local_rows(height: int, rank: int, world: int, stripe_rows: int = capi.RT_HIP_DEFAULT_STRIPE_ROWS) -> int:
@@ -94,6 +94,13 @@ def temporal_default_params() -> RtHipTemporalParams:
     """rt_hip_temporal_default_params: what a NULL `temporal` stands for (pure host code)."""
     params = RtHipTemporalParams()
     check(capi.hip_lib().rt_hip_temporal_default_params(C.byref(params)))
+    return params
+
+
+def adaptive_default_params() -> RtHipAdaptiveParams:
+    """rt_hip_adaptive_default_params: what a NULL `params` of the adaptive entry points stands for (pure host code)."""
+    params = RtHipAdaptiveParams()
+    check(capi.hip_lib().rt_hip_adaptive_default_params(C.byref(params)))
     return params
 
 
@@ -273,6 +280,34 @@ class HipRayTracer:
         check(self._lib.rt_hip_render_temporal(self._ctx, C.byref(scene), rgba.ctypes.data, width, height, seed, flags, C.byref(temporal) if temporal is not None else None, C.byref(filter) if filter is not None else None,
                                                rgb.ctypes.data if rgb is not None else None, C.byref(stats_pod) if stats else None, C.byref(info)))
         return rgba, rgb, stats_pod.as_dict() if stats else {}, info.as_dict()
+
+    # ---- adaptive sampling -----------------------------------------------------------------
+    def render_adaptive(self, scene: RtHipScene, width: int, height: int, seed: int = 1, flags: int = 0, pass_samples: int = 16, params: RtHipAdaptiveParams | None = None, want_rgb: bool = False, want_counts: bool = True,
+                        out: np.ndarray | None = None, stats: bool = True):
+        """rt_hip_render_adaptive: the next pass of the adaptive accumulation in flight, over the pixels still active — or the first
+        of a new one.  Returns (rgba8 uint32[H, W], rgb float32[H, W, 3] or None, sample map uint32[H, W] or None, stats dict of THIS
+        pass, info dict: samples_done, samples_total, passes, restarted, active_pixels, pixels, samples_traced, complete).  Pixel
+        (x, y) of the frame is the one-shot frame's pixel at samples_per_pixel = map[y, x], bit for bit."""
+        stats_pod, info = RtHipStats(), RtHipAdaptiveInfo()
+        rgba = out if out is not None else np.empty((height, width), dtype=np.uint32)
+        assert rgba.dtype == np.uint32 and rgba.shape == (height, width) and rgba.flags.c_contiguous
+        rgb = np.empty((height, width, 3), dtype=np.float32) if want_rgb else None
+        counts = np.empty((height, width), dtype=np.uint32) if want_counts else None
+        check(self._lib.rt_hip_render_adaptive(self._ctx, C.byref(scene), rgba.ctypes.data, width, height, seed, flags, pass_samples, C.byref(params) if params is not None else None, rgb.ctypes.data if rgb is not None else None,
+                                               counts.ctypes.data if counts is not None else None, C.byref(stats_pod) if stats else None, C.byref(info)))
+        return rgba, rgb, counts, stats_pod.as_dict() if stats else {}, info.as_dict()
+
+    def adaptive_pass_device(self, width: int, height: int, first_sample: int, n_samples: int, d_block: int, d_rgba8: int, seed: int = 1, flags: int = 0, params: RtHipAdaptiveParams | None = None, d_rgb_f32: int | None = None,
+                             d_active_pixels: int | None = None, stream: int | None = None) -> None:
+        """rt_hip_adaptive_pass_device: one adaptive pass on the resident scene — samples [first_sample, first_sample + n_samples) of the
+        active pixels, then the update step.  `d_block`: 9 x width x height words on the device (accum, state, pass_sum, moments)."""
+        check(self._lib.rt_hip_adaptive_pass_device(self._ctx, width, height, seed, flags, first_sample, n_samples, C.byref(params) if params is not None else None, d_block, d_rgba8, d_rgb_f32, d_active_pixels, stream))
+
+    def adaptive_update_device(self, width: int, height: int, pass_samples: int, first_pass: bool, whole_pass: bool, d_accum: int, d_pass_sum: int, d_moments: int, d_state: int, d_rgba8_out: int,
+                               params: RtHipAdaptiveParams | None = None, d_rgb_out: int | None = None, d_active_pixels: int | None = None, stream: int | None = None) -> None:
+        """rt_hip_adaptive_update_device: the update step alone on DEVICE buffers (moments and state in place).  Asynchronous."""
+        check(self._lib.rt_hip_adaptive_update_device(self._ctx, width, height, pass_samples, int(bool(first_pass)), int(bool(whole_pass)), C.byref(params) if params is not None else None, d_accum, d_pass_sum, d_moments, d_state, d_rgba8_out,
+                                                      d_rgb_out, d_active_pixels, stream))
 
     def forget_frame(self) -> None:
         """Drop the page-lock on the back buffer last rendered into with RT_HIP_FLAG_PERSISTENT_FRAME."""
