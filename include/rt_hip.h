@@ -226,8 +226,12 @@ enum
 	 * first such frame after the scene's columns changed (counted in `upload_ms`), kept while they stay the same, and freed
 	 * with the context.  kernel_variant reports RT_HIP_KERNEL_BVH.  Refused (RT_HIP_UNSUPPORTED) with RT_HIP_FLAG_FORCE_TILED,
 	 * _FORCE_RESIDENT, _FORCE_STREAMED and RT_HIP_FLAG_FAST; ignored with RT_HIP_FLAG_PREVIEW (one ray per pixel: nothing to
-	 * gain).  Works with RT_HIP_FLAG_SM_MATERIALS and on every kind of context.  A library older than this flag refuses the
-	 * bit with RT_HIP_UNSUPPORTED (unknown flag bits): that is how a caller finds out whether it is there. */
+	 * gain).  Works with RT_HIP_FLAG_SM_MATERIALS and on every kind of context.  LDS: the kernel's traversal stacks (24 KiB) stand in
+	 * front of the pixels' chunk sums, 65 664 bytes together at 3409 samples and 73 728 at 4096 — a frame, a pass or an adaptive pass is
+	 * launched only if the DEVICE gives one workgroup that much (hipDeviceProp_t::sharedMemPerBlock, read when the context is made), and is
+	 * otherwise refused with RT_HIP_UNSUPPORTED and a message that says how many samples fit (3408 at 64 KiB).  The MI355X gives a
+	 * workgroup 160 KiB and renders these frames: observed (tests/test_gpu_chunk_sweep.py), not derived.  A library older than this flag
+	 * refuses the bit with RT_HIP_UNSUPPORTED (unknown flag bits): that is how a caller finds out whether it is there. */
 	RT_HIP_FLAG_BVH = 1u << 10,
 	/* OPT-IN, modifies RT_HIP_FLAG_BVH: build the hierarchy on the GPU from the resident (c, r^2) table — a Morton-ordered
 	 * binary tree (radix sort, one launch per level, bottom-up boxes) instead of the host's binned SAH — on the frame's stream,
@@ -518,7 +522,8 @@ RT_HIP_API rt_hip_status rt_hip_render(rt_hip_ctx* ctx,
  * names it: passes are built for the parity contract's tile-per-wave kernels only.  kernel_variant is RT_HIP_KERNEL_RESIDENT,
  * or RT_HIP_KERNEL_BVH — with RT_HIP_FLAG_BVH, and for every scene of the streamed kernel's size (above about 1300 primitives)
  * with or without the flag.  samples_per_pixel may be anything up to 2^20 (beyond that the samples' windows alias): rt_hip_render's
- * limit of 4096 applies to ONE PASS, not to the frame; a pass that is too large is refused with RT_HIP_UNSUPPORTED.
+ * limit of 4096 applies to ONE PASS, not to the frame; a pass that is too large is refused with RT_HIP_UNSUPPORTED — so is a pass
+ * through the hierarchy whose stacks and chunk sums the device does not give one workgroup the LDS for (RT_HIP_FLAG_BVH above).
  * What passes cost next to the one-shot frame through the same kernel (per pass: a launch, 12 bytes per pixel read and
  * written, the per-pixel finish): DESIGN.md §3.6 says what has been measured (tools/progressive_bench.py); nothing here
  * promises more than it says.

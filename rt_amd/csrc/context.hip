@@ -82,6 +82,7 @@ extern "C" rt_hip_status rt_hip_create(rt_hip_ctx** out_ctx, int device)
 		return fail(RT_HIP_RUNTIME_ERROR, "rt_hip_create: out of host memory");
 	ctx->device = device;
 	ctx->compute_units = props.multiProcessorCount > 0 ? static_cast<uint32_t>(props.multiProcessorCount) : 256u;
+	ctx->workgroup_lds_bytes = props.sharedMemPerBlock; // (what a launch may ask for: launch_request::lds_limit; 0 = the plan's own default)
 	ctx->numa_node = numa_node_of(device);
 	if (const char* knob = std::getenv("RT_HIP_NUMA_NODE")) // (tests and odd hosts: say which node the back buffer should live on)
 	{

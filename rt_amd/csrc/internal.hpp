@@ -245,6 +245,7 @@ struct rt_hip_ctx
 {
 	int device = 0;
 	uint32_t compute_units = 256;
+	size_t workgroup_lds_bytes = 0; // LDS bytes one workgroup may ask for, as the device's properties say (rt_hip_create); 0 = unknown
 	int numa_node = -1; // host NUMA node the GPU hangs off (sysfs), -1 = unknown
 
 	// the scene, resident in HBM: one buffer holding every column back to back (256-byte aligned starts)

@@ -297,8 +297,23 @@ namespace rt_hip
 				std::snprintf(plan.refusal, sizeof(plan.refusal), "RT_HIP_FLAG_TRACE_BOXES: %u boxes: at most %u are traced (a linear scan from LDS; there is no hierarchy over boxes)", request.n_boxes, box_max_count);
 			else if (plan.table_bytes + plan.slot_bytes > workgroup_lds_bytes)
 				std::snprintf(plan.refusal, sizeof(plan.refusal), "RT_HIP_FLAG_TRACE_BOXES: %zu bytes of tables and %zu of chunk sums do not fit a workgroup's %zu bytes of LDS", plan.table_bytes, plan.slot_bytes, workgroup_lds_bytes);
+			else if (plan.slot_bytes > max_slot_bytes) // (the resident kernel's box builds, whose tables leave room: the one-shot limit, said by the plan —
+													   // max_slot_bytes of four tiles of four pixels, 12 bytes per chunk and pixel)
+				std::snprintf(plan.refusal, sizeof(plan.refusal), "RT_HIP_FLAG_TRACE_BOXES: %u samples per pixel are more than the box builds hold chunk sums for (%u)", request.samples_per_pixel,
+							  static_cast<uint32_t>(max_slot_bytes / (block_threads / 64u * 4u * 3u * sizeof(float)) * sample_chunk));
 		}
 		plan.lds_bytes = plan.table_bytes + plan.slot_bytes;
+		// No plan is launched that the device cannot hold.  (Slots beyond max_slot_bytes are refused by the sample count: render.hip.)  How many
+		// samples do fit: at such a count a tile holds four pixels whatever the count (choose_queue: from 33 chunks on), so the slots grow by
+		// the same bytes per chunk all the way down to the limit.
+		const size_t lds_limit = request.lds_limit ? request.lds_limit : workgroup_lds_bytes;
+		if (!plan.refusal[0] && !big_scene && plan.slot_bytes <= max_slot_bytes && plan.lds_bytes > lds_limit)
+		{
+			const size_t per_chunk = plan.slot_bytes / queue.chunks;
+			const size_t fit = plan.table_bytes < lds_limit ? (lds_limit - plan.table_bytes) / per_chunk * sample_chunk : 0u;
+			std::snprintf(plan.refusal, sizeof(plan.refusal), "%s%u samples%s need%s %zu bytes of LDS (%zu of tables, %zu of chunk sums) and a workgroup of this device has %zu: at most %zu samples fit", pass ? "a pass of " : "",
+						  pass ? request.pass_samples : request.samples_per_pixel, pass ? "" : " per pixel", pass ? "s" : "", plan.lds_bytes, plan.table_bytes, plan.slot_bytes, lds_limit, fit);
+		}
 
 		// what the context remembers of a persistent kernel (launch_cache): one entry per kernel, table and item size
 		plan.persistent_slot = -1;

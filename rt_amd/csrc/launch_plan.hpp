@@ -95,7 +95,8 @@ namespace rt_hip
 	// RT_HIP_FLAG_TRACE_BOXES: the box builds scan the boxes linearly from LDS, two float4s each (the corners), staged behind the scan's own
 	// table — 8 KiB at the most.  (RT_HIP_FLAG_BOX_BVH's frames reach the boxes through a hierarchy instead and know no such cap.)
 	constexpr uint32_t box_max_count = 256;
-	constexpr size_t workgroup_lds_bytes = 64u * 1024u; // what one workgroup may ask for
+	constexpr size_t workgroup_lds_bytes = 64u * 1024u; // what one workgroup may ask for where the device has not been asked (launch_request::lds_limit), and what the box builds are planned within
+	constexpr size_t max_slot_bytes = 48u * 1024u;		// chunk-sum slots of a workgroup's four tiles at the most: 4096 samples (render.hip refuses more by the sample count)
 
 	// which kernel a launch takes (RT_HIP_KERNEL_*)
 	uint32_t choose_kernel(uint32_t n_spheres, uint32_t n_planes, bool planes_tame /* device_scene::planes_tame */, uint32_t flags, uint32_t samples_per_pixel,
@@ -167,6 +168,10 @@ namespace rt_hip
 		// An ADAPTIVE pass (set by the adaptive entry points only, with pass_samples != 0): the pass's adaptive build, whose
 		// waves ballot their tile's state words into ONE 64-bit stop mask — so a tile holds at most adaptive_max_tile_pixels pixels.
 		bool adaptive = false;
+	// LDS bytes a workgroup of the device may ask for (the context reads it off the device's properties); 0: workgroup_lds_bytes.  A plan
+	// of a tile-per-wave kernel whose tables and chunk sums need more is refused, whatever the build: only the hierarchy kernel's — 24 KiB
+	// of stacks in front of the slots — can, from 3409 samples (a frame's, or a pass's) at a limit of 64 KiB.
+	size_t lds_limit = 0;
 	};
 	constexpr uint32_t adaptive_max_tile_pixels = 64;
 
@@ -200,9 +205,9 @@ namespace rt_hip
 		int persistent_slot; // index into launch_cache::persistent, or -1: not a persistent launch
 		int per_cu_cap;		 // persistent launches: workgroups per CU at most
 		uint32_t first_chunk; // a pass: the chunk of every pixel its items start at (queue.chunks is the PASS's chunk count); else 0
-		// a frame with traced boxes that is NOT launched (RT_HIP_UNSUPPORTED with this text): more than box_max_count boxes without a tree, or tables and
-		// chunk sums beyond a workgroup's LDS.  Empty: the plan stands.
-		char refusal[160];
+		// a frame that is NOT launched (RT_HIP_UNSUPPORTED with this text): traced boxes beyond box_max_count without a tree, or tables and chunk sums
+		// beyond a workgroup's LDS (the box builds: workgroup_lds_bytes; every build: launch_request::lds_limit).  Empty: the plan stands.
+		char refusal[192];
 	};
 	launch_plan plan_launch(const launch_request& request);
 }

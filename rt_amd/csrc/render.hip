@@ -88,11 +88,6 @@ rt_hip_status render_device(rt_hip_ctx* ctx, uint32_t width, uint32_t height, ui
 	flags = checked.flags; // (the launch's: without the BVH bits for the preview, without the builder's)
 	if (!ctx->have_scene)
 		return fail(RT_HIP_NO_SCENE, "rt_hip_render_device: no scene uploaded");
-	if (flags & RT_HIP_FLAG_BVH)
-		if (const rt_hip_status st = ensure_bvh(ctx, checked.bvh_device_build, static_cast<hipStream_t>(stream), keep_stats))
-			return st;
-	const device_bvh* bvh = (flags & RT_HIP_FLAG_BVH) ? ctx->bvh_descriptor : nullptr;
-
 	RT_HIP_TRY(hipSetDevice(ctx->device));
 	const hipStream_t s = static_cast<hipStream_t>(stream);
 	// A context serialises its launches: they share the work counters, the tile queue's head and the timing events.  Work
@@ -112,7 +107,6 @@ rt_hip_status render_device(rt_hip_ctx* ctx, uint32_t width, uint32_t height, ui
 	// every decision of the launch is made here, once: the buffers below are prepared from the plan the launch code then follows
 	launch_plan plan{}; // (the preview: nothing to plan)
 	rolling_buffers rolling;
-	rolling.bvh = bvh;
 	if (!(flags & RT_HIP_FLAG_PREVIEW))
 	{
 		launch_request request{};
@@ -123,20 +117,24 @@ rt_hip_status render_device(rt_hip_ctx* ctx, uint32_t width, uint32_t height, ui
 		request.camera = camera_form_of(f);
 		request.flags = flags, request.host_frame = host_frame, request.fast_arithmetic = (flags & RT_HIP_FLAG_FAST) != 0;
 		request.n_boxes = ctx->scene.n_boxes;
+		request.lds_limit = ctx->workgroup_lds_bytes;
 		plan = plan_launch(request);
-		if (plan.refusal[0]) // (traced boxes beyond what the box builds hold: nothing is launched)
+		// the refusals of the plan come before anything is enqueued — the hierarchy's build included
+		if (plan.refusal[0]) // (traced boxes beyond what the box builds hold, or tables and chunk sums beyond a workgroup's LDS on this device: nothing is launched)
 			return fail(RT_HIP_UNSUPPORTED, "rt_hip_render_device: %s", plan.refusal);
 		// small scenes: a pixel's chunk sums (one per 16 samples) are parked in LDS until the pixel is complete
-		if (pass && plan.slot_bytes > 48u * 1024u)
+		if (pass && plan.slot_bytes > max_slot_bytes)
 			return fail(RT_HIP_UNSUPPORTED, "rt_hip_render_pass_device: a pass of %u samples is more than the kernels hold chunk sums for (4096 per pass; the frame's samples_per_pixel has no such limit)", pass->n_samples);
-		if (plan.slot_bytes > 48u * 1024u)
+		if (plan.slot_bytes > max_slot_bytes)
 			return fail(RT_HIP_UNSUPPORTED, "rt_hip_render_device: %u samples per pixel are more than the kernels hold chunk sums for (4096; the reference clamps to 1000, src/scene.cpp:544)", f.samples_per_pixel);
-		if ((pass || plan.build.boxes) && plan.build.scan == scan_bvh && !bvh) // a pass, or a frame with traced boxes, of a scene of the streamed kernel's size goes through the hierarchy (plan_launch), flag or no flag
+		// the hierarchy kernel: under RT_HIP_FLAG_BVH with the builder the call names; a pass, or a frame with traced boxes, of a scene of the streamed
+		// kernel's size, and every frame of RT_HIP_FLAG_BOX_BVH, go through it flag or no flag (plan_launch), on the host's tree
+		if (plan.build.scan == scan_bvh)
 		{
-			if (const rt_hip_status st = ensure_bvh(ctx, false, s, keep_stats))
+			if (const rt_hip_status st = ensure_bvh(ctx, (flags & RT_HIP_FLAG_BVH) ? checked.bvh_device_build : false, s, keep_stats))
 				return st;
 			RT_HIP_TRY(hipSetDevice(ctx->device));
-			rolling.bvh = bvh = ctx->bvh_descriptor;
+			rolling.bvh = ctx->bvh_descriptor;
 		}
 		if (plan.build.box_tree) // RT_HIP_FLAG_BOX_BVH: the box hierarchy's descriptor travels behind (a copy of) the sphere hierarchy's
 		{
