@@ -18,6 +18,14 @@ TRACE_ITERATIVE = 0
 TRACE_RECURSIVE = 1
 MATERIALS_SM = 2
 PREVIEW = 4
+TEST_NO_RARE_RULES = 8  # honoured by render_census alone: no re-draw of a zero vector, no approx_zero replacement (cpu_ref.h)
+
+# the events of the branch census, in the order of cpu_ref.h's ORACLE_CENSUS_* (oracle_render_census fills one count per name)
+CENSUS_EVENTS = [
+    "redraw", "zero_jitter", "lambert_rule", "lambert_near_zero", "lambert_ordinary", "metal_absorbed", "metal_scattered", "dielectric_from_inside", "dielectric_from_outside",
+    "dielectric_total_internal", "dielectric_reflected", "dielectric_refracted", "dielectric_index_one", "out_of_bounces", "plane_parallel", "hit_behind", "hit_below_min_dist",
+    "sphere_from_inside", "sphere_plane_tie", "pack_clamped_above", "pack_negative_or_nan", "pack_non_finite",
+]
 
 
 class OracleStats(C.Structure):
@@ -50,6 +58,10 @@ def lib() -> C.CDLL:
         l = C.CDLL(str(path))
         l.oracle_render.restype = C.c_int
         l.oracle_render.argtypes = [C.POINTER(RtHipScene), C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.POINTER(RtHipPartition), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(OracleStats)]
+        l.oracle_render_census.restype = C.c_int
+        l.oracle_render_census.argtypes = l.oracle_render.argtypes + [C.c_void_p]
+        l.oracle_unit_vector.restype = C.c_uint32
+        l.oracle_unit_vector.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
         l.oracle_render_mt19937.restype = C.c_int
         l.oracle_render_mt19937.argtypes = [C.POINTER(RtHipScene), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(OracleStats)]
         l.oracle_random.restype = None
@@ -116,6 +128,29 @@ def render(scene: RtHipScene, width: int, height: int, seed: int = 1, trace_orde
     if rc != 0:
         raise RuntimeError(f"oracle_render failed ({rc})")
     return rgba, rgb, stats.as_dict()
+
+
+def render_census(scene: RtHipScene, width: int, height: int, seed: int = 1, threads: int = 0, sm_materials: bool = False, rare_rules: bool = True):
+    """oracle_render_census: render()'s frame with the branch census — (rgba, rgb, stats dict, {event name: count} in CENSUS_EVENTS order).
+    rare_rules=False is the test-only mode in which a zero random vector is not re-drawn and lambert's approx_zero replacement is not
+    made: for showing that a constructed case depends on its rule, never for a comparison with the GPU."""
+    rgba = np.zeros((height, width), dtype=np.uint32)
+    rgb = np.zeros((height, width, 3), dtype=np.float32)
+    stats = OracleStats()
+    census = np.zeros(len(CENSUS_EVENTS), dtype=np.uint64)
+    mode = TRACE_ITERATIVE | (MATERIALS_SM if sm_materials else 0) | (0 if rare_rules else TEST_NO_RARE_RULES)
+    rc = lib().oracle_render_census(C.byref(scene), width, height, seed, mode, None, rgba.ctypes.data, rgb.ctypes.data, threads or default_threads(), C.byref(stats), census.ctypes.data)
+    if rc != 0:
+        raise RuntimeError(f"oracle_render_census failed ({rc})")
+    return rgba, rgb, stats.as_dict(), {name: int(count) for name, count in zip(CENSUS_EVENTS, census)}
+
+
+def unit_vector(seed: int, pixel: int, sample: int, step: int):
+    """random_unit_vector() drawn at generator step `step` (1 = the first) of the stream of (pixel, sample): (float32[3], the number of
+    steps it took — 2 or more where the zero vector came up and was drawn again)."""
+    out = np.empty(3, dtype=np.float32)
+    steps = lib().oracle_unit_vector(seed, pixel, sample, step, out.ctypes.data)
+    return out, int(steps)
 
 
 def render_mt19937(scene: RtHipScene, width: int, height: int, fixed_seed: int = 0, want_rgb=False, threads: int = 0):

@@ -132,6 +132,31 @@ namespace
 		}
 	};
 
+	// ---- branch census (test infrastructure of the test infrastructure) -------------------------------------------
+	// Which contract branches a render takes, counted per thread and summed at the end (oracle_render_census).  The
+	// counting reads values the render computes anyway and changes none: a census render's pixels, floats and
+	// segments are oracle_render's bytes (tests/test_rare_branches.py).  `probe` is null outside a census render,
+	// and then nothing below is counted.  The order of the fields is ORACLE_CENSUS_* of cpu_ref.h.
+	struct counters
+	{
+		uint64_t segments = 0;
+		uint64_t census[ORACLE_CENSUS_EVENTS] = {};
+	};
+
+	struct render_probe
+	{
+		counters* count = nullptr; // where this thread's events go
+		bool rare_rules_off = false; // ORACLE_TEST_NO_RARE_RULES: no re-draw of a zero vector, no approx_zero replacement
+	};
+
+	thread_local render_probe probe;
+
+	inline void note(int event)
+	{
+		if (probe.count)
+			probe.count->census[event]++;
+	}
+
 	// ---- random streams -------------------------------------------------------------------------------------
 	// The reference draws from a thread_local std::mt19937 seeded by std::random_device (src/random.cpp:9-26):
 	// not reproducible, and tied to which host thread ran the pixel.  Replaced by counter-based streams in which
@@ -231,8 +256,11 @@ namespace
 			const float x = static_cast<float>(k.a) * 0x1.0p-24f;
 			const float y = static_cast<float>(k.b) * 0x1.0p-24f;
 			const float z = static_cast<float>(k.c) * 0x1.0p-24f;
-			if (x == 0.0f && y == 0.0f && z == 0.0f)
+			if (x == 0.0f && y == 0.0f && z == 0.0f && !probe.rare_rules_off)
+			{
+				note(ORACLE_CENSUS_REDRAW);
 				continue;
+			}
 			return normalize({ x, y, z });
 		}
 	}
@@ -469,8 +497,13 @@ namespace
 			return false;
 		const float f = std::sqrt(disc);
 		t = (e2 < r2) ? a + f : a - f; // origin inside: far root; outside: near root
+		if (e2 < r2)
+			note(ORACLE_CENSUS_SPHERE_FROM_INSIDE);
 		if (t < 0.0f)
+		{
+			note(ORACLE_CENSUS_HIT_BEHIND);
 			return false;
+		}
 		return true;
 	}
 
@@ -479,11 +512,17 @@ namespace
 	{
 		const float den = dot(n, r.dir);
 		if (std::fabs(den) <= approx_zero_epsilon)
+		{
+			note(ORACLE_CENSUS_PLANE_PARALLEL);
 			return false;
+		}
 		const float num = dot(n, r.origin) + d;
 		t = (-num) * (1.0f / den);
 		if (t < 0.0f)
+		{
+			note(ORACLE_CENSUS_HIT_BEHIND);
 			return false;
+		}
 		return true;
 	}
 
@@ -528,6 +567,8 @@ namespace
 		{
 			float t;
 			const bool hit = hits_plane(r, { s.plane_normal_x[i], s.plane_normal_y[i], s.plane_normal_z[i] }, s.plane_d[i], t);
+			if (hit && t < min_hit_dist)
+				note(ORACLE_CENSUS_HIT_BELOW_MIN_DIST);
 			if (!hit || t < min_hit_dist || (have && hit_dist <= t))
 				continue;
 			have = true;
@@ -554,6 +595,8 @@ namespace
 			float t;
 			const bool hit =
 				hits_sphere(r, { s.sphere_center_x[i], s.sphere_center_y[i], s.sphere_center_z[i] }, s.sphere_radius[i], t);
+			if (hit && t < min_hit_dist)
+				note(ORACLE_CENSUS_HIT_BELOW_MIN_DIST);
 			if (!hit || t < min_hit_dist || (have && hit_dist <= t))
 				continue;
 			have = true;
@@ -577,7 +620,10 @@ namespace
 	inline hit_result closest_hit(const rt_hip_scene& s, const ray& r)
 	{
 		hit_result hit = test_planes(s, r);	  // :160
-		hit = select(test_spheres(s, r), hit); // :161  (sphere wins a tie)
+		const hit_result spheres = test_spheres(s, r);
+		if (hit && spheres && hit.distance == spheres.distance)
+			note(ORACLE_CENSUS_SPHERE_PLANE_TIE);
+		hit = select(spheres, hit); // :161  (sphere wins a tie)
 		hit = select(no_hit, hit);			  // :162  test_boxes always misses (:89-93)
 		return hit;
 	}
@@ -596,8 +642,12 @@ namespace
 	inline bool lambert_scatter(const ray& r, const hit_result& hit, random_stream& rng, ray& out)
 	{
 		vec3 scatter = hit.normal + random_unit_vector(rng);
-		if (std::fabs(scatter.x) <= approx_zero_epsilon && std::fabs(scatter.y) <= approx_zero_epsilon
-			&& std::fabs(scatter.z) <= approx_zero_epsilon)
+		const bool rule = std::fabs(scatter.x) <= approx_zero_epsilon && std::fabs(scatter.y) <= approx_zero_epsilon
+			&& std::fabs(scatter.z) <= approx_zero_epsilon;
+		// (the sum of squares under 3.0001e-12 is what the kernels vote on before they evaluate the rule: a vector can
+		// pass the vote and fail the rule — one component beyond 1e-6, the others next to nothing)
+		note(rule ? ORACLE_CENSUS_LAMBERT_RULE : (dot(scatter, scatter) <= 3.0001e-12f ? ORACLE_CENSUS_LAMBERT_NEAR_ZERO : ORACLE_CENSUS_LAMBERT_ORDINARY));
+		if (rule && !probe.rare_rules_off)
 			scatter = hit.normal;
 		out = { r.at(hit.distance), normalize(scatter) };
 		return true;
@@ -614,7 +664,11 @@ namespace
 							   std::fmaf(roughness, u.y, reflected.y),
 							   std::fmaf(roughness, u.z, reflected.z) };
 		if (dot(scatter, hit.normal) <= 0.0f)
+		{
+			note(ORACLE_CENSUS_METAL_ABSORBED);
 			return false;
+		}
+		note(ORACLE_CENSUS_METAL_SCATTERED);
 		out = { r.at(hit.distance), normalize(scatter) };
 		return true;
 	}
@@ -673,6 +727,13 @@ namespace
 		}
 		if (out_reflect_prob)
 			*out_reflect_prob = reflect_prob;
+		if (probe.count) // (never under the leaf oracle_dielectric_direction: no census is open there)
+		{
+			note(dn > 0.0f ? ORACLE_CENSUS_DIELECTRIC_FROM_INSIDE : ORACLE_CENSUS_DIELECTRIC_FROM_OUTSIDE);
+			if (refl == 1.0f)
+				note(ORACLE_CENSUS_DIELECTRIC_INDEX_ONE);
+			note(sin2_t > 1.0f ? ORACLE_CENSUS_DIELECTRIC_TOTAL_INTERNAL : (u < reflect_prob ? ORACLE_CENSUS_DIELECTRIC_REFLECTED : ORACLE_CENSUS_DIELECTRIC_REFRACTED));
+		}
 		return (u < reflect_prob) ? reflected : refracted;
 	}
 
@@ -695,16 +756,14 @@ namespace
 		return lambert_scatter(r, hit, rng, out);
 	}
 
-	struct counters
-	{
-		uint64_t segments = 0;
-	};
-
 	// mg_ray_tracer.cpp:155-174, literal recursion
 	vec3 trace_recursive(const frame& f, const ray& r, uint32_t max_bounces, random_stream& rng, counters& c)
 	{
 		if (!(max_bounces--))
+		{
+			note(ORACLE_CENSUS_OUT_OF_BOUNCES);
 			return { 0, 0, 0 };
+		}
 		c.segments++;
 		const hit_result hit = closest_hit(*f.scene, r);
 		if (!hit)
@@ -727,7 +786,10 @@ namespace
 		while (true)
 		{
 			if (!(max_bounces--))
+			{
+				note(ORACLE_CENSUS_OUT_OF_BOUNCES);
 				return { 0, 0, 0 };
+			}
 			c.segments++;
 			const hit_result hit = closest_hit(*f.scene, r);
 			if (!hit)
@@ -769,6 +831,8 @@ namespace
 				const random_stream::step k = rng.next_step(); // random<vec2>(): one step
 				ka = static_cast<float>(k.a);
 				kb = static_cast<float>(k.b);
+				if (k.a == 0u && k.b == 0u)
+					note(ORACLE_CENSUS_ZERO_JITTER);
 			}
 			const ray r = primary_ray(f, x, y, ka, kb);
 			const vec3 sample = f.trace_order == ORACLE_TRACE_RECURSIVE ? trace_recursive(f, r, s.max_bounces, rng, c)
@@ -782,6 +846,10 @@ namespace
 		}
 		const float n = static_cast<float>(s.samples_per_pixel);
 		colour = { colour.x / n, colour.y / n, colour.z / n }; // :195
+		if (probe.count)
+			for (const float v : { colour.x, colour.y, colour.z })
+				if (!std::isfinite(v))
+					note(ORACLE_CENSUS_PACK_NON_FINITE);
 		if (out_rgb)
 		{
 			out_rgb[0] = colour.x;
@@ -789,6 +857,14 @@ namespace
 			out_rgb[2] = colour.z;
 		}
 		colour = { std::sqrt(colour.x), std::sqrt(colour.y), std::sqrt(colour.z) }; // :196-198
+		if (probe.count)
+			for (const float* v : { &colour.x, &colour.y, &colour.z })
+			{
+				if (*v > 1.0f)
+					note(ORACLE_CENSUS_PACK_CLAMPED_ABOVE);
+				else if (!(*v >= 0.0f))
+					note(ORACLE_CENSUS_PACK_NEGATIVE_OR_NAN);
+			}
 		out_rgba = pack(colour);													 // :200
 	}
 
@@ -857,16 +933,20 @@ namespace
 	}
 }
 
-extern "C" int oracle_render(const rt_hip_scene* scene,
-							 uint32_t width,
-							 uint32_t height,
-							 uint64_t seed,
-							 int mode,
-							 const rt_hip_partition* part,
-							 uint32_t* rgba8,
-							 float* rgb_f32,
-							 int n_threads,
-							 oracle_stats* stats)
+namespace
+{
+	// oracle_render; with `census` (ORACLE_CENSUS_EVENTS words) the same render with the events counted into it
+	int render_frame(const rt_hip_scene* scene,
+					 uint32_t width,
+					 uint32_t height,
+					 uint64_t seed,
+					 int mode,
+					 const rt_hip_partition* part,
+					 uint32_t* rgba8,
+					 float* rgb_f32,
+					 int n_threads,
+					 oracle_stats* stats,
+					 uint64_t* census)
 {
 	if (!scene || !rgba8 || !width || !height || !scene->samples_per_pixel || !scene->max_bounces)
 		return 1;
@@ -891,10 +971,15 @@ extern "C" int oracle_render(const rt_hip_scene* scene,
 
 	std::atomic<size_t> next_row{ 0 };
 	std::atomic<uint64_t> segments{ 0 };
+	std::atomic<uint64_t> events[ORACLE_CENSUS_EVENTS];
+	for (auto& e : events)
+		e = 0;
 	const auto t0 = std::chrono::steady_clock::now();
 	const auto body = [&]()
 	{
 		counters c;
+		if (census)
+			probe = { &c, (mode & ORACLE_TEST_NO_RARE_RULES) != 0 };
 		for (size_t local_y = next_row++; local_y < rows.size(); local_y = next_row++)
 		{
 			const uint32_t y = rows[local_y];
@@ -911,6 +996,12 @@ extern "C" int oracle_render(const rt_hip_scene* scene,
 			}
 		}
 		segments += c.segments;
+		if (census)
+		{
+			for (int e = 0; e < ORACLE_CENSUS_EVENTS; e++)
+				events[e] += c.census[e];
+			probe = {};
+		}
 	};
 	std::vector<std::thread> pool;
 	for (unsigned t = 1; t < threads; t++)
@@ -928,7 +1019,57 @@ extern "C" int oracle_render(const rt_hip_scene* scene,
 		stats->plane_tests = stats->segments * scene->n_planes;
 		stats->seconds = std::chrono::duration<double>(t1 - t0).count();
 	}
+	if (census)
+		for (int e = 0; e < ORACLE_CENSUS_EVENTS; e++)
+			census[e] = events[e].load();
 	return 0;
+}
+}
+
+extern "C" int oracle_render(const rt_hip_scene* scene,
+							 uint32_t width,
+							 uint32_t height,
+							 uint64_t seed,
+							 int mode,
+							 const rt_hip_partition* part,
+							 uint32_t* rgba8,
+							 float* rgb_f32,
+							 int n_threads,
+							 oracle_stats* stats)
+{
+	return render_frame(scene, width, height, seed, mode, part, rgba8, rgb_f32, n_threads, stats, nullptr);
+}
+
+extern "C" int oracle_render_census(const rt_hip_scene* scene,
+									uint32_t width,
+									uint32_t height,
+									uint64_t seed,
+									int mode,
+									const rt_hip_partition* part,
+									uint32_t* rgba8,
+									float* rgb_f32,
+									int n_threads,
+									oracle_stats* stats,
+									uint64_t* census)
+{
+	if (!census)
+		return 1;
+	return render_frame(scene, width, height, seed, mode, part, rgba8, rgb_f32, n_threads, stats, census);
+}
+
+extern "C" uint32_t oracle_unit_vector(uint64_t seed, uint32_t pixel, uint32_t sample, uint32_t step, uint32_t* out_bits)
+{
+	// random_unit_vector() drawn at step `step` (1 = the first) of the stream of (pixel, sample), as bit patterns; returns the
+	// number of generator steps it took (more than 1: the zero vector was drawn and re-drawn)
+	random_stream rng{ make_frame_keys(seed), pixel, sample };
+	for (uint32_t i = 1; i < step; i++)
+		rng.next_step();
+	counters c;
+	probe = { &c, false };
+	const vec3 u = random_unit_vector(rng);
+	probe = {};
+	std::memcpy(out_bits, &u, sizeof(u));
+	return 1u + static_cast<uint32_t>(c.census[ORACLE_CENSUS_REDRAW]);
 }
 
 extern "C" void oracle_random(uint64_t seed, uint32_t pixel, uint32_t sample, uint32_t n, float* out)

@@ -37,7 +37,39 @@ enum
 	ORACLE_TRACE_ITERATIVE = 0, /* the arithmetic contract shared with the GPU (forward throughput product) */
 	ORACLE_TRACE_RECURSIVE = 1, /* literal recursion of mg_ray_tracer.cpp:155-174 (attenuation * trace(...)) */
 	ORACLE_MATERIALS_SM	   = 2, /* scatter table of sm_ray_tracer.cpp:221-236: dielectric/air/vacuum/water/ice refract */
-	ORACLE_PREVIEW		   = 4	/* src/renderers/rasterizer.cpp:24-85 instead of mg_ray_tracer: one ray per pixel (seed unused) */
+	ORACLE_PREVIEW		   = 4,	/* src/renderers/rasterizer.cpp:24-85 instead of mg_ray_tracer: one ray per pixel (seed unused) */
+	/* TEST ONLY, honoured by oracle_render_census alone (oracle_render ignores it): the two rare rules OFF — a zero random vector is
+	 * not re-drawn (it goes on and normalises to NaN) and lambert's approx_zero replacement is not made.  It exists so that a CPU
+	 * test can show a constructed case to be SENSITIVE to its rule; such a frame is never compared with the GPU's. */
+	ORACLE_TEST_NO_RARE_RULES = 8
+};
+
+/* The branch census: events of a render, counted by oracle_render_census in this order (binding.py CENSUS_EVENTS has the names). */
+enum
+{
+	ORACLE_CENSUS_REDRAW = 0,				/* random_unit_vector drew (0, 0, 0) and drew again (random.hpp:61-62) */
+	ORACLE_CENSUS_ZERO_JITTER,				/* a sample > 0 whose pixel jitter is exactly (0, 0) */
+	ORACLE_CENSUS_LAMBERT_RULE,				/* lambert: normal + u is approx_zero, the normal replaces it (mg_ray_tracer.cpp:118-119) */
+	ORACLE_CENSUS_LAMBERT_NEAR_ZERO,		/* lambert: |normal + u|^2 <= 3.0001e-12 (the kernels' vote) but the rule is not met */
+	ORACLE_CENSUS_LAMBERT_ORDINARY,			/* lambert: neither */
+	ORACLE_CENSUS_METAL_ABSORBED,			/* metal: dot(scatter, normal) <= 0 (:135-136) */
+	ORACLE_CENSUS_METAL_SCATTERED,
+	ORACLE_CENSUS_DIELECTRIC_FROM_INSIDE,	/* dielectric (sm table): dot(dir, normal) > 0 */
+	ORACLE_CENSUS_DIELECTRIC_FROM_OUTSIDE,
+	ORACLE_CENSUS_DIELECTRIC_TOTAL_INTERNAL, /* refract() returned false */
+	ORACLE_CENSUS_DIELECTRIC_REFLECTED,		/* refract() returned true and the draw fell below the reflect probability */
+	ORACLE_CENSUS_DIELECTRIC_REFRACTED,
+	ORACLE_CENSUS_DIELECTRIC_INDEX_ONE,		/* a dielectric scatter whose index of refraction is exactly 1 */
+	ORACLE_CENSUS_OUT_OF_BOUNCES,			/* trace() returned {} at :157-158 */
+	ORACLE_CENSUS_PLANE_PARALLEL,			/* a plane missed because |n . dir| <= 1e-6 */
+	ORACLE_CENSUS_HIT_BEHIND,				/* a plane or sphere root rejected for t < 0 */
+	ORACLE_CENSUS_HIT_BELOW_MIN_DIST,		/* a hit rejected for t < min_hit_dist (:20) */
+	ORACLE_CENSUS_SPHERE_FROM_INSIDE,		/* a sphere met from inside (the far root) */
+	ORACLE_CENSUS_SPHERE_PLANE_TIE,			/* the nearest sphere and the nearest plane at equal distance (the sphere wins, :96-102) */
+	ORACLE_CENSUS_PACK_CLAMPED_ABOVE,		/* at pack, per channel: sqrt(mean) > 1 */
+	ORACLE_CENSUS_PACK_NEGATIVE_OR_NAN,		/* at pack, per channel: sqrt(mean) negative or NaN, sent to 0 */
+	ORACLE_CENSUS_PACK_NON_FINITE,			/* at pack, per channel: the mean is infinite or NaN */
+	ORACLE_CENSUS_EVENTS
 };
 
 /* Counter-RNG, strict IEEE render: the parity oracle.  rgba8 / rgb_f32 are local_rows x width (compact
@@ -53,6 +85,20 @@ int oracle_render(const rt_hip_scene* scene,
 				  float* rgb_f32, /* nullable */
 				  int n_threads,
 				  oracle_stats* stats /* nullable */);
+
+/* oracle_render with the branch census: the same frame, floats and stats byte for byte, and census[ORACLE_CENSUS_EVENTS] filled with how
+ * often each event above took place.  The only entry point that honours ORACLE_TEST_NO_RARE_RULES. */
+int oracle_render_census(const rt_hip_scene* scene,
+						 uint32_t width,
+						 uint32_t height,
+						 uint64_t seed,
+						 int mode,
+						 const rt_hip_partition* part,
+						 uint32_t* rgba8,
+						 float* rgb_f32, /* nullable */
+						 int n_threads,
+						 oracle_stats* stats, /* nullable */
+						 uint64_t* census);
 
 /* Reference-faithful COST model of mg_ray_tracer (AoS primitives, recursion, std::optional, function-pointer
  * scatter table, thread_local std::mt19937 + uniform_real_distribution<float>), built with the reference's
@@ -72,6 +118,9 @@ int oracle_render_mt19937(const rt_hip_scene* scene,
 void oracle_random(uint64_t seed, uint32_t pixel, uint32_t sample, uint32_t n, float* out);
 /* state of the random stream of (pixel, sample) before its first draw: the pixel's function key and stride, and the counter */
 void oracle_stream_keys(uint64_t seed, uint32_t n, const uint32_t* pixels, const uint32_t* samples, uint32_t* out_function_key, uint32_t* out_stride, uint32_t* out_counter);
+/* random_unit_vector() (random.hpp:57-66) drawn at generator step `step` (1 = the first) of the stream of (pixel, sample): its three
+ * components as bit patterns.  Returns how many steps it took (2 or more: the zero vector came up and was drawn again). */
+uint32_t oracle_unit_vector(uint64_t seed, uint32_t pixel, uint32_t sample, uint32_t step, uint32_t* out_bits);
 void oracle_closest_hit(const rt_hip_scene* scene,
 						uint32_t n,
 						const float* origins,

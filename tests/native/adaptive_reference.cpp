@@ -23,6 +23,8 @@
 #define oracle_frame_constants adaptive_ref_oracle_frame_constants
 #define oracle_dielectric_direction adaptive_ref_oracle_dielectric_direction
 #define oracle_hits_box adaptive_ref_oracle_hits_box
+#define oracle_render_census adaptive_ref_oracle_render_census
+#define oracle_unit_vector adaptive_ref_oracle_unit_vector
 #include "../../oracle/cpu_ref.cpp"
 
 #include "../../rt_amd/csrc/adaptive_rules.hpp"

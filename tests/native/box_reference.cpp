@@ -44,6 +44,8 @@ namespace
 #define oracle_frame_constants box_ref_oracle_frame_constants
 #define oracle_dielectric_direction box_ref_oracle_dielectric_direction
 #define oracle_hits_box box_ref_oracle_hits_box
+#define oracle_render_census box_ref_oracle_render_census
+#define oracle_unit_vector box_ref_oracle_unit_vector
 #include "../../oracle/cpu_ref.cpp"
 #undef closest_hit
 

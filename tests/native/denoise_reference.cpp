@@ -22,6 +22,8 @@
 #define oracle_frame_constants denoise_ref_oracle_frame_constants
 #define oracle_dielectric_direction denoise_ref_oracle_dielectric_direction
 #define oracle_hits_box denoise_ref_oracle_hits_box
+#define oracle_render_census denoise_ref_oracle_render_census
+#define oracle_unit_vector denoise_ref_oracle_unit_vector
 #include "../../oracle/cpu_ref.cpp"
 
 namespace rt_hip

@@ -23,6 +23,8 @@
 #define oracle_frame_constants reproject_ref_oracle_frame_constants
 #define oracle_dielectric_direction reproject_ref_oracle_dielectric_direction
 #define oracle_hits_box reproject_ref_oracle_hits_box
+#define oracle_render_census reproject_ref_oracle_render_census
+#define oracle_unit_vector reproject_ref_oracle_unit_vector
 #include "../../oracle/cpu_ref.cpp"
 
 namespace rt_hip
