@@ -1,7 +1,11 @@
 """RT_HIP_FLAG_BVH_DEVICE_BUILD on the GPU: the hierarchy built by rt_amd/csrc/bvh_build.hip is, byte for byte, the tree of its
 serial restatement (tests/native/lbvh_reference.cpp, checked on the CPU by tests/test_bvh_lbvh_reference.py); closest hits
 through it are the linear scan's bit for bit; whole frames with the flag equal the frames without it, on every kind of context;
-the cached tree remembers its builder; the plug-in's RT_HIP_ACCEL=bvh-device gives RT_HIP_ACCEL=bvh's frame."""
+the cached tree remembers its builder; the plug-in's RT_HIP_ACCEL=bvh-device gives RT_HIP_ACCEL=bvh's frame.
+
+The scenes here stop at 5000 spheres, two sort tiles and one trip of the scan.  tests/test_gpu_bvh_device_build_scale.py goes on
+from there: every edge of the sort and of the per-sphere kernels up to 262145 spheres, the large sort and the always list over
+several tiles, closest hits and frames through trees of 100000."""
 import os
 import subprocess
 
