@@ -17,17 +17,17 @@ HIPFLAGS += -fvisibility=hidden
 # basic + plane 2.74 -> 2.62, tilted camera 2.80 -> 2.62 (profiles/r05/codegen_ab.txt).
 HIPFLAGS += -fno-slp-vectorize
 API_UNITS := context scene frame render passes multi group denoise temporal adaptive
-HIP_HDR  := rt_amd/csrc/kernels.hpp rt_amd/csrc/launch_plan.hpp rt_amd/csrc/progressive.hpp rt_amd/csrc/denoise.hpp rt_amd/csrc/denoise_rules.hpp rt_amd/csrc/temporal.hpp rt_amd/csrc/reproject_rules.hpp rt_amd/csrc/adaptive.hpp rt_amd/csrc/adaptive_rules.hpp rt_amd/csrc/centre_ray.hpp rt_amd/csrc/frame_setup.hpp rt_amd/csrc/contract.hpp rt_amd/csrc/scan.hpp rt_amd/csrc/bvh_scan.hpp rt_amd/csrc/bvh.hpp rt_amd/csrc/box_bvh.hpp rt_amd/csrc/box_bvh_scan.hpp rt_amd/csrc/bvh_build.hpp rt_amd/csrc/bvh_build_device.hpp rt_amd/csrc/frame_group.hpp rt_amd/csrc/delivery.hpp rt_amd/csrc/internal.hpp include/rt_hip.h
+HIP_HDR  := rt_amd/csrc/kernels.hpp rt_amd/csrc/launch_plan.hpp rt_amd/csrc/progressive.hpp rt_amd/csrc/denoise.hpp rt_amd/csrc/denoise_rules.hpp rt_amd/csrc/temporal.hpp rt_amd/csrc/reproject_rules.hpp rt_amd/csrc/adaptive.hpp rt_amd/csrc/adaptive_rules.hpp rt_amd/csrc/lights.hpp rt_amd/csrc/centre_ray.hpp rt_amd/csrc/frame_setup.hpp rt_amd/csrc/contract.hpp rt_amd/csrc/scan.hpp rt_amd/csrc/bvh_scan.hpp rt_amd/csrc/bvh.hpp rt_amd/csrc/box_bvh.hpp rt_amd/csrc/box_bvh_scan.hpp rt_amd/csrc/bvh_build.hpp rt_amd/csrc/bvh_build_device.hpp rt_amd/csrc/frame_group.hpp rt_amd/csrc/delivery.hpp rt_amd/csrc/internal.hpp include/rt_hip.h
 HOST_SRC := rt_amd/host/host_capi.cpp rt_amd/host/scene.cpp rt_amd/host/toml_subset.cpp
 HOST_HDR := $(wildcard rt_amd/host/*.hpp) rt_amd/host/host_capi.h rt_amd/host/named_colours.inc include/rt_hip.h
 
-all: $(LIBDIR)/librt_hip.so $(LIBDIR)/librt_hip_kat.so $(LIBDIR)/librt_host.so rt_amd/bin/rt_headless tests/native/lbvh_reference tests/native/libbox_reference.so tests/native/libdenoise_reference.so tests/native/libreproject_reference.so tests/native/libadaptive_reference.so oracle
+all: $(LIBDIR)/librt_hip.so $(LIBDIR)/librt_hip_kat.so $(LIBDIR)/librt_host.so rt_amd/bin/rt_headless tests/native/lbvh_reference tests/native/libbox_reference.so tests/native/libdenoise_reference.so tests/native/libreproject_reference.so tests/native/libadaptive_reference.so tests/native/liblight_reference.so oracle
 
 # kernels.hip is compiled twice: the parity contract (contraction off), and RT_HIP_FLAG_FAST's arithmetic
 # (-DRT_HIP_FAST_BUILD -ffp-contract=fast: only launch_render_fast comes out of that one)
 FASTFLAGS := $(filter-out -ffp-contract=off,$(HIPFLAGS)) -ffp-contract=fast -DRT_HIP_FAST_BUILD
 OBJDIR   := build/obj$(NAME)
-HIP_OBJS := $(OBJDIR)/kernels.o $(OBJDIR)/kernels_fast.o $(API_UNITS:%=$(OBJDIR)/%.o) $(OBJDIR)/delivery.o $(OBJDIR)/bvh.o $(OBJDIR)/box_bvh.o $(OBJDIR)/bvh_build.o $(OBJDIR)/launch_plan.o $(OBJDIR)/frame_setup.o $(OBJDIR)/progressive.o $(OBJDIR)/denoise_params.o $(OBJDIR)/temporal_params.o $(OBJDIR)/adaptive_params.o
+HIP_OBJS := $(OBJDIR)/kernels.o $(OBJDIR)/kernels_fast.o $(API_UNITS:%=$(OBJDIR)/%.o) $(OBJDIR)/delivery.o $(OBJDIR)/bvh.o $(OBJDIR)/box_bvh.o $(OBJDIR)/bvh_build.o $(OBJDIR)/launch_plan.o $(OBJDIR)/frame_setup.o $(OBJDIR)/progressive.o $(OBJDIR)/denoise_params.o $(OBJDIR)/temporal_params.o $(OBJDIR)/adaptive_params.o $(OBJDIR)/lights.o
 
 $(OBJDIR)/kernels.o: rt_amd/csrc/kernels.hip $(HIP_HDR)
 	@mkdir -p $(OBJDIR)
@@ -77,6 +77,12 @@ $(OBJDIR)/temporal_params.o: rt_amd/csrc/temporal.cpp rt_amd/csrc/temporal.hpp r
 # adaptive sampling's host-only rules (parameters, the sequencing of an accumulation): plain C++17 too, and the same source is built
 # into tests/native/libadaptive_reference.so and tests/native/adaptive_plan_dump on the CPU
 $(OBJDIR)/adaptive_params.o: rt_amd/csrc/adaptive.cpp rt_amd/csrc/adaptive.hpp rt_amd/csrc/progressive.hpp rt_amd/csrc/launch_plan.hpp include/rt_hip.h
+	@mkdir -p $(OBJDIR)
+	$(CXX) -std=c++17 -O2 -fPIC -fvisibility=hidden -Wall -Wextra $(DEFS) -c $< -o $@
+
+# emissive materials' host-only rules (the emission table's checks, rt_hip_lights_from_spec): plain C++17 too, and the same source is
+# built into tests/native/light_plan_dump and the program of `make sanitize-lights` on the CPU
+$(OBJDIR)/lights.o: rt_amd/csrc/lights.cpp rt_amd/csrc/lights.hpp include/rt_hip.h
 	@mkdir -p $(OBJDIR)
 	$(CXX) -std=c++17 -O2 -fPIC -fvisibility=hidden -Wall -Wextra $(DEFS) -c $< -o $@
 
@@ -171,6 +177,19 @@ sanitize-adaptive: tests/native/adaptive_sanitize.cpp $(ADAPTIVE_REF_SRC)
 	$(CXX) -O1 -g -std=c++17 -ffp-contract=off -fno-fast-math -fno-math-errno -mfma -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer $< tests/native/adaptive_reference.cpp rt_amd/csrc/adaptive.cpp rt_amd/csrc/progressive.cpp -o build/adaptive_sanitize -lpthread
 	build/adaptive_sanitize
 
+# the CPU restatement of RT_HIP_FLAG_EMISSION: the oracle's own translation unit with a trace loop that knows lights (it
+# includes oracle/cpu_ref.cpp and restates nothing else of it), g++ alone, the oracle's strict flags; tests/light_reference.py binds it
+tests/native/liblight_reference.so: tests/native/light_reference.cpp oracle/cpu_ref.cpp oracle/cpu_ref.h include/rt_hip.h
+	$(CXX) -O2 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -fno-math-errno -mfma -Wall -Wextra -shared $< -o $@ -lpthread
+
+# `make sanitize-lights`: rt_hip_lights_from_spec and the emission table's checks behind a main() of their own — every well-formed and
+# malformed shape of tests/test_light_spec.py, truncated and oversized specs — under AddressSanitizer and UndefinedBehaviorSanitizer.
+# CPU only, nothing is loaded into python; the binary goes to build/ and is run at once
+sanitize-lights: tests/native/light_spec_sanitize.cpp rt_amd/csrc/lights.cpp rt_amd/csrc/lights.hpp include/rt_hip.h
+	@mkdir -p build
+	$(CXX) -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer $< rt_amd/csrc/lights.cpp -o build/light_spec_sanitize
+	build/light_spec_sanitize
+
 oracle:
 	$(MAKE) -C oracle
 
@@ -186,7 +205,7 @@ oracle/_ref/soagen_columns: tests/native/soagen_columns.cpp $(LIBDIR)/librt_hip.
 endif
 
 clean:
-	rm -f $(LIBDIR)/*.so rt_amd/bin/rt_headless tests/native/lbvh_reference tests/native/libbox_reference.so tests/native/libdenoise_reference.so tests/native/libreproject_reference.so tests/native/libadaptive_reference.so
+	rm -f $(LIBDIR)/*.so rt_amd/bin/rt_headless tests/native/lbvh_reference tests/native/libbox_reference.so tests/native/libdenoise_reference.so tests/native/libreproject_reference.so tests/native/libadaptive_reference.so tests/native/liblight_reference.so
 	$(MAKE) -C oracle clean
 
-.PHONY: all oracle clean variant sanitize-temporal sanitize-box-bvh sanitize-adaptive
+.PHONY: all oracle clean variant sanitize-temporal sanitize-box-bvh sanitize-adaptive sanitize-lights

@@ -279,7 +279,31 @@ enum
 	 * rt_hip_render_temporal, rt_hip_denoise_progressive and rt_hip_guide_device, whose guide kernel keeps its linear scan.  Nothing
 	 * is promised about speed (DESIGN.md §3.10 has the measured table).  A library older than this flag refuses the bit (unknown
 	 * flag bits). */
-	RT_HIP_FLAG_BOX_BVH = 1u << 14
+	RT_HIP_FLAG_BOX_BVH = 1u << 14,
+	/* (bit 15 stays unassigned, like bit 12: the tests pin 1u << 15 as "unknown flag bits") */
+	/* OPT-IN: EMISSIVE MATERIALS — lights.  The reference has no emitters: all its light is the sky gradient.  With this flag a
+	 * material whose row of the context's emission table (rt_hip_set_emission: r, g, b per material of the resident scene) has a
+	 * component above 0 IS A LIGHT, and a path whose accepted closest hit has such a material ends there with
+	 * throughput * emission (component-wise, throughput on the left, as throughput * sky): no random draw, no scatter.  The bounce
+	 * check comes first as ever — a path with no bounce left is worth 0 before it can reach a light — and the query, its acceptance
+	 * rule and its ties are unchanged.  A light ignores its material's type, albedo, roughness and reflectivity under both scatter
+	 * tables and is not sided (a sphere from inside, a plane from behind emit the same).  Everything behind the sample is the
+	 * contract's: chunk fold, mean, sqrt, pack — a mean above 1 stays in rgb_f32 and the packed byte clamps.  rt_hip_stats is
+	 * unchanged; a segment that ends on a light is counted like any other.  The PROMISE: the frame, the float mean and `segments`
+	 * are bit for bit those of the CPU restatement (tests/native/light_reference.cpp); WITHOUT the flag nothing
+	 * changes, and with the flag and a table in which no material is a light the frame is the flag-less one in every respect
+	 * (plan, kernel, kernel_variant, frame, counters).  A frame with at least one light takes a light build of the resident kernel
+	 * (RT_HIP_KERNEL_RESIDENT; scenes of the scalar-register kernel's size too) or, with RT_HIP_FLAG_BVH and for scenes of the
+	 * streamed kernel's size, of the hierarchy kernel (RT_HIP_KERNEL_BVH).  Nothing is promised about speed.
+	 * Works with RT_HIP_FLAG_SM_MATERIALS, RT_HIP_FLAG_BVH, RT_HIP_FLAG_BVH_DEVICE_BUILD, RT_HIP_FLAG_STATS,
+	 * RT_HIP_FLAG_PERSISTENT_FRAME and RT_HIP_FLAG_FORCE_WHOLE_CHUNKS, in rt_hip_render and rt_hip_render_device, with a partition
+	 * and on every kind of context; ignored with RT_HIP_FLAG_PREVIEW.  Refused with RT_HIP_INVALID_ARGUMENT when no table is set
+	 * or its row count is not the resident scene's n_materials.  Refused (RT_HIP_UNSUPPORTED, the message names the flag) with
+	 * RT_HIP_FLAG_FAST, RT_HIP_FLAG_FORCE_TILED, _FORCE_RESIDENT, _FORCE_STREAMED, RT_HIP_FLAG_FORCE_HALF_CHUNKS,
+	 * RT_HIP_FLAG_TRACE_BOXES and RT_HIP_FLAG_BOX_BVH, and by both progressive entry points, both adaptive entry points,
+	 * rt_hip_render_temporal, rt_hip_denoise_progressive and rt_hip_guide_device.  A library older than this flag refuses the bit
+	 * (unknown flag bits): that is how a caller finds out whether it is there. */
+	RT_HIP_FLAG_EMISSION = 1u << 16
 };
 
 typedef struct rt_hip_ctx rt_hip_ctx;
@@ -867,6 +891,29 @@ RT_HIP_API rt_hip_status rt_hip_render_adaptive(rt_hip_ctx* ctx,
  * --adaptive).  RT_HIP_INVALID_ARGUMENT before the first such call.  Pure host code, safe to call from any thread.
  */
 RT_HIP_API rt_hip_status rt_hip_adaptive_last_info(rt_hip_adaptive_info* out_info);
+
+/* ---- emissive materials (RT_HIP_FLAG_EMISSION): additions to ABI 6 — rt_hip_scene keeps its size ---------------- */
+
+/*
+ * The context's EMISSION TABLE: one row of 3 floats (r, g, b) per material of the resident scene, copied inside the call.  Every
+ * component must be finite and >= 0: a NaN, a negative value or an infinity is RT_HIP_INVALID_ARGUMENT, the message naming the
+ * material's index and the component; -0.0f passes and counts as zero.  A material IS A LIGHT iff r > 0 || g > 0 || b > 0.
+ * NULL / 0 clears the table.  The table is state of the context: it survives scene uploads (a frame with the flag checks its row
+ * count against the resident scene's n_materials), and on a context from rt_hip_create_multi it reaches every member device.
+ * Without RT_HIP_FLAG_EMISSION no frame reads it.
+ */
+RT_HIP_API rt_hip_status rt_hip_set_emission(rt_hip_ctx* ctx, const float* emission_rgb, uint32_t n_materials);
+
+/*
+ * An emission table from a text: how a host whose materials have no emission column (rt::materials, src/soa.toml:6-12) reaches the
+ * feature.  Host-only; touches no device.  `spec` is a list of items KEY=R,G,B separated by ';' (KEY=V is the grey light V,V,V;
+ * blanks around keys, numbers and separators are ignored).  An all-digit KEY is a material index; any other KEY is a material name
+ * and sets EVERY material of that name (`material_names`: n_materials strings, may be NULL when only indices are used).  An empty
+ * spec gives an all-zero table.  RT_HIP_INVALID_ARGUMENT, with a message that quotes the item: an unknown name, an index out of
+ * range, a missing '=', an empty item (a trailing ';'), two or more than three numbers, anything that is not a number, and a value
+ * that is negative, NaN or infinite.  out_emission_rgb receives 3 * n_materials floats (untouched on failure).
+ */
+RT_HIP_API rt_hip_status rt_hip_lights_from_spec(const char* spec, const char* const* material_names, uint32_t n_materials, float* out_emission_rgb);
 
 /* Drop the page-lock taken under RT_HIP_FLAG_PERSISTENT_FRAME (see there).  Waits for the context's stream first. */
 RT_HIP_API void rt_hip_forget_frame(rt_hip_ctx* ctx);

@@ -32,6 +32,7 @@ RT_HIP_FLAG_BVH = 1 << 10  # spheres through a bounding volume hierarchy: same f
 RT_HIP_FLAG_BVH_DEVICE_BUILD = 1 << 11  # with RT_HIP_FLAG_BVH: the hierarchy is built on the GPU (rt_amd/csrc/bvh_build.hip), same frame
 RT_HIP_FLAG_TRACE_BOXES = 1 << 13  # the traced frame hits the scene's boxes too; bit 12 is unassigned
 RT_HIP_FLAG_BOX_BVH = 1 << 14  # with RT_HIP_FLAG_TRACE_BOXES: the boxes through a hierarchy of their own, no 256-box cap, same frame
+RT_HIP_FLAG_EMISSION = 1 << 16  # materials with a row > 0 in the context's emission table are lights; bit 15 is unassigned
 RT_HIP_MULTI_PEER_COPY = 1 << 0
 RT_HIP_MULTI_DIRECT_FRAME = 1 << 1
 RT_HIP_TRANSPORT_NONE, RT_HIP_TRANSPORT_RCCL_GATHER, RT_HIP_TRANSPORT_PEER_COPY, RT_HIP_TRANSPORT_DIRECT_FRAME = 0, 1, 2, 3
@@ -269,6 +270,8 @@ RT_HIP_SYMBOLS = [
         [C.c_void_p, C.POINTER(RtHipScene), C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(RtHipAdaptiveParams), C.c_void_p, C.c_void_p, C.POINTER(RtHipStats), C.POINTER(RtHipAdaptiveInfo)],
     ),
     ("rt_hip_adaptive_last_info", C.c_int, [C.POINTER(RtHipAdaptiveInfo)]),
+    ("rt_hip_set_emission", C.c_int, [C.c_void_p, c_float_p, C.c_uint32]),
+    ("rt_hip_lights_from_spec", C.c_int, [C.c_char_p, C.POINTER(C.c_char_p), C.c_uint32, c_float_p]),
     ("rt_hip_forget_frame", None, [C.c_void_p]),
     ("rt_hip_live_frame_locks", C.c_uint32, []),
 ]

@@ -417,6 +417,44 @@ extern "C" rt_hip_status rt_hip_member_device(const rt_hip_ctx* ctx, int rank, i
 	return ok();
 }
 
+// RT_HIP_FLAG_EMISSION's table (rt_hip.h): context state, copied here, on every member of a multi-GPU context.  The
+// light variant of the per-primitive tables is derived from it by the next frame with the flag (scene.hip, ensure_light_tables).
+extern "C" rt_hip_status rt_hip_set_emission(rt_hip_ctx* ctx, const float* emission_rgb, uint32_t n_materials)
+{
+	if (!ctx)
+		return fail(RT_HIP_INVALID_ARGUMENT, "rt_hip_set_emission: NULL context");
+	if ((emission_rgb == nullptr) != (n_materials == 0u))
+		return fail(RT_HIP_INVALID_ARGUMENT, "rt_hip_set_emission: a table and its row count go together (NULL and 0 clear the table)");
+	if (n_materials)
+	{
+		const light_check values = check_emission_values(emission_rgb, n_materials);
+		if (values.status)
+			return fail(values.status, "%s", values.message);
+	}
+	try // (the copies allocate: nothing may propagate through the C boundary)
+	{
+		std::vector<rt_hip_ctx*> members(1, ctx);
+		members.insert(members.end(), ctx->peers.begin(), ctx->peers.end());
+		std::vector<std::vector<float>> copies(members.size());
+		for (std::vector<float>& copy : copies) // every copy made before any member changes: all of them, or none
+			copy.assign(emission_rgb, emission_rgb + static_cast<size_t>(n_materials) * 3u);
+		const uint32_t lights = n_materials ? count_lights(emission_rgb, n_materials) : 0u;
+		for (size_t m = 0; m < members.size(); m++)
+		{
+			members[m]->emission.swap(copies[m]);
+			members[m]->have_emission = n_materials != 0u;
+			members[m]->emission_rows = n_materials;
+			members[m]->emission_lights = lights;
+			members[m]->emission_version++; // (the light tables are stale from here on, whatever the scene's fingerprint)
+		}
+		return ok();
+	}
+	catch (...)
+	{
+		return fail(RT_HIP_RUNTIME_ERROR, "rt_hip_set_emission: out of host memory");
+	}
+}
+
 extern "C" void rt_hip_destroy(rt_hip_ctx* ctx)
 {
 	if (!ctx)
@@ -438,6 +476,7 @@ extern "C" void rt_hip_destroy(rt_hip_ctx* ctx)
 	ctx->bvh_block.release();
 	ctx->bvh_scratch.release();
 	ctx->box_bvh_block.release();
+	ctx->light_tables.release();
 	ctx->scene_staging.release();
 	ctx->item_sums.release();
 	ctx->pixel_done.release();

@@ -31,6 +31,7 @@
 #include "kernels.hpp"
 #include "progressive.hpp"
 #include "adaptive.hpp"
+#include "lights.hpp"
 
 #include <rccl/rccl.h>
 
@@ -237,7 +238,7 @@ namespace rt_hip
 	struct frame_delivery; // below: the module-owned frame and the threads that carry it to the caller's buffer
 
 	// (RT_HIP_FLAG_PERSISTENT_FRAME and RT_HIP_FLAG_STATS are rt_hip_render's own: they do not travel to the launch)
-	constexpr uint32_t render_flag_mask = RT_HIP_FLAG_FORCE_TILED | RT_HIP_FLAG_FORCE_RESIDENT | RT_HIP_FLAG_SM_MATERIALS | RT_HIP_FLAG_PREVIEW | RT_HIP_FLAG_FORCE_STREAMED | RT_HIP_FLAG_FAST | RT_HIP_FLAG_FORCE_HALF_CHUNKS | RT_HIP_FLAG_FORCE_WHOLE_CHUNKS | RT_HIP_FLAG_BVH | RT_HIP_FLAG_BVH_DEVICE_BUILD | RT_HIP_FLAG_TRACE_BOXES | RT_HIP_FLAG_BOX_BVH;
+	constexpr uint32_t render_flag_mask = RT_HIP_FLAG_FORCE_TILED | RT_HIP_FLAG_FORCE_RESIDENT | RT_HIP_FLAG_SM_MATERIALS | RT_HIP_FLAG_PREVIEW | RT_HIP_FLAG_FORCE_STREAMED | RT_HIP_FLAG_FAST | RT_HIP_FLAG_FORCE_HALF_CHUNKS | RT_HIP_FLAG_FORCE_WHOLE_CHUNKS | RT_HIP_FLAG_BVH | RT_HIP_FLAG_BVH_DEVICE_BUILD | RT_HIP_FLAG_TRACE_BOXES | RT_HIP_FLAG_BOX_BVH | RT_HIP_FLAG_EMISSION;
 
 }
 
@@ -314,6 +315,21 @@ struct rt_hip_ctx
 	uint64_t box_bvh_sphere_stamp = 0;	 // which sphere hierarchy the copied descriptor describes (0 = none): 2 * bvh_built_for + bvh_device_built
 	uint64_t box_bvh_builds = 0;		 // host builds so far (the known-answer library reads it: tests/test_gpu_box_bvh.py)
 	size_t scene_bytes = 0;				 // size of the resident block
+	// RT_HIP_FLAG_EMISSION: the emission table (rt_hip_set_emission: context state, survives scene uploads) and the
+	// LIGHT variant of the four per-primitive shading / scatter tables derived from it and the resident scene (scene.hip,
+	// ensure_light_tables): a light's primitives carry (emission.rgb, 0) and scatter_emit, every other row is the ordinary table's.
+	// Built when a frame with the flag finds them missing or stale — after a scene upload, after rt_hip_set_emission — and handed to
+	// the light builds in a COPY of `scene` whose four pointers point here (render.hip): no kernel argument is added or moved.
+	std::vector<float> emission;		 // 3 floats per row
+	bool have_emission = false;
+	uint32_t emission_rows = 0, emission_lights = 0; // rows of the table, and how many of them are lights
+	uint64_t emission_version = 0;		 // rt_hip_set_emission calls so far
+	rt_hip::device_buffer light_tables;	 // shading, scatter, shading_sm, scatter_sm (256-byte aligned starts)
+	uint64_t light_tables_uploads = 0, light_tables_version = 0; // the scene_uploads and emission_version they were built for (0 = none)
+	const float4* light_shading = nullptr;
+	const uint32_t* light_scatter = nullptr;
+	const float4* light_shading_sm = nullptr;
+	const uint32_t* light_scatter_sm = nullptr;
 	// Opt-in (RT_HIP_FLAG_PERSISTENT_FRAME, frame groups): the CALLER's buffer, page-locked and mapped into the GPU's address
 	// space while it keeps arriving at the same address: the kernel renders straight into it.  The caller then owes the
 	// module rt_hip_forget_frame before that memory is unmapped (rt_hip.h).
@@ -380,6 +396,9 @@ namespace rt_hip
 	// the first such frame after the box columns' fingerprint changed, its time added to upload_ms — behind a copy of the CURRENT
 	// sphere hierarchy's descriptor (ensure_bvh has run), refreshed on `stream` whenever that hierarchy was rebuilt
 	rt_hip_status ensure_box_bvh(rt_hip_ctx* ctx, hipStream_t stream);
+	// RT_HIP_FLAG_EMISSION: make ctx->light_* the light variant of the resident scene's per-primitive tables under the context's emission
+	// table (whose row count the caller has checked against the scene's materials); rebuilt only when the scene or the table is new
+	rt_hip_status ensure_light_tables(rt_hip_ctx* ctx);
 
 	// ---- render.hip ----
 	// whole_frame_buffers: d_rgba8 / d_rgb_f32 are the whole width x height frame and every pixel goes to its image row

@@ -463,6 +463,11 @@ namespace rt_hip
 		// reached through a hierarchy of their own (box_bvh_scan.hpp), walked per lane on the stack the sphere traversal has finished with; its
 		// descriptor lies behind the sphere hierarchy's, where item_sums points, so no argument is added.  A lane the traversal does not take
 		// (a zero or non-finite component) scans s.box_bounds in memory; the winning box's corners are read there too.
+		// LIGHTS (RT_HIP_FLAG_EMISSION; the same two kernels, whole chunks only): scan_resident_lights, scan_bvh_lights.  The launch
+		// hands these builds a device_scene whose per-primitive shading / scatter pointers are the LIGHT variant of the tables (scene.hip,
+		// ensure_light_tables): a hit whose scatter row says scatter_emit ends its sample with throughput * the row's shading.rgb — to the fused
+		// tail such a lane is what a lane that ended on the sky is: it draws nothing for the old sample and its stream stands where next_sample
+		// puts it.  No argument is added or moved; every other instantiation keeps its symbol and its instructions.
 		template <int SCAN, bool SM, bool HALF = false, int NP = 0, bool GC = false>
 		__global__ __launch_bounds__(block_threads, waves_per_simd(scan_of(SCAN), NP)) void render_queue(const frame_params p,
 																	  const queue_params q,
@@ -482,7 +487,9 @@ namespace rt_hip
 			constexpr bool BOXES = scan_has_boxes(SCAN);
 			constexpr bool BOXTREE = scan_has_box_tree(SCAN);
 			static_assert(!PASS || !HALF, "passes are built for whole chunks only");
+			constexpr bool LIGHTS = scan_has_lights(SCAN);
 			static_assert(!BOXES || !HALF, "the box builds are built for whole chunks only");
+			static_assert(!LIGHTS || (!HALF && scan_of(SCAN) <= 0), "the light builds are built for whole chunks of the tile-per-wave table kernels only");
 			extern __shared__ float4 lds[];
 			// [NS > 0] 8 geometry (with the scatter function) + 8 shading float4s | [NS == scan_resident] all primitives; then the chunk slots
 			float4* const lds_geometry = lds;
@@ -1128,6 +1135,11 @@ namespace rt_hip
 						RT_HIP_REGION(4); // miss: sky, end of sample
 						end_sample(st.throughput * sky(st.dir.y)); // miss (:163-164)
 					}
+					else if (LIGHTS && scatter_kind == scatter_emit)
+					{
+						// the accepted hit's material is a light: the sample is throughput * emission and the path ends — no draw, no scatter (§3.12)
+						end_sample(st.throughput * vec3{ shading.x, shading.y, shading.z });
+					}
 					else
 					{
 						shade = true;
@@ -1755,6 +1767,14 @@ namespace rt_hip
 						}
 					constexpr int box_scan = NS == scan_bvh ? scan_bvh_boxes : scan_resident_boxes;
 					hipLaunchKernelGGL((render_queue<box_scan, SM, false, NP, GC>), grid, dim3(block_threads), plan.lds_bytes, a.stream, a.frame, plan.queue, a.small, a.scene, a.scene.primitive_geometry, a.d_rgba8, a.d_rgb_f32, a.d_counters, item_sums,
+									   a.rolling.pixel_done);
+					return;
+				}
+				if (plan.build.lights) // (RT_HIP_FLAG_EMISSION with at least one light: whole chunks, never a pass, never with boxes — the plan's and the API's rules;
+									   // a.scene is the copy whose per-primitive shading / scatter pointers are the light variant's, render.hip)
+				{
+					constexpr int light_scan = NS == scan_bvh ? scan_bvh_lights : scan_resident_lights;
+					hipLaunchKernelGGL((render_queue<light_scan, SM, false, NP, GC>), grid, dim3(block_threads), plan.lds_bytes, a.stream, a.frame, plan.queue, a.small, a.scene, a.scene.primitive_geometry, a.d_rgba8, a.d_rgb_f32, a.d_counters, item_sums,
 									   a.rolling.pixel_done);
 					return;
 				}

@@ -68,7 +68,9 @@ namespace rt_hip
 	{
 		scatter_lambert = 0,	// mg_ray_tracer.cpp:110-123
 		scatter_metal = 1,		// mg_ray_tracer.cpp:126-140
-		scatter_dielectric = 2	// sm_ray_tracer.cpp:181-219 (opt-in)
+		scatter_dielectric = 2,	// sm_ray_tracer.cpp:181-219 (opt-in)
+		scatter_emit = 3		// a light (RT_HIP_FLAG_EMISSION): no scatter at all — the row's shading.rgb is the emission and the path ends; only
+								// the light variant of the per-primitive tables holds it, and only the light builds read that
 	};
 
 	// the whole scene of the `small` kernel, passed by value as a kernel argument (-> SGPRs); host copy kept by the context

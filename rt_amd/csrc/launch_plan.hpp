@@ -124,17 +124,22 @@ namespace rt_hip
 		// the ADAPTIVE builds of the two pass builds (kernel_build::adaptive): a pass that reads the pixels' state words,
 		// traces and folds the active pixels only, stores the pass's own fold next to the running sum and finishes no pixel
 		scan_resident_adapt = -10,
-		scan_bvh_adapt = -11
+		scan_bvh_adapt = -11,
+		// the LIGHT builds of the same two scans (kernel_build::lights; RT_HIP_FLAG_EMISSION with at least one light): a hit
+		// whose scatter row says scatter_emit ends the sample with throughput * the row's shading.rgb — the same scan, whole chunks only
+		scan_resident_lights = -12,
+		scan_bvh_lights = -13
 	};
+	constexpr bool scan_has_lights(int code) { return code == scan_resident_lights || code == scan_bvh_lights; }
 	constexpr bool scan_is_adaptive(int code) { return code == scan_resident_adapt || code == scan_bvh_adapt; }
 	constexpr bool scan_is_pass(int code) { return code == scan_resident_pass || code == scan_bvh_pass || scan_is_adaptive(code); }
 	constexpr bool scan_has_boxes(int code) { return code == scan_resident_boxes || code == scan_bvh_boxes || code == scan_bvh_boxtree; }
 	constexpr bool scan_has_box_tree(int code) { return code == scan_bvh_boxtree; }
 	constexpr int scan_of(int code) // the scan a build's code stands for
 	{
-		return (code == scan_resident_pass || code == scan_resident_boxes || code == scan_resident_adapt)
+		return (code == scan_resident_pass || code == scan_resident_boxes || code == scan_resident_adapt || code == scan_resident_lights)
 				   ? static_cast<int>(scan_resident)
-				   : ((code == scan_bvh_pass || code == scan_bvh_boxes || code == scan_bvh_boxtree || code == scan_bvh_adapt) ? static_cast<int>(scan_bvh) : code);
+				   : ((code == scan_bvh_pass || code == scan_bvh_boxes || code == scan_bvh_boxtree || code == scan_bvh_adapt || code == scan_bvh_lights) ? static_cast<int>(scan_bvh) : code);
 	}
 	// the rolling kernels are launched persistent: as many workgroups as the device keeps resident (launch_cache, kernels.hpp)
 	constexpr bool scan_is_persistent(int scan) { return scan == scan_tiled || scan == scan_streamed || scan == scan_streamed_dense; }
@@ -168,6 +173,10 @@ namespace rt_hip
 		// An ADAPTIVE pass (set by the adaptive entry points only, with pass_samples != 0): the pass's adaptive build, whose
 		// waves ballot their tile's state words into ONE 64-bit stop mask — so a tile holds at most adaptive_max_tile_pixels pixels.
 		bool adaptive = false;
+		// RT_HIP_FLAG_EMISSION: how many materials of the context's emission table are lights.  Without the flag, or with none (the
+		// default: "no lights"), a frame is planned as it always was, field for field; with at least one it is planned like a box frame,
+		// onto the light builds of the two tile-per-wave kernels.
+		uint32_t n_lights = 0;
 	// LDS bytes a workgroup of the device may ask for (the context reads it off the device's properties); 0: workgroup_lds_bytes.  A plan
 	// of a tile-per-wave kernel whose tables and chunk sums need more is refused, whatever the build: only the hierarchy kernel's — 24 KiB
 	// of stacks in front of the slots — can, from 3409 samples (a frame's, or a pass's) at a limit of 64 KiB.
@@ -187,6 +196,7 @@ namespace rt_hip
 		bool boxes;			  // RT_HIP_FLAG_TRACE_BOXES with at least one box: the scan's BOX build (scan_resident_boxes / scan_bvh_boxes)
 		bool box_tree;		  // ... and RT_HIP_FLAG_BOX_BVH: the hierarchy kernel's scan_bvh_boxtree build (`boxes` is set too)
 		bool adaptive;		  // an adaptive pass: the scan's ADAPT build (scan_resident_adapt / scan_bvh_adapt; implies `pass`)
+		bool lights;		  // RT_HIP_FLAG_EMISSION with at least one light: the scan's LIGHT build (scan_resident_lights / scan_bvh_lights)
 	};
 
 	struct launch_plan

@@ -88,6 +88,13 @@ rt_hip_status render_device(rt_hip_ctx* ctx, uint32_t width, uint32_t height, ui
 	flags = checked.flags; // (the launch's: without the BVH bits for the preview, without the builder's)
 	if (!ctx->have_scene)
 		return fail(RT_HIP_NO_SCENE, "rt_hip_render_device: no scene uploaded");
+	// RT_HIP_FLAG_EMISSION: the frame is checked against the context's table before anything is enqueued (the preview has dropped the flag)
+	if (flags & RT_HIP_FLAG_EMISSION)
+	{
+		const light_check table = check_emission_table("rt_hip_render_device", ctx->have_emission, ctx->emission_rows, ctx->scene.n_materials);
+		if (table.status)
+			return fail(table.status, "%s", table.message);
+	}
 	RT_HIP_TRY(hipSetDevice(ctx->device));
 	const hipStream_t s = static_cast<hipStream_t>(stream);
 	// A context serialises its launches: they share the work counters, the tile queue's head and the timing events.  Work
@@ -117,6 +124,7 @@ rt_hip_status render_device(rt_hip_ctx* ctx, uint32_t width, uint32_t height, ui
 		request.camera = camera_form_of(f);
 		request.flags = flags, request.host_frame = host_frame, request.fast_arithmetic = (flags & RT_HIP_FLAG_FAST) != 0;
 		request.n_boxes = ctx->scene.n_boxes;
+		request.n_lights = (flags & RT_HIP_FLAG_EMISSION) ? ctx->emission_lights : 0u;
 		request.lds_limit = ctx->workgroup_lds_bytes;
 		plan = plan_launch(request);
 		// the refusals of the plan come before anything is enqueued — the hierarchy's build included
@@ -144,6 +152,12 @@ rt_hip_status render_device(rt_hip_ctx* ctx, uint32_t width, uint32_t height, ui
 		}
 		if (pass)
 			rolling.accum = pass->d_accum;
+		if (plan.build.lights) // RT_HIP_FLAG_EMISSION with at least one light: the light variant of the per-primitive tables, built if missing or stale
+		{
+			if (const rt_hip_status st = ensure_light_tables(ctx))
+				return st;
+			RT_HIP_TRY(hipSetDevice(ctx->device));
+		}
 		// big scenes: they meet in HBM, 16 bytes per chunk (or per sample) of this rank's rows
 		if (plan.item_sums_bytes > ctx->item_sums.bytes && plan.queue.halves && plan.big_scene && ctx->item_sums.reserve(plan.item_sums_bytes) != hipSuccess)
 		{
@@ -180,6 +194,14 @@ rt_hip_status render_device(rt_hip_ctx* ctx, uint32_t width, uint32_t height, ui
 		launch_preview(f, ctx->scene, d_rgba8, d_rgb_f32, counters, s);
 	else if (flags & RT_HIP_FLAG_FAST)
 		variant = launch_render_fast(f, ctx->scene, ctx->small, plan, d_rgba8, d_rgb_f32, counters, rolling, ctx->compute_units, ctx->cache, s);
+	else if (plan.build.lights)
+	{
+		// the light builds read the SAME device_scene words: a copy whose four per-primitive shading / scatter pointers point at the light variant
+		device_scene lit = ctx->scene;
+		lit.primitive_shading = ctx->light_shading, lit.primitive_scatter = ctx->light_scatter;
+		lit.primitive_shading_sm = ctx->light_shading_sm, lit.primitive_scatter_sm = ctx->light_scatter_sm;
+		variant = launch_render(f, lit, (flags & RT_HIP_FLAG_SM_MATERIALS) ? ctx->small_sm : ctx->small, plan, d_rgba8, d_rgb_f32, counters, rolling, ctx->compute_units, ctx->cache, s);
+	}
 	else
 		variant = launch_render(f, ctx->scene, (flags & RT_HIP_FLAG_SM_MATERIALS) ? ctx->small_sm : ctx->small, plan, d_rgba8, d_rgb_f32, counters, rolling, ctx->compute_units, ctx->cache, s);
 	RT_HIP_TRY(hipGetLastError());

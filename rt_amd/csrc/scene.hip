@@ -440,6 +440,75 @@ namespace rt_hip
 		return ok();
 	}
 
+	// RT_HIP_FLAG_EMISSION: the light variant of the four per-primitive tables.  From the resident tables read back from
+	// the device — the very rows the ordinary builds read — and the primitives' material indices: a primitive whose material is a light
+	// gets (emission.rgb, 0) and scatter_emit under both scatter tables, every other row is the ordinary table's.  One block, 256-byte
+	// aligned starts.  Stale after a scene upload (even of an unchanged fingerprint's re-upload) and after rt_hip_set_emission.
+	rt_hip_status ensure_light_tables(rt_hip_ctx* ctx)
+	{
+		if (ctx->light_tables_uploads == ctx->scene_uploads && ctx->light_tables_version == ctx->emission_version && ctx->light_shading)
+			return ok();
+		const auto t0 = std::chrono::steady_clock::now();
+		const device_scene& d = ctx->scene;
+		if (ctx->emission_rows != d.n_materials) // (the caller's check; an index below must stay inside the table)
+			return fail(RT_HIP_INVALID_ARGUMENT, "RT_HIP_FLAG_EMISSION: the emission table has %u rows, the resident scene %u materials", ctx->emission_rows, d.n_materials);
+		RT_HIP_TRY(hipSetDevice(ctx->device));
+		RT_HIP_TRY(hipDeviceSynchronize()); // a previous frame may still be reading the old tables
+		ctx->light_tables_uploads = 0;
+		ctx->light_shading = ctx->light_shading_sm = nullptr;
+		ctx->light_scatter = ctx->light_scatter_sm = nullptr;
+		const size_t n_primitives = static_cast<size_t>(d.n_spheres) + d.n_planes + d.n_boxes;
+		std::vector<uint32_t> material(n_primitives, 0u);
+		std::vector<float> box_bounds(static_cast<size_t>(d.n_boxes) * 8u);
+		if (d.n_spheres)
+			RT_HIP_TRY(hipMemcpy(material.data(), d.sphere_material, static_cast<size_t>(d.n_spheres) * 4u, hipMemcpyDeviceToHost));
+		if (d.n_planes)
+			RT_HIP_TRY(hipMemcpy(material.data() + d.n_spheres, d.plane_material, static_cast<size_t>(d.n_planes) * 4u, hipMemcpyDeviceToHost));
+		if (d.n_boxes)
+		{
+			RT_HIP_TRY(hipMemcpy(box_bounds.data(), d.box_bounds, box_bounds.size() * 4u, hipMemcpyDeviceToHost));
+			for (uint32_t i = 0; i < d.n_boxes; i++) // (the material index rides in the min corner's spare lane: build_image)
+				std::memcpy(&material[static_cast<size_t>(d.n_spheres) + d.n_planes + i], &box_bounds[static_cast<size_t>(i) * 8u + 3u], 4);
+		}
+		const size_t shading_bytes = align_up(n_primitives * sizeof(float4), 256), scatter_bytes = align_up(n_primitives * 4u, 256);
+		const size_t shading_at = 0, scatter_at = shading_bytes, shading_sm_at = scatter_at + scatter_bytes, scatter_sm_at = shading_sm_at + shading_bytes;
+		const size_t total = std::max<size_t>(scatter_sm_at + scatter_bytes, 256);
+		std::vector<unsigned char> image(total, 0);
+		if (n_primitives)
+		{
+			RT_HIP_TRY(hipMemcpy(image.data() + shading_at, d.primitive_shading, n_primitives * sizeof(float4), hipMemcpyDeviceToHost));
+			RT_HIP_TRY(hipMemcpy(image.data() + scatter_at, d.primitive_scatter, n_primitives * 4u, hipMemcpyDeviceToHost));
+			RT_HIP_TRY(hipMemcpy(image.data() + shading_sm_at, d.primitive_shading_sm, n_primitives * sizeof(float4), hipMemcpyDeviceToHost));
+			RT_HIP_TRY(hipMemcpy(image.data() + scatter_sm_at, d.primitive_scatter_sm, n_primitives * 4u, hipMemcpyDeviceToHost));
+		}
+		for (size_t i = 0; i < n_primitives; i++)
+		{
+			const uint32_t m = material[i];
+			if (m >= ctx->emission_rows) // (make_resident refuses such an index: never)
+				return fail(RT_HIP_RUNTIME_ERROR, "RT_HIP_FLAG_EMISSION: primitive %zu has material index %u out-of-range", i, m);
+			const float* const rgb = ctx->emission.data() + static_cast<size_t>(m) * 3u;
+			if (!is_light(rgb))
+				continue;
+			const float row[4] = { rgb[0], rgb[1], rgb[2], 0.0f };
+			const uint32_t emit = scatter_emit;
+			for (const size_t at : { shading_at, shading_sm_at })
+				std::memcpy(image.data() + at + i * sizeof(float4), row, sizeof row);
+			for (const size_t at : { scatter_at, scatter_sm_at })
+				std::memcpy(image.data() + at + i * 4u, &emit, 4);
+		}
+		RT_HIP_TRY(ctx->light_tables.reserve(total));
+		RT_HIP_TRY(hipMemcpy(ctx->light_tables.ptr, image.data(), total, hipMemcpyHostToDevice));
+		const unsigned char* const base = ctx->light_tables.as<unsigned char>();
+		ctx->light_shading = reinterpret_cast<const float4*>(base + shading_at);
+		ctx->light_scatter = reinterpret_cast<const uint32_t*>(base + scatter_at);
+		ctx->light_shading_sm = reinterpret_cast<const float4*>(base + shading_sm_at);
+		ctx->light_scatter_sm = reinterpret_cast<const uint32_t*>(base + scatter_sm_at);
+		ctx->light_tables_uploads = ctx->scene_uploads;
+		ctx->light_tables_version = ctx->emission_version;
+		ctx->stats.upload_ms += static_cast<float>(seconds_since(t0) * 1e3);
+		return ok();
+	}
+
 	rt_hip_status ensure_box_bvh(rt_hip_ctx* ctx, hipStream_t stream)
 	{
 		RT_HIP_TRY(hipSetDevice(ctx->device));

@@ -28,6 +28,10 @@
 //                           16 samples — or of --progressive SAMPLES — over the pixels that have not converged yet; render() is called
 //                           until the accumulation is complete, the last frame is written, and the samples traced are printed against
 //                           pixels x spp.  Hip renderers only; not with --frames, --temporal, --boxes or --denoise
+//   --light KEY=R,G,B       repeatable: the materials named KEY (or the material of that index) are LIGHTS of that emission; KEY=V is a grey
+//                           light (exported to the renderer as RT_HIP_LIGHTS, the items joined with ';': rt_hip_lights_from_spec,
+//                           rt_hip_set_emission, RT_HIP_FLAG_EMISSION).  Hip renderers only; not with --progressive, --adaptive,
+//                           --temporal, --denoise or --boxes
 //   --dolly DX,DY,DZ        the camera moves by that much in world space before every frame after the first (camera::pose)
 //   --shared-frame NAME --rank R --world N   this process is rank R of N rt_headless processes that render ONE frame
 //                together (one per GPU: RT_HIP_DEVICE picks this one's): the back buffer is every process's mapping of the
@@ -141,7 +145,7 @@ namespace
 
 int main(int argc, char** argv)
 {
-	std::string scene_path, renderer_name, out_path, shared_name;
+	std::string scene_path, renderer_name, out_path, shared_name, lights;
 	unsigned width = 800, height = 600, spp = 0, bounces = 0, frames = 1, rank = 0, world = 1, progressive = 0;
 	bool frames_given = false;
 	bool list = false;
@@ -234,6 +238,11 @@ int main(int argc, char** argv)
 			adaptive = true;
 			::setenv("RT_HIP_ADAPTIVE", threshold, 1); // (read by the plug-in: every render() is one rt_hip_render_adaptive pass)
 		}
+		else if (arg == "--light"sv)
+		{
+			lights += (lights.empty() ? "" : ";") + std::string{ value() };
+			::setenv("RT_HIP_LIGHTS", lights.c_str(), 1); // (read by the plug-in: the emission table from the scene's material names, RT_HIP_FLAG_EMISSION)
+		}
 		else if (arg == "--dolly"sv)
 		{
 			char trailing = 0;
@@ -252,7 +261,7 @@ int main(int argc, char** argv)
 			world = static_cast<unsigned>(std::strtoul(value(), nullptr, 10));
 		else if (arg == "--help"sv || arg == "-h"sv)
 		{
-			log("usage: rt_headless [--list] [--scene file.toml] [--renderer name] [--size WxH] [--spp N] [--bounces N] [--seed N] [--frames N] [--out file.ppm] [--progressive SAMPLES] [--denoise] [--boxes [--box-bvh]] [--temporal] [--adaptive THRESHOLD] [--dolly DX,DY,DZ] [--shared-frame NAME --rank R --world N]");
+			log("usage: rt_headless [--list] [--scene file.toml] [--renderer name] [--size WxH] [--spp N] [--bounces N] [--seed N] [--frames N] [--out file.ppm] [--progressive SAMPLES] [--denoise] [--boxes [--box-bvh]] [--temporal] [--adaptive THRESHOLD] [--light KEY=R,G,B]... [--dolly DX,DY,DZ] [--shared-frame NAME --rank R --world N]");
 			return 0;
 		}
 		else
@@ -288,6 +297,11 @@ int main(int argc, char** argv)
 	if (boxes && (progressive || std::string_view{ desc->name }.substr(0, 3) != "hip"sv))
 	{
 		error("--boxes traces the scene's boxes in one-shot frames of a hip renderer (not with --progressive, not '", desc->name, "')");
+		return 2;
+	}
+	if (!lights.empty() && (progressive || adaptive || temporal || denoise || boxes || std::string_view{ desc->name }.substr(0, 3) != "hip"sv))
+	{
+		error("--light makes materials lights in one-shot frames of a hip renderer (not with --progressive, --adaptive, --temporal, --denoise or --boxes, not '", desc->name, "')");
 		return 2;
 	}
 	if (box_bvh && (!boxes || temporal))

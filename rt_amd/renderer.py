@@ -104,6 +104,18 @@ def adaptive_default_params() -> RtHipAdaptiveParams:
     return params
 
 
+def lights_from_spec(spec: str, material_names=None, n_materials: int | None = None) -> np.ndarray:
+    """rt_hip_lights_from_spec: an emission table float32[n_materials, 3] from ``KEY=R,G,B;KEY=V;...`` (pure host code).  An
+    all-digit KEY is a material index, any other a material name (every material of that name).  Raises RtHipError with the item
+    in the message for a malformed spec."""
+    names = list(material_names) if material_names is not None else None
+    n = len(names) if n_materials is None else n_materials
+    table = np.zeros((n, 3), dtype=np.float32)
+    c_names = (C.c_char_p * max(n, 1))(*[name.encode() for name in names]) if names is not None else None
+    check(capi.hip_lib().rt_hip_lights_from_spec(spec.encode(), c_names, n, table.ctypes.data_as(capi.c_float_p)))
+    return table
+
+
 def device_count() -> int:
     n = C.c_int()
     check(capi.hip_lib().rt_hip_device_count(C.byref(n)))
@@ -181,6 +193,16 @@ class HipRayTracer:
 
     def __exit__(self, *exc):
         self.close()
+
+    def set_emission(self, emission=None) -> None:
+        """rt_hip_set_emission: the context's emission table, float32[n_materials, 3] (None clears it).  A material whose row has a
+        component above 0 is a light in frames rendered with RT_HIP_FLAG_EMISSION; the table is copied, survives
+        scene uploads and reaches every member device."""
+        if emission is None:
+            check(self._lib.rt_hip_set_emission(self._ctx, None, 0))
+            return
+        table = np.ascontiguousarray(emission, dtype=np.float32).reshape(-1, 3)
+        check(self._lib.rt_hip_set_emission(self._ctx, table.ctypes.data_as(capi.c_float_p), len(table)))
 
     # ---- drop-in ------------------------------------------------------------------------------------------
     def render(self, scene: RtHipScene, width: int, height: int, seed: int = 1, flags: int = 0, want_rgb: bool = False, out: np.ndarray | None = None, stats: bool = True):

@@ -15,10 +15,13 @@
 #include "../renderer.hpp"
 MUU_DISABLE_WARNINGS;
 #include <muu/thread_pool.h>
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
+#include <string>
+#include <vector>
 #include <rt_hip.h>
 MUU_ENABLE_WARNINGS;
 
@@ -207,6 +210,20 @@ namespace
 		return threshold;
 	}
 
+	// RT_HIP_LIGHTS="KEY=R,G,B;KEY=V;..." (rt_headless --light) makes materials LIGHTS (RT_HIP_FLAG_EMISSION): rt::materials has no emission
+	// column, so the table comes from this text and the scene's material names (rt_hip_lights_from_spec: a KEY is a material's name, or its
+	// index) and is handed to the context (rt_hip_set_emission) — again whenever the materials change.  Unset or empty: no lights.  One-shot
+	// frames only: progressive, adaptive and temporal frames refuse the flag by name.  (Not for the preview, which ignores it.)
+	const char* lights_spec()
+	{
+		static const char* const spec = []
+		{
+			const char* lights = std::getenv("RT_HIP_LIGHTS");
+			return (lights && *lights) ? lights : nullptr;
+		}();
+		return spec;
+	}
+
 	// ModeFlags: 0 = mg_ray_tracer's scatter table; RT_HIP_FLAG_SM_MATERIALS = sm_ray_tracer's (dielectrics refract);
 	// RT_HIP_FLAG_PREVIEW = the one-ray-per-pixel preview of src/renderers/rasterizer.cpp
 	template <uint32_t ModeFlags>
@@ -217,6 +234,37 @@ namespace
 		uint64_t frame_number = 0;
 		bool temporal_unsupported = false; // RT_HIP_TEMPORAL on a renderer of several GPUs: refused once, then whole frames as without it
 		bool adaptive_unsupported = false; // RT_HIP_ADAPTIVE on such a renderer: likewise
+		std::vector<std::string> light_names; // RT_HIP_LIGHTS: the material names the context's emission table was made from
+		bool lights_set = false;
+
+		// RT_HIP_FLAG_EMISSION with the context's table made from RT_HIP_LIGHTS and this scene's materials; false: it could not be (said)
+		bool light_flags(const rt::scene& scene, uint32_t& flags)
+		{
+			flags = RT_HIP_FLAG_NONE;
+			const char* const spec = lights_spec();
+			if (!spec || ModeFlags == RT_HIP_FLAG_PREVIEW)
+				return true;
+			const size_t n = scene.materials.size();
+			const std::string* const names = scene.materials.name();
+			if (!lights_set || light_names.size() != n || !std::equal(light_names.begin(), light_names.end(), names))
+			{
+				lights_set = false;
+				light_names.assign(names, names + n);
+				std::vector<const char*> c_names(n);
+				for (size_t m = 0; m < n; m++)
+					c_names[m] = light_names[m].c_str();
+				std::vector<float> emission(n * 3u);
+				if (rt_hip_lights_from_spec(spec, c_names.data(), static_cast<uint32_t>(n), emission.data()) != RT_HIP_OK
+					|| rt_hip_set_emission(ctx, n ? emission.data() : nullptr, static_cast<uint32_t>(n)) != RT_HIP_OK)
+				{
+					std::cerr << "error: hip_ray_tracer: " << rt_hip_last_error() << "\n";
+					return false;
+				}
+				lights_set = true;
+			}
+			flags = RT_HIP_FLAG_EMISSION;
+			return true;
+		}
 
 		~hip_renderer() noexcept override
 		{
@@ -278,6 +326,10 @@ namespace
 			const char* fixed	= std::getenv("RT_HIP_SEED");
 			const uint64_t seed = fixed ? std::strtoull(fixed, nullptr, 0) : ++frame_number;
 
+			uint32_t lights = RT_HIP_FLAG_NONE; // (RT_HIP_LIGHTS: RT_HIP_FLAG_EMISSION, the table in place)
+			if (!light_flags(scene, lights))
+				return;
+
 			if constexpr (ModeFlags != RT_HIP_FLAG_PREVIEW)
 				if (const float threshold = adaptive_threshold(); threshold >= 0.0f && !adaptive_unsupported)
 				{
@@ -291,7 +343,7 @@ namespace
 						if (params.min_samples < two_passes && two_passes <= 0xFFFFFFFFull)
 							params.min_samples = static_cast<uint32_t>(two_passes);
 					}
-					const rt_hip_status st = rt_hip_render_adaptive(ctx, &s, pixels.data(), pixels.size().x, pixels.size().y, fixed ? seed : 1u, accel_flags() | ModeFlags, pass_samples, &params, nullptr, nullptr, nullptr, nullptr);
+					const rt_hip_status st = rt_hip_render_adaptive(ctx, &s, pixels.data(), pixels.size().x, pixels.size().y, fixed ? seed : 1u, accel_flags() | lights | ModeFlags, pass_samples, &params, nullptr, nullptr, nullptr, nullptr);
 					if (st == RT_HIP_OK)
 						return;
 					if (st != RT_HIP_UNSUPPORTED)
@@ -309,7 +361,7 @@ namespace
 					const uint64_t frame_seed = fixed ? std::strtoull(fixed, nullptr, 0) + ++frame_number : seed; // (unpinned: `seed` is ++frame_number already)
 					rt_hip_denoise_params filter{};
 					const bool filtered = denoise_mode() != 0u && rt_hip_denoise_default_params(&filter) == RT_HIP_OK;
-					const rt_hip_status st = temporal_unsupported ? RT_HIP_UNSUPPORTED : rt_hip_render_temporal(ctx, &s, pixels.data(), pixels.size().x, pixels.size().y, frame_seed, accel_flags() | ModeFlags, nullptr, filtered ? &filter : nullptr, nullptr, nullptr, nullptr);
+					const rt_hip_status st = temporal_unsupported ? RT_HIP_UNSUPPORTED : rt_hip_render_temporal(ctx, &s, pixels.data(), pixels.size().x, pixels.size().y, frame_seed, accel_flags() | lights | ModeFlags, nullptr, filtered ? &filter : nullptr, nullptr, nullptr, nullptr);
 					if (st == RT_HIP_OK)
 						return;
 					if (st != RT_HIP_UNSUPPORTED)
@@ -321,7 +373,7 @@ namespace
 					if (!temporal_unsupported)
 						std::cerr << "error: hip_ray_tracer: " << rt_hip_last_error() << ": RT_HIP_TEMPORAL is ignored for this renderer\n";
 					temporal_unsupported = true;
-					if (rt_hip_render(ctx, &s, pixels.data(), pixels.size().x, pixels.size().y, frame_seed, frame_flags() | accel_flags() | ModeFlags, nullptr, nullptr) != RT_HIP_OK)
+					if (rt_hip_render(ctx, &s, pixels.data(), pixels.size().x, pixels.size().y, frame_seed, frame_flags() | accel_flags() | lights | ModeFlags, nullptr, nullptr) != RT_HIP_OK)
 						std::cerr << "error: hip_ray_tracer: " << rt_hip_last_error() << "\n";
 					return;
 				}
@@ -330,14 +382,14 @@ namespace
 				{
 					// (a seed per frame would start the accumulation again on every call: RT_HIP_SEED, or 1, for all of them)
 					rt_hip_progress progress{};
-					if (rt_hip_render_progressive(ctx, &s, pixels.data(), pixels.size().x, pixels.size().y, fixed ? seed : 1u, accel_flags() | ModeFlags, pass_samples, nullptr, nullptr, &progress) != RT_HIP_OK)
+					if (rt_hip_render_progressive(ctx, &s, pixels.data(), pixels.size().x, pixels.size().y, fixed ? seed : 1u, accel_flags() | lights | ModeFlags, pass_samples, nullptr, nullptr, &progress) != RT_HIP_OK)
 						std::cerr << "error: hip_ray_tracer: " << rt_hip_last_error() << "\n";
 					else if (const uint32_t mode = denoise_mode(); mode == 2u || (mode == 1u && progress.samples_done < progress.samples_total))
 						if (rt_hip_denoise_progressive(ctx, nullptr, pixels.data(), nullptr, nullptr) != RT_HIP_OK) // (on failure the pass's own frame stays)
 							std::cerr << "error: hip_ray_tracer: " << rt_hip_last_error() << "\n";
 					return;
 				}
-			if (rt_hip_render(ctx, &s, pixels.data(), pixels.size().x, pixels.size().y, seed, frame_flags() | accel_flags() | ModeFlags, nullptr, nullptr)
+			if (rt_hip_render(ctx, &s, pixels.data(), pixels.size().x, pixels.size().y, seed, frame_flags() | accel_flags() | lights | ModeFlags, nullptr, nullptr)
 				!= RT_HIP_OK)
 				std::cerr << "error: hip_ray_tracer: " << rt_hip_last_error() << "\n";
 		}
