@@ -2,7 +2,7 @@
 // render kernel (kernels.hip, render_queue<-4>) and the known-answer kernel of the test-only library (kat.hip).
 //
 // SAME ANSWER AS THE LINEAR SCAN.  test_spheres keeps the lexicographic minimum of (t, index) over the spheres it accepts
-// (scan.hpp, and scan_spheres_together in kernels.hip).  The traversal below
+// (scan.hpp, and scan_spheres_together in scan_streamed.hpp).  The traversal below
 //   * tests every sphere it reaches with probe_sphere and the square-root half of finish_sphere, on the same (c, r^2) floats;
 //   * accepts a candidate when t < best.t || (t == best.t && index < best.index), `index` being the sphere's scene index;
 //   * culls a box only where no sphere inside can produce a computed t that would be accepted (the bound below).

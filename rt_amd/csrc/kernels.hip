@@ -40,11 +40,21 @@
 //
 // What is launched is decided elsewhere: launch_plan.cpp (plan_launch: which kernel, which build, queue shape, grid, LDS — host-only
 // policy, tested on the CPU).  This file holds the kernels and the dispatch from a plan's kernel_build to the instantiation.
+// What render_queue is made of lies in headers by subject: queue_build.hpp (every build's properties, and the argument words that mean
+// different things per build), scan.hpp / scan_streamed.hpp / bvh_scan.hpp / box_bvh_scan.hpp (the closest-hit scans), camera_forms.hpp
+// and lane_state.hpp (what a lane carries, what a pixel's samples start from), handover.hpp (the rolling kernels' cross-wave protocol),
+// pixel_output.hpp (rows, finishing a pixel, the segment count).
 #include "kernels.hpp"
 #include "contract.hpp"
 #include "scan.hpp"
 #include "bvh_scan.hpp"
 #include "box_bvh_scan.hpp"
+#include "scan_streamed.hpp"
+#include "handover.hpp"
+#include "pixel_output.hpp"
+#include "lane_state.hpp"
+#include "queue_build.hpp"
+#include "camera_forms.hpp"
 
 #ifdef RT_HIP_FAST_BUILD
 #define render_queue render_queue_fast
@@ -54,26 +64,6 @@
 #include "../../include/rt_hip.h"
 
 #include <algorithm>
-
-// waves per SIMD the kernel variants are compiled for (register budget = 512 / waves): measured, see render_queue
-#ifndef RT_HIP_WAVES_FEW
-#define RT_HIP_WAVES_FEW 7 // scalar-register kernels in general
-#endif
-// ... and those that hold six or more spheres and seven or more primitives (7 + 0, 8 + 0, 6 + 1, 7 + 1, 6 + 2): 80 registers instead of
-// 72 spare them most of their scratch, which costs more than the seventh wave brings — every (spheres, planes) build at 7 and at 6 waves:
-// profiles/r05/small_sweep.txt (round 4 had settled the same question build by build: waves_full_ab.txt)
-#ifndef RT_HIP_WAVES_MANY
-#define RT_HIP_WAVES_MANY 6
-#endif
-#ifndef RT_HIP_WAVES_RESIDENT
-#define RT_HIP_WAVES_RESIDENT 7
-#endif
-// (RT_HIP_WAVES_DENSE — the streamed kernel of frames that fill the device — and RT_HIP_PERSISTENT_WAVES_CAP: launch_plan.hpp, whose plan reads them too)
-// the BVH kernel (scan_bvh, RT_HIP_FLAG_BVH): a pixel tile per wave with a traversal stack of bvh_max_depth words per lane in LDS
-// (24 KiB per workgroup)
-#ifndef RT_HIP_WAVES_BVH
-#define RT_HIP_WAVES_BVH 5
-#endif
 
 // Region counters (tools/region_profile.py; built only as an experiment variant, never in the product): how often each
 // part of a loop trip runs and with how many lanes — the dynamic side of profiles/r02/isa_trip_breakdown.txt.
@@ -95,177 +85,6 @@ namespace rt_hip
 
 	namespace
 	{
-		// The streamed kernel's sphere scan: the (center, radius^2) table is read from HBM/L2 with wave-uniform scalar loads,
-		// four spheres = 64 bytes = one s_load_dwordx16.  Every wave of a CU walks the 1.6 MB table at its own position, so
-		// the 16 KB scalar cache holds next to nothing of it (SQC_DCACHE: 29 % hits at 100 000 spheres,
-		// profiles/r03/config5_streamed/) and most loads come from L2.  The load of group g+1 is therefore issued BEFORE
-		// group g is probed (two register sets, the loop unrolled by two so that no set is ever copied): the wave has 48
-		// vector instructions to issue while its next 64 bytes are on their way.
-		__device__ __forceinline__ void probe_group(candidate& best, vec3 o, vec3 d, float4 s0, float4 s1, float4 s2, float4 s3, uint32_t first_index)
-		{
-			const sphere_probe p0 = probe_sphere(o, d, s0);
-			const sphere_probe p1 = probe_sphere(o, d, s1);
-			const sphere_probe p2 = probe_sphere(o, d, s2);
-			const sphere_probe p3 = probe_sphere(o, d, s3);
-			const unsigned long long m0 = __builtin_amdgcn_ballot_w64(p0.pos), m1 = __builtin_amdgcn_ballot_w64(p1.pos);
-			const unsigned long long m2 = __builtin_amdgcn_ballot_w64(p2.pos), m3 = __builtin_amdgcn_ballot_w64(p3.pos);
-			if ((m0 | m1 | m2 | m3) != 0)
-			{
-				finish_sphere(best, p0, s0.w, first_index, m0);
-				finish_sphere(best, p1, s1.w, first_index + 1, m1);
-				finish_sphere(best, p2, s2.w, first_index + 2, m2);
-				finish_sphere(best, p3, s3.w, first_index + 3, m3);
-			}
-		}
-
-		__device__ __forceinline__ void scan_streamed_spheres(candidate& best, vec3 o, vec3 d, const float4* __restrict__ table, uint32_t count)
-		{
-			const uint32_t groups = count >> 2;
-			if (groups)
-			{
-				float4 a0 = table[0], a1 = table[1], a2 = table[2], a3 = table[3];
-				uint32_t g = 0;
-				for (; g + 2 <= groups; g += 2)
-				{
-					const float4* const b = table + (g + 1) * 4;
-					const float4 b0 = b[0], b1 = b[1], b2 = b[2], b3 = b[3];
-					probe_group(best, o, d, a0, a1, a2, a3, g * 4);
-					const float4* const a = table + (g + 2 < groups ? g + 2 : groups - 1) * 4; // (past the end: the last group again, unused)
-					a0 = a[0], a1 = a[1], a2 = a[2], a3 = a[3];
-					probe_group(best, o, d, b0, b1, b2, b3, (g + 1) * 4);
-				}
-				if (g < groups)
-					probe_group(best, o, d, a0, a1, a2, a3, g * 4);
-			}
-			for (uint32_t i = groups * 4; i < count; i++)
-				test_sphere(best, o, d, table[i], i);
-		}
-
-		// SPARSE WAVES (streamed kernel).  A scan costs a wave the same whether one lane holds a ray or all 64 do.  At the
-		// end of a launch — and in small frames of big scenes — waves hold a handful of rays: such a wave turns the scan
-		// around and walks the table ONCE PER RAY with all 64 lanes, lane l testing spheres l, l + 64, ... (coalesced 16-byte
-		// loads), followed by a wave-wide minimum.  test_spheres keeps the first sphere at the smallest accepted distance
-		// (`hit_dist <= *hit` -> continue, mg_ray_tracer.cpp:74), i.e. the lexicographic minimum of (t, index) over the
-		// accepted candidates; every lane takes that minimum over its own spheres in index order, and the 64 partial results
-		// are reduced with the same order — accepted distances are >= 0.001, so their bit patterns order like the numbers.
-		// The one thing a minimum cannot reproduce is a NaN distance (a degenerate ray), which the sequential rule lets
-		// in and then never displaces consistently: if any lane meets one, the ray is reported as not scanned and goes
-		// through the sequential scan.  The per-sphere arithmetic is finish_sphere's, bit for bit.
-		constexpr uint32_t sparse_min_spheres = sparse_launch_min_spheres; // (below that a sequential scan is a few microseconds anyway)
-
-		__device__ __forceinline__ void test_sphere_alone(candidate& best, bool& met_nan, vec3 o, vec3 d, float4 s, uint32_t index)
-		{
-			const sphere_probe p = probe_sphere(o, d, s);
-			if (p.pos) // a per-lane branch: every lane looks at a different sphere, and few spheres lie on a ray's line
-			{
-				const float f = sqrt_rn(p.disc);
-				const float t = (p.e2 < s.w) ? p.a + f : p.a - f;
-				met_nan = met_nan || t != t;
-				const bool accept = !(t < min_hit_dist) && !(best.have && best.t <= t);
-				best.t = accept ? t : best.t;
-				best.index = accept ? index : best.index;
-				best.have = best.have || accept;
-			}
-		}
-
-		// call converged, with a wave-uniform ray; returns false if the ray has to be scanned sequentially instead
-		__device__ __forceinline__ bool scan_spheres_together(candidate& found, vec3 o, vec3 d, const float4* __restrict__ table, uint32_t count, uint32_t lane)
-		{
-			candidate mine = { 0.0f, 0u, false };
-			bool met_nan = false;
-			uint32_t i = lane;
-			// four independent loads in flight per lane: the walk is bound by L2 latency, not by arithmetic.  (The registers
-			// they take cost the kernel one wave per SIMD of occupancy, 5 instead of 6, which the sequential scan — bound by
-			// vector issue — does not miss: config 5 5.61 against 5.69 s with two loads in flight, 10 000 spheres 277 against
-			// 290 ms; profiles/r03/config5_streamed/sparse_waves_ab.txt.)
-			for (; i + 192u < count; i += 256u)
-			{
-				const float4 s0 = table[i], s1 = table[i + 64u], s2 = table[i + 128u], s3 = table[i + 192u];
-				test_sphere_alone(mine, met_nan, o, d, s0, i);
-				test_sphere_alone(mine, met_nan, o, d, s1, i + 64u);
-				test_sphere_alone(mine, met_nan, o, d, s2, i + 128u);
-				test_sphere_alone(mine, met_nan, o, d, s3, i + 192u);
-			}
-			for (; i < count; i += 64u)
-				test_sphere_alone(mine, met_nan, o, d, table[i], i);
-			if (__builtin_amdgcn_ballot_w64(met_nan) != 0)
-				return false;
-			uint32_t key_t = mine.have ? __float_as_uint(mine.t) : 0xFFFFFFFFu; // (no accepted distance has this pattern: it is a NaN's)
-			uint32_t key_i = mine.have ? mine.index : 0xFFFFFFFFu;
-#pragma unroll
-			for (int offset = 32; offset > 0; offset >>= 1)
-			{
-				const uint32_t other_t = __shfl_xor(key_t, offset, 64);
-				const uint32_t other_i = __shfl_xor(key_i, offset, 64);
-				const bool take = other_t < key_t || (other_t == key_t && other_i < key_i);
-				key_t = take ? other_t : key_t;
-				key_i = take ? other_i : key_i;
-			}
-			found.have = key_t != 0xFFFFFFFFu;
-			found.t = found.have ? __uint_as_float(key_t) : 0.0f;
-			found.index = found.have ? key_i : 0u;
-			return true;
-		}
-
-		// everything a lane carries between loop trips
-		struct lane_state
-		{
-			vec3 origin, dir;	// current ray
-			vec3 throughput;	// product of attenuations so far (trace unrolled front to back)
-			vec3 chunk_sum;		// running sum of the chunk of samples in flight (:186,193)
-			// what a pixel's samples start from (frame_params): pinhole camera — the near-to-far vector through the pixel's
-			// corner; eye form — s N' and s N.w of the corner; homogeneous form — (x, y, -, -) of the pixel
-			float base_x, base_y, base_z, base_w; // (named words, not an array: hipcc otherwise keeps half of it in scratch)
-			stream_keys keys;	// random streams of the pixel (contract.hpp): the key of its hash function and its counter stride
-			uint32_t counter;	// random stream position
-			// The samples of an item, counted in STREAM POSITIONS: a sample's window starts at stride * (index << 12)
-			// (contract.hpp), so "the next sample" is one shift-and-add on the window start and nothing has to be multiplied
-			// per restart.  `window` = where the sample in flight started, `window_end` = where the first sample behind the
-			// item would start (the stride is odd and an index is below 2^20: distinct samples, distinct windows; index 0 is
-			// the one window that starts at position 0).
-			uint32_t window, window_end;
-			uint32_t sample;	 // [INDEXED kernels only] index of the sample in flight
-			uint32_t sample_end; // [INDEXED kernels only] one past the last sample of the item in flight
-		};
-
-		// image row of row `local_row` of this rank's compact buffer (rt_hip_partition).  All branches are wave-uniform.
-		__device__ __forceinline__ uint32_t global_row(uint32_t local_row, const frame_params& p)
-		{
-			if (p.world == 1u)
-				return local_row; // the whole frame: no arithmetic at all
-			if (p.stripe_shift != 0xFFFFFFFFu) // stripes of 2^k rows (the default, 8): shifts instead of a division
-				return ((((local_row >> p.stripe_shift) * p.world) + p.rank) << p.stripe_shift) | (local_row & ((1u << p.stripe_shift) - 1u));
-			return ((local_row / p.stripe_rows) * p.world + p.rank) * p.stripe_rows + (local_row % p.stripe_rows);
-		}
-
-		// row of the output buffers that local row `ly` of this rank is written to (wave-uniform branch)
-		__device__ __forceinline__ uint32_t output_row(uint32_t ly, const frame_params& p) { return p.frame_rows ? global_row(ly, p) : ly; }
-
-		// :195-200 — mean, sqrt "gamma", pack, store
-		__device__ __forceinline__ void finish_pixel(vec3 colour, const frame_params& p, uint32_t lx, uint32_t ly, uint32_t* out_rgba, float* out_rgb)
-		{
-			const vec3 mean = pixel_mean(colour, static_cast<float>(p.samples_per_pixel));
-			const size_t o = static_cast<size_t>(output_row(ly, p)) * p.width + lx;
-			if (out_rgb)
-			{
-				out_rgb[o * 3 + 0] = mean.x;
-				out_rgb[o * 3 + 1] = mean.y;
-				out_rgb[o * 3 + 2] = mean.z;
-			}
-			// A system-scope store: written through to memory at once.  When the frame is the caller's page-locked back buffer
-			// (rt_hip_render) the pixels then cross PCIe while the rest of the frame is still being traced; an ordinary store
-			// would sit in L2 until the end-of-kernel write-back and put the whole 8 MB transfer behind the kernel
-			// (measured: + 0.10-0.14 ms per frame, profiles/r02/frame_store_ab.txt).  For a frame in HBM it costs nothing.
-			__hip_atomic_store(&out_rgba[o], pack_mean(mean), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-		}
-
-		// `segments` = the wave's count (wave-uniform: kept in a scalar register, one popcount of the tracing lanes per trip)
-		__device__ __forceinline__ void add_segments(device_counters* counters, unsigned long long segments)
-		{
-			if ((threadIdx.x & 63u) == 0 && segments)
-				atomicAdd(&counters->segments[(blockIdx.x + blockIdx.y * 7u + (threadIdx.x >> 6)) % device_counters::segment_counters], segments);
-		}
-
 		// ---- small / resident kernel: a wave works through a queue of (pixel, sample chunk) items -----------------------
 		//
 		// The pixel sum is defined chunk-wise (arithmetic contract: chunks of 16 consecutive samples, each summed in
@@ -276,22 +95,9 @@ namespace rt_hip
 		// keep waves short, so that a launch has tens of thousands of them to balance over the chip; which lane
 		// computes which chunk cannot change a result.
 		//
-		// NS > 0: `small` kernel, NS spheres in SGPRs (kernel argument).  NS == scan_resident: `resident` kernel, all primitives in LDS.
-		// NS == scan_tiled: `tiled` kernel — the primitives stream from the SoA columns in HBM/L2 through one LDS tile shared by the
-		// workgroup's four waves (coalesced dword per lane per column, radius squared on the way in); every wave still
-		// runs its own queue, but the workgroup advances in lock step, one path segment per trip, with barriers around
-		// each tile, until all four waves are done.  NS == scan_streamed: `streamed` kernel — the resident loop reading the primitive
-		// table from HBM/L2 with wave-uniform scalar loads.  NS == scan_streamed_dense: the same without the cooperative scan of sparse waves, for frames
-		// that fill the device (6 waves per SIMD; RT_HIP_WAVES_DENSE, launch_plan.hpp).  NS == scan_bvh: the BVH kernel (RT_HIP_FLAG_BVH) — the resident
-		// kernel's tile queue, planes scanned from the table in memory, spheres through the hierarchy, one traversal per lane
-		// (bvh_scan.hpp; the lanes of a wave hold unrelated rays, and a wave-wide walk would visit the union of their paths).
-		// SM: scatter table of sm_ray_tracer (RT_HIP_FLAG_SM_MATERIALS) instead of mg_ray_tracer's.
-		// launch bounds: compiled for 7 waves per SIMD.  That raises the compiler's budgets from 64 to 72 vector and from 72
-		// to 88 scalar registers.  With 5..8 spheres in SGPRs and in the resident kernel 64 VGPRs mean scratch
-		// (dielectric.toml, 7 spheres: 3.85 -> 3.54 ms with 72; resident, 1000 spheres: -2 %).  The 1..4 sphere kernels
-		// still fit 64 VGPRs — they keep running 8 waves — and use the extra scalar registers: the lane-mask bookkeeping of
-		// the divergent loop no longer spills to VGPR lanes (3.12 -> 3.05 ms).  6 waves are slower everywhere.  The
-		// big-scene modes get the registers of 5 waves per SIMD.
+		// The builds — SCAN (the scan proper NS and its pass / adaptive / box / box-tree / light builds), HALF, NP, GC — and every property the
+		// body branches on: queue_build.hpp, one paragraph each.  SM: scatter table of sm_ray_tracer (RT_HIP_FLAG_SM_MATERIALS) instead of
+		// mg_ray_tracer's.
 		//
 		// ROLLING ITEMS (NS < 0).  In a big scene a trip is one closest-hit scan over all primitives — the same cost for a
 		// wave with one lane holding a ray as for a wave with 64 — so what matters is that every lane holds a ray in every
@@ -310,166 +116,8 @@ namespace rt_hip
 		// was spent waiting for the slowest waves.  With items the stragglers' excess is one item, not four tiles' worth.
 		// (For small scenes the per-trip cost is the shading code, and lanes that never start together lose the phase
 		// coherence that keeps it short — profiles/r01/queue_shape_sweep.txt.  They keep one tile per wave.)
-		// half-chunks: how many samples of chunk `chunk` lie in its second half (indices chunk * 16 + 8 ..)
-		__device__ __forceinline__ uint32_t parked_samples(uint32_t samples_per_pixel, uint32_t chunk)
-		{
-			const uint32_t first = chunk * sample_chunk + sample_chunk / 2u;
-			return samples_per_pixel > first ? min(samples_per_pixel - first, sample_chunk / 2u) : 0u;
-		}
-
-		__device__ __forceinline__ unsigned long long fetch_items(device_counters* counters, uint32_t count) // call converged
-		{
-			unsigned long long base = 0;
-			if ((threadIdx.x & 63u) == 0)
-				base = atomicAdd(&counters->next_item, static_cast<unsigned long long>(count));
-			const uint32_t lo = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(base));
-			const uint32_t hi = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(base >> 32));
-			return (static_cast<unsigned long long>(hi) << 32) | lo;
-		}
-
-		// A value (a chunk's sum, or one sample's) on its way between waves: 16 bytes per slot, ONE store and ONE load, both
-		// past this CU's L1 and this XCD's L2 (... sc1: the XCDs' L2s are not coherent with one another).
-		//   Round 3 wrote a slot as an 8-byte and a 4-byte agent-scope atomic store and read it back the same way: two memory
-		//   requests each way per sample, tallied by the counters at 32 bytes apiece (config 5: WRITE_SIZE 8.9 GB for 2.1 GB of
-		//   payload).  hipcc has no 16-byte atomic, so the single dwordx4 access is written out
-		//   (the A/B against the old form: profiles/r04/ab_publish_16_bytes.txt).
-		// THE HAND-OVER PROTOCOL (publish -> count the arrival -> the last arrival reads), as the hardware executes it:
-		//   1. the producer's stores are write-through (sc1): when `s_waitcnt vmcnt(0)` lets the wave go on, they have been
-		//      acknowledged by the memory side (gfx950 counts stores in vmcnt and acknowledges a write-through store when it
-		//      has left the L2 for the fabric);
-		//   2. the arrival is an agent-scope atomic add, executed at the memory side, issued after (1) in program order;
-		//   3. the consumer's loads are issued after the atomic's RETURN VALUE has come back (they depend on the branch on
-		//      it) and bypass the non-coherent caches (sc1): they observe memory as of a moment after every producer's (1).
-		// That is an argument from the gfx950 ISA, not from the HIP memory model: in the model's terms the
-		// arrival would be a release (buffer_wbl2 sc1 + s_waitcnt in front of the atomic) and the last arrival an acquire
-		// (buffer_inv sc1 behind it).  RT_HIP_MODEL_ORDERING=1 builds exactly that; measured, it costs the streamed kernel
-		// its scene — buffer_inv sc1 drops the XCD's L2 copy of the sphere table once per finished pixel
-		// (profiles/r04/arrival_ordering_ab.txt) — so the ISA-level form stays, and this file refuses to be compiled for
-		// anything but gfx950, where the argument was made and the suite's parity tests exercise it.
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
-#error "kernels.hip: the cross-wave hand-over of the rolling kernels relies on gfx950's store acknowledgement and sc1 semantics"
-#endif
-		typedef float v4f __attribute__((ext_vector_type(4)));
-
-		__device__ __forceinline__ void publish_sum(unsigned long long* slot, vec3 sum)
-		{
-			const v4f value = { sum.x, sum.y, sum.z, 0.0f };
-			// The two wait states behind the store are part of it: a VMEM store of more than 64 bits reads its data registers
-			// after issue, and a vector instruction that overwrites them within two wait states corrupts the stored value
-			// (gfx940+ "VMEM store data hazard").  The compiler pads its own stores; it cannot see into this one — found the
-			// hard way: the sm kernels' next instruction recycled the value's upper half for an address, and z arrived as a
-			// pointer's low word (profiles/r04/case0_bisect.txt).
-			asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(slot), "v"(value) : "memory");
-		}
-		__device__ __forceinline__ vec3 read_sum(unsigned long long* slot)
-		{
-			v4f value;
-			asm volatile("global_load_dwordx4 %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=v"(value) : "v"(slot) : "memory");
-			return { value.x, value.y, value.z };
-		}
-		// eight consecutive slots, the loads in flight together
-		__device__ __forceinline__ void read_sums8(unsigned long long* first, vec3 (&out)[8])
-		{
-			v4f v0, v1, v2, v3, v4, v5, v6, v7;
-			asm volatile("global_load_dwordx4 %0, %8, off sc1\n\t"
-						 "global_load_dwordx4 %1, %8, off offset:16 sc1\n\t"
-						 "global_load_dwordx4 %2, %8, off offset:32 sc1\n\t"
-						 "global_load_dwordx4 %3, %8, off offset:48 sc1\n\t"
-						 "global_load_dwordx4 %4, %8, off offset:64 sc1\n\t"
-						 "global_load_dwordx4 %5, %8, off offset:80 sc1\n\t"
-						 "global_load_dwordx4 %6, %8, off offset:96 sc1\n\t"
-						 "global_load_dwordx4 %7, %8, off offset:112 sc1\n\t"
-						 "s_waitcnt vmcnt(0)"
-						 : "=&v"(v0), "=&v"(v1), "=&v"(v2), "=&v"(v3), "=&v"(v4), "=&v"(v5), "=&v"(v6), "=&v"(v7)
-						 : "v"(first)
-						 : "memory");
-			out[0] = { v0.x, v0.y, v0.z }, out[1] = { v1.x, v1.y, v1.z }, out[2] = { v2.x, v2.y, v2.z }, out[3] = { v3.x, v3.y, v3.z };
-			out[4] = { v4.x, v4.y, v4.z }, out[5] = { v5.x, v5.y, v5.z }, out[6] = { v6.x, v6.y, v6.z }, out[7] = { v7.x, v7.y, v7.z };
-		}
-
-		// the arrival of an item at its pixel's counter, and what the lane that brings the LAST item does before it reads
-		__device__ __forceinline__ uint32_t count_arrival(uint32_t* counter)
-		{
-#ifdef RT_HIP_MODEL_ORDERING
-			return __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-#else
-			asm volatile("s_waitcnt vmcnt(0) ; what was published has left before the arrival is counted" ::: "memory");
-			return __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
-		}
-		__device__ __forceinline__ void last_arrival()
-		{
-#ifdef RT_HIP_MODEL_ORDERING
-			__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-#else
-			__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); // (no instruction: keeps the loads below the counter's answer)
-#endif
-		}
-
-		// waves per SIMD a build is compiled for (the RT_HIP_WAVES_* above)
-		constexpr int waves_per_simd(int NS, int NP)
-		{
-			if (NS == scan_bvh)
-				return RT_HIP_WAVES_BVH;
-			if (NS == scan_streamed_dense)
-				return RT_HIP_WAVES_DENSE;
-			if (NS < 0) // scan_tiled, scan_streamed
-				return 5;
-			if (NS == scan_resident)
-				return RT_HIP_WAVES_RESIDENT;
-			return NS >= 6 && NS + NP >= 7 ? RT_HIP_WAVES_MANY : RT_HIP_WAVES_FEW;
-		}
-
-		// HALF (small and resident kernels, short launches; see choose_queue): the unit of work is HALF a chunk, 8 samples.
-		// The chunk sum stays what the contract says — sixteen samples added in sample order — so the lane that traces a
-		// chunk's second half cannot add anything up itself: it parks its (up to) eight sample values in the tile's LDS
-		// slot, next to the first half's partial sum, and the fold at the end of the wave continues that partial sum with
-		// them, in order.  Twice as many, half as long items: what a launch with two or three chunks per lane needs to end
-		// evenly (profiles/r03/chunk_probe.txt).
-		// NP (small kernel only; round 4): the NS scalar-register spheres are FOLLOWED BY NP PLANES (slots NS .. NS + NP - 1 of
-		// the kernel argument), so that the reference's own scenes with their ground plane back in (scenes/basic.toml:11-13,
-		// scenes/dielectric.toml:17-19) stay on the scalar-operand path.  Which slot is what is known at compile time: no
-		// kind check at run time, and the no-plane variants are what they were.  NS + NP <= 8, NP <= 3 (more planes, or planes
-		// without a sphere, take the LDS-resident kernel).
-		// GC (small kernel only; round 4): the GENERAL camera — an inverse view-projection whose w varies over the frame takes
-		// the per-sample division (camera.hpp:42-48) instead of contract v3's affine primary rays.  rt's own matrix is the
-		// float inverse of projection x view (camera.hpp:122-137): for a camera that is not axis-aligned its last row comes
-		// out with rounding noise in the x and y terms (-4.5e-7 against a w of 0.001 at the far plane: 4.5e-4 relative — not
-		// something to round away), i.e. every frame while the user looks around.  Those frames used to fall to the
-		// LDS-resident kernel (+35 % on basic.toml); now they keep the scalar-register kernel, in a build of it that carries
-		// the 18 scalars of the general form INSTEAD of the 18 of the affine one (both would not fit its scalar registers).
-		// PASS (progressive frames; the tile-per-wave whole-chunk kernels only): the launch traces chunks [first_chunk, first_chunk +
-		// q.chunks) of every pixel and its fold CONTINUES the pixel's running sum, kept between passes in an accumulator of 3 floats per pixel
-		// laid out like out_rgb.  p.samples_per_pixel is the sample count AFTER the pass, so the frame a pass leaves is the one-shot frame at that
-		// sample count, bit for bit.  A pass build is named by its scan code — scan_resident_pass, scan_bvh_pass: the kernel's first template
-		// argument, of which NS below is the scan proper — so that every other instantiation keeps its symbol, and with it its place in the
-		// listings the unchanged-kernels check compares (tools/kernel_listing_diff.py).  Neither the accumulator nor first_chunk is an argument
-		// of its own: they travel in words these builds do not read (rolling_buffers::accum, kernels.hpp).
-		// ADAPT (adaptive sampling; scan_resident_adapt, scan_bvh_adapt): a PASS build whose pixels carry a state word — samples
-		// held, and "stopped" in bit 31.  Before its first trip the wave ballots its tile's state words into ONE wave-uniform stop mask (a tile
-		// holds at most 64 pixels: launch_plan.cpp); an item of a stopped pixel is empty, like an item of a pixel outside the frame, and the
-		// fold neither reads nor writes such a pixel; a wave whose in-frame pixels have all stopped leaves at once.  An active pixel folds as
-		// PASS does and stores the pass's OWN fold besides (pass_sum: c0, + c1, ... in chunk order — not a difference of running sums).  These
-		// builds finish no pixel: adaptive_update (adaptive.hip) does that for the whole frame.  State words and pass sums lie in one block
-		// behind the accumulator (rt_hip.h, rt_hip_adaptive_pass_device: accum, state, pass_sum, moments), at offsets frame_params gives: no
-		// argument is added.  The first pass (first_chunk == 0) reads no word of the block.
-		// BOXES (RT_HIP_FLAG_TRACE_BOXES; the same two kernels, whole chunks only): the query also scans the scene's boxes — staged
-		// ONCE per workgroup into LDS behind the scan's own table (the resident kernel's primitives, the hierarchy kernel's stacks), two float4s
-		// each, read with wave-uniform addresses after spheres and planes, no votes — and selects among three candidates (scan.hpp).  Named by
-		// scan code like the pass builds — scan_resident_boxes, scan_bvh_boxes — so that every other instantiation keeps its symbol and its
-		// instructions; the box count and the table's pointer are device_scene's.  (Staged rather than read through scalar loads: the
-		// scalar-load build's scalar registers are spoken for by its two groups of four spheres, and 8 KiB of LDS cost no occupancy here.)
-		// BOXTREE (RT_HIP_FLAG_BOX_BVH; the hierarchy kernel only): scan_bvh_boxtree, a box build that stages nothing — the boxes are
-		// reached through a hierarchy of their own (box_bvh_scan.hpp), walked per lane on the stack the sphere traversal has finished with; its
-		// descriptor lies behind the sphere hierarchy's, where item_sums points, so no argument is added.  A lane the traversal does not take
-		// (a zero or non-finite component) scans s.box_bounds in memory; the winning box's corners are read there too.
-		// LIGHTS (RT_HIP_FLAG_EMISSION; the same two kernels, whole chunks only): scan_resident_lights, scan_bvh_lights.  The launch
-		// hands these builds a device_scene whose per-primitive shading / scatter pointers are the LIGHT variant of the tables (scene.hip,
-		// ensure_light_tables): a hit whose scatter row says scatter_emit ends its sample with throughput * the row's shading.rgb — to the fused
-		// tail such a lane is what a lane that ended on the sky is: it draws nothing for the old sample and its stream stands where next_sample
-		// puts it.  No argument is added or moved; every other instantiation keeps its symbol and its instructions.
 		template <int SCAN, bool SM, bool HALF = false, int NP = 0, bool GC = false>
-		__global__ __launch_bounds__(block_threads, waves_per_simd(scan_of(SCAN), NP)) void render_queue(const frame_params p,
+		__global__ __launch_bounds__(block_threads, (queue_build<SCAN, HALF, NP, GC>::waves)) void render_queue(const frame_params p,
 																	  const queue_params q,
 																	  const small_scene small,
 																	  const device_scene s,
@@ -481,27 +129,22 @@ namespace rt_hip
 																									 // descriptor (rolling_buffers::bvh)
 																	  uint32_t* pixel_done)			 // [NS < 0] items arrived per pixel (zeroed in front of every launch); [PASS] the accumulator
 		{
-			constexpr int NS = scan_of(SCAN);
-			constexpr bool PASS = scan_is_pass(SCAN);
-			constexpr bool ADAPT = scan_is_adaptive(SCAN);
-			constexpr bool BOXES = scan_has_boxes(SCAN);
-			constexpr bool BOXTREE = scan_has_box_tree(SCAN);
-			static_assert(!PASS || !HALF, "passes are built for whole chunks only");
-			constexpr bool LIGHTS = scan_has_lights(SCAN);
-			static_assert(!BOXES || !HALF, "the box builds are built for whole chunks only");
-			static_assert(!LIGHTS || (!HALF && scan_of(SCAN) <= 0), "the light builds are built for whole chunks of the tile-per-wave table kernels only");
+			// what this build is (queue_build.hpp has the why of each)
+			using build = queue_build<SCAN, HALF, NP, GC>;
+			constexpr int NS = build::NS;
+			constexpr bool PASS = build::PASS, ADAPT = build::ADAPT, BOXES = build::BOXES, BOXTREE = build::BOXTREE, LIGHTS = build::LIGHTS;
+			constexpr bool RESIDENT = build::RESIDENT, RESIDENT_SCALAR_SCAN = build::RESIDENT_SCALAR_SCAN, BVH = build::BVH, ROLLING = build::ROLLING;
+			constexpr bool INDEXED = build::INDEXED, SCALAR_SEGMENTS = build::SCALAR_SEGMENTS;
+			constexpr uint32_t slot_floats = build::slot_floats;
+			// (the camera form per build: the restart below selects as camera_forms.hpp does.  Its three branches stay in the body, selection
+			// included — as functions of that header they moved the instructions of 133 to 211 kernels)
+			constexpr bool PINHOLE_ONLY = build::PINHOLE_ONLY, EYE_ONLY = build::EYE_ONLY, NEVER_PINHOLE = build::NEVER_PINHOLE;
 			extern __shared__ float4 lds[];
 			// [NS > 0] 8 geometry (with the scatter function) + 8 shading float4s | [NS == scan_resident] all primitives; then the chunk slots
 			float4* const lds_geometry = lds;
 			float4* const lds_shading = lds + scalar_max_spheres;
-			constexpr bool RESIDENT = NS == scan_resident; // all primitives in LDS
-			// [NS == scan_resident] from resident_scalar_scan_from spheres on the sphere scan reads the table in memory (scalar loads): only the planes are staged
-			// (a build of its own, NP == 1: the scalar-load scan keeps two groups of four spheres in 32 scalar registers, which the
-			// LDS-scan build — scenes below the threshold — has for the frame's constants instead)
-			constexpr bool RESIDENT_SCALAR_SCAN = NS == scan_resident && NP == 1;
 			const bool spheres_in_lds = RESIDENT && !RESIDENT_SCALAR_SCAN;
 			const uint32_t lds_spheres = spheres_in_lds ? s.n_spheres : 0u;
-			constexpr bool BVH = NS == scan_bvh;
 			uint32_t table_float4s = NS > 0 ? small_table_float4s : (RESIDENT ? lds_spheres + s.n_planes : (NS == scan_tiled ? tile_primitives : (BVH ? bvh_stack_float4s : 0u)));
 			// [BOXES] the boxes' corners behind that table (launch_plan.cpp: at most box_max_count, and the whole within a workgroup's LDS)
 			float4* const lds_boxes = lds + table_float4s;
@@ -536,38 +179,24 @@ namespace rt_hip
 #ifdef RT_HIP_REGION_COUNTERS
 			uint32_t region_runs[device_counters::regions] = {}, region_lanes[device_counters::regions] = {};
 #endif
-			constexpr bool ROLLING = NS < 0 && !BVH;
-			// [PASS] where the two words of a pass travel (launch_queue_sm): the first chunk in q.block_items, which only the rolling kernels
-			// read; the accumulator in pixel_done's place, which only they have
-			const uint32_t first_chunk = PASS ? q.block_items : 0u;
-			float* const accum = PASS ? reinterpret_cast<float*>(pixel_done) : nullptr;
+			// what travels to this build in argument words it does not otherwise read.  (`PASS ? .. : 0`: where the build has no use for a word its
+			// name stays a constant, which no lambda below captures.)
+			const queue_words words = unpack_words<build>(q, item_sums, pixel_done);
+			const uint32_t first_chunk = PASS ? words.first_chunk : 0u;
+			float* const accum = PASS ? words.accum : nullptr;
 			// [BVH] the hierarchy, read once into scalar registers (its pointers and counts are the same for the whole launch)
 			device_bvh bvh{};
 			if constexpr (BVH)
-				bvh = *reinterpret_cast<const device_bvh*>(item_sums);
-			// [BOXTREE] ... and the boxes' hierarchy, whose descriptor lies behind it
+				bvh = *words.bvh;
+			// [BOXTREE] ... and the boxes' hierarchy
 			device_box_bvh box_tree{};
 			if constexpr (BOXTREE)
-				box_tree = *reinterpret_cast<const device_box_bvh*>(reinterpret_cast<const unsigned char*>(item_sums) + box_bvh_descriptor_offset);
-			// the camera form a scalar-register kernel is built for: the pinhole form, or (GC) the eye form.  A matrix without a
-			// finite eye (an orthographic frustum: nothing rt's camera can produce) takes the LDS-resident kernel, which carries all
-			// three forms — together with seven spheres their scalars do not fit the scalar registers, and hipcc then reloads the
-			// SPHERES from the argument block inside the loop (round 5: dielectric.toml through a tilted camera 3.85 ms).
-			// The LDS-resident kernel is built per scan, and its LDS-scan build per camera form too: as ONE kernel it carried the three camera
-			// forms' constants AND the scalar-load scan's two groups of four spheres (32 scalar registers), and its loop reloaded the frame's
-			// constants from the argument block (30 s_load and 35 v_readlane of spilled scalars per loop body).  NP == 0: the LDS scan (scenes
-			// below resident_scalar_scan_from spheres), GC = "the frame is not a pinhole's" (eye or homogeneous form, chosen at run time);
-			// NP == 1: the scalar-load scan, all forms at run time as before (split by form it gained nothing and lost 4 % through a tilted
-			// camera).  12 spheres 1.23 -> 1.15 ms, 32: 2.06 -> 2.01, basic.toml forced here 2.89 -> 2.72 (profiles/r05/resident_forms_ab.txt).
-			constexpr bool RESIDENT_LDS_SCAN = NS == scan_resident && NP == 0;
-			constexpr bool PINHOLE_ONLY = (NS > 0 || RESIDENT_LDS_SCAN) && !GC, EYE_ONLY = NS > 0 && GC, NEVER_PINHOLE = RESIDENT_LDS_SCAN && GC;
+				box_tree = *words.box_tree;
 			const uint32_t lane = threadIdx.x & 63u;
 			const uint32_t wave = threadIdx.x >> 6;
 			const uint32_t chunk_items = q.chunks << q.pixels_log2;	   // chunks of one pixel tile: P x K
 			const uint32_t items = HALF ? 2u * chunk_items : chunk_items; // work items of the tile
-			// chunk-sum slots of this wave's tile (one tile per wave; the rolling kernels keep no sums in LDS): 3 floats per
-			// chunk; HALF: 27 — the first half's partial sum, then the second half's eight sample values
-			constexpr uint32_t slot_floats = HALF ? half_chunk_slot_floats : 3u;
+			// chunk-sum slots of this wave's tile (one tile per wave; the rolling kernels keep no sums in LDS)
 			float* const slots = reinterpret_cast<float*>(lds + table_float4s) + static_cast<size_t>(wave) * chunk_items * slot_floats;
 			const uint32_t tile_w = 1u << q.tile_w_log2;
 			const uint32_t tile_h = (1u << q.pixels_log2) >> q.tile_w_log2;
@@ -582,15 +211,14 @@ namespace rt_hip
 			float* pass_sums = nullptr;
 			if constexpr (ADAPT)
 			{
-				const size_t frame_pixels = static_cast<size_t>(p.width) * p.height;
-				const uint32_t* const pixel_state = reinterpret_cast<const uint32_t*>(accum + 3u * frame_pixels);
-				pass_sums = accum + 4u * frame_pixels;
+				const adaptive_words adaptive = unpack_adaptive_words(accum, p);
+				pass_sums = adaptive.pass_sums;
 				const uint32_t lx = tile_x0 + (lane & (tile_w - 1u));
 				const uint32_t ly = tile_y0 + (lane >> q.tile_w_log2);
 				const bool in_frame = lane < (1u << q.pixels_log2) && lx < p.width && ly < p.local_rows;
 				bool stopped = false;
 				if (first_chunk && in_frame) // (the first pass reads nothing: every pixel is active)
-					stopped = (pixel_state[static_cast<size_t>(output_row(ly, p)) * p.width + lx] & 0x80000000u) != 0u;
+					stopped = (adaptive.pixel_state[static_cast<size_t>(output_row(ly, p)) * p.width + lx] & 0x80000000u) != 0u;
 				tile_stopped = __builtin_amdgcn_ballot_w64(stopped);
 				if ((__builtin_amdgcn_ballot_w64(in_frame) & ~tile_stopped) == 0) // nothing to trace, nothing to fold (no barrier follows in these kernels)
 					return;
@@ -612,9 +240,7 @@ namespace rt_hip
 #endif
 
 			lane_state st;
-			// path segments traced: counted on the scalar unit (one popcount of the tracing lanes per trip) where scalar
-			// registers are to spare — the 1..4-sphere kernels; 2 more live SGPRs make the others spill — else per lane
-			constexpr bool SCALAR_SEGMENTS = NS >= 1 && NS + NP <= 4;
+			// path segments traced: on the scalar unit (SCALAR_SEGMENTS) or per lane
 			unsigned long long wave_segments = 0;
 			uint32_t lane_segments = 0;
 			uint32_t slot = 0; // chunk-sum slot of the item in flight on this lane; rolling: its pixel's place in the hand-out order
@@ -822,7 +448,6 @@ namespace rt_hip
 			// on to the next sample of the item in flight; false = that was the last one.  The lane's stream moves to the next
 			// sample's window (a restarting lane has no other use for its position).  The kernels that look at a sample's INDEX
 			// (half chunks park by it, rolling items publish by it) count indices; the others count windows only.
-			constexpr bool INDEXED = HALF || ROLLING;
 			const auto next_sample = [&]() -> bool
 			{
 #ifdef RT_HIP_FAST_BUILD
@@ -1179,28 +804,7 @@ namespace rt_hip
 						return; // (the lane stays free and asks again)
 					const uint32_t gy = global_row(ly, p);
 					st.chunk_sum = { 0.0f, 0.0f, 0.0f };
-					{
-						const float fx = static_cast<float>(lx), fy = static_cast<float>(gy);
-						if (PINHOLE_ONLY || (!EYE_ONLY && !NEVER_PINHOLE && p.pinhole)) // (wave-uniform: a kernel argument)
-						{
-							st.base_x = fma(p.ray_d1[0], fx, fma(p.ray_d2[0], fy, p.ray_d0[0]));
-							st.base_y = fma(p.ray_d1[1], fx, fma(p.ray_d2[1], fy, p.ray_d0[1]));
-							st.base_z = fma(p.ray_d1[2], fx, fma(p.ray_d2[2], fy, p.ray_d0[2]));
-							st.base_w = 0.0f;
-						}
-						else if (EYE_ONLY || p.eye_form) // (wave-uniform)
-						{
-							st.base_x = fma(p.eye_q1[0], fx, fma(p.eye_q2[0], fy, p.eye_q0[0]));
-							st.base_y = fma(p.eye_q1[1], fx, fma(p.eye_q2[1], fy, p.eye_q0[1]));
-							st.base_z = fma(p.eye_q1[2], fx, fma(p.eye_q2[2], fy, p.eye_q0[2]));
-							st.base_w = fma(p.eye_w1, fx, fma(p.eye_w2, fy, p.eye_w0));
-						}
-						else
-						{
-							st.base_x = fx, st.base_y = fy;
-							st.base_z = st.base_w = 0.0f;
-						}
-					}
+					camera_base<build>(st, p, static_cast<float>(lx), static_cast<float>(gy));
 					st.keys.function_key = pixel_function_key(p.frame_key_a, gy * p.width + lx); // image_view::position_of, image.hpp:155-159
 					st.keys.stride = pixel_stride(p.frame_key_b, st.keys.function_key);
 					const uint32_t first = (PASS ? first_chunk + chunk : chunk) * item_samples, end = min(first + item_samples, p.samples_per_pixel);
@@ -1703,184 +1307,181 @@ namespace rt_hip
 
 #endif // !RT_HIP_FAST_BUILD
 
-		// what launch_render was called with, on its way to the instantiation the plan names
-		struct launch_arguments
-		{
-			const frame_params& frame;
-			const device_scene& scene;
-			const small_scene& small;
-			const launch_plan& plan;
-			uint32_t* d_rgba8;
-			float* d_rgb_f32;
-			device_counters* d_counters;
-			const rolling_buffers& rolling;
-			uint32_t compute_units;
-			launch_cache& cache;
-			hipStream_t stream;
-		};
+		// ---- the dispatch: from a plan's kernel_build to the instantiation of render_queue it names -------------------------------
+		// Every instantiation has one signature, so the selection RETURNS the kernel and launch_render launches through the pointer.
+		// Two things here are deliberate beyond the mapping itself.  Which build reads which aliased argument word is pack_words'
+		// business, not the selection's (kernels.hpp, rolling_buffers).  And a kernel's place in the code object follows the order in which
+		// this code first names the instantiations — DESIGN.md §3.12 has that place as a suspect for effects of microseconds — so the
+		// order of mention below is part of what the listings check (tools/kernel_listing_diff.py compares text; the sequence of
+		// .amdhsa_kernel lines is compared next to it): the table kernels are reached through as many templates as the scalar-register
+		// ones, and build_of names a scan's plain builds first.
+		using queue_kernel = decltype(&render_queue<1, false>);
 
-		template <int NS, bool SM, int NP = 0, bool GC = false>
-		void launch_queue_sm(const launch_arguments& a)
+		// the build of scan NS (NS spheres in scalar registers, or scan_*) under one scatter table: plain, sub-chunk items, or — the two
+		// tile-per-wave table scans of the parity build — its box / box-tree / light / adaptive / pass build, in the plan's and the API's
+		// order of precedence (boxes: whole chunks, never a pass; lights: never with boxes; adaptive implies pass)
+		template <int NS, bool SM, int NP, bool GC>
+		queue_kernel build_of(const kernel_build& build)
 		{
-			const launch_plan& plan = a.plan;
-			dim3 grid(plan.grid_x, plan.grid_y); // small scenes: the grid of tiles; big scenes: x = the most workgroups the items can occupy
-			if (scan_is_persistent(NS))
-			{
-				// persistent launch: exactly what the device keeps resident (surplus workgroups would only find the queue dry).
-				// The answer is remembered per context (= per device and host thread of use), per kernel and LDS size.
-				launch_cache::entry& known = a.cache.persistent[plan.persistent_slot];
-				if (known.lds_bytes != plan.lds_bytes || known.per_cu < 1)
-				{
-					int per_cu = 0;
-					hipError_t asked;
-					if constexpr (!SM)
-						asked = plan.build.sub_chunk_items ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, render_queue<NS, SM, true>, static_cast<int>(block_threads), plan.lds_bytes)
-														   : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, render_queue<NS, SM, false>, static_cast<int>(block_threads), plan.lds_bytes); // (persistent kernels: never with scalar-register planes)
-					else
-						asked = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, render_queue<NS, SM>, static_cast<int>(block_threads), plan.lds_bytes);
-					if (asked != hipSuccess || per_cu < 1)
-						per_cu = 4;
-					// Not more workgroups than the kernels were compiled for (5 waves per SIMD = 5 workgroups per CU), even when the
-					// register allocation of a build happens to leave room for a sixth (round 4 saw 6 144 waves instead of 5 120
-					// on one build): the launch's shape should not depend on that.  Measured, it makes no difference either way
-					// (config 5: 5.479 against 5.476 s, profiles/r04/persistent_waves_ab.txt).
-					per_cu = std::min(per_cu, plan.per_cu_cap);
-					(void)hipGetLastError();
-					known.lds_bytes = plan.lds_bytes;
-					known.per_cu = per_cu;
-				}
-				grid = dim3(std::min(grid.x, a.compute_units * static_cast<uint32_t>(known.per_cu)));
-			}
-			// (the BVH kernel takes its hierarchy's descriptor in the item_sums argument's place)
-			unsigned long long* const item_sums = NS == scan_bvh ? reinterpret_cast<unsigned long long*>(const_cast<device_bvh*>(a.rolling.bvh)) : a.rolling.item_sums;
+			// (the scan's plain builds, named first: see above)
+			[[maybe_unused]] constexpr queue_kernel plain[] = { render_queue<NS, SM, !SM>, render_queue<NS, SM, false> };
 #ifndef RT_HIP_FAST_BUILD
 			if constexpr (NS == scan_resident || NS == scan_bvh)
 			{
-				if (plan.build.boxes) // (RT_HIP_FLAG_TRACE_BOXES with at least one box: whole chunks, never a pass — the plan's and the API's rules)
+				constexpr bool tree = NS == scan_bvh;
+				if (build.boxes)
 				{
-					if constexpr (NS == scan_bvh)
-						if (plan.build.box_tree) // (RT_HIP_FLAG_BOX_BVH: rolling.bvh is then the pair of descriptors, render.hip)
-						{
-							hipLaunchKernelGGL((render_queue<scan_bvh_boxtree, SM, false, NP, GC>), grid, dim3(block_threads), plan.lds_bytes, a.stream, a.frame, plan.queue, a.small, a.scene, a.scene.primitive_geometry, a.d_rgba8, a.d_rgb_f32, a.d_counters,
-											   item_sums, a.rolling.pixel_done);
-							return;
-						}
-					constexpr int box_scan = NS == scan_bvh ? scan_bvh_boxes : scan_resident_boxes;
-					hipLaunchKernelGGL((render_queue<box_scan, SM, false, NP, GC>), grid, dim3(block_threads), plan.lds_bytes, a.stream, a.frame, plan.queue, a.small, a.scene, a.scene.primitive_geometry, a.d_rgba8, a.d_rgb_f32, a.d_counters, item_sums,
-									   a.rolling.pixel_done);
-					return;
+					if constexpr (tree)
+						if (build.box_tree)
+							return render_queue<scan_bvh_boxtree, SM, false, NP, GC>;
+					return render_queue<tree ? scan_bvh_boxes : scan_resident_boxes, SM, false, NP, GC>;
 				}
-				if (plan.build.lights) // (RT_HIP_FLAG_EMISSION with at least one light: whole chunks, never a pass, never with boxes — the plan's and the API's rules;
-									   // a.scene is the copy whose per-primitive shading / scatter pointers are the light variant's, render.hip)
-				{
-					constexpr int light_scan = NS == scan_bvh ? scan_bvh_lights : scan_resident_lights;
-					hipLaunchKernelGGL((render_queue<light_scan, SM, false, NP, GC>), grid, dim3(block_threads), plan.lds_bytes, a.stream, a.frame, plan.queue, a.small, a.scene, a.scene.primitive_geometry, a.d_rgba8, a.d_rgb_f32, a.d_counters, item_sums,
-									   a.rolling.pixel_done);
-					return;
-				}
-				if (plan.build.adaptive) // (an adaptive pass: as the pass below; rolling.accum is the block of accumulator, state words, pass sums and moments)
-				{
-					constexpr int adapt_scan = NS == scan_bvh ? scan_bvh_adapt : scan_resident_adapt;
-					queue_params queue = plan.queue;
-					queue.block_items = plan.first_chunk;
-					hipLaunchKernelGGL((render_queue<adapt_scan, SM, false, NP, GC>), grid, dim3(block_threads), plan.lds_bytes, a.stream, a.frame, queue, a.small, a.scene, a.scene.primitive_geometry, a.d_rgba8, a.d_rgb_f32, a.d_counters, item_sums,
-									   reinterpret_cast<uint32_t*>(a.rolling.accum));
-					return;
-				}
-				if (plan.build.pass) // (a pass of a progressive frame: first_chunk and the accumulator in the words these kernels do not read)
-				{
-					constexpr int pass_scan = NS == scan_bvh ? scan_bvh_pass : scan_resident_pass;
-					queue_params queue = plan.queue;
-					queue.block_items = plan.first_chunk;
-					hipLaunchKernelGGL((render_queue<pass_scan, SM, false, NP, GC>), grid, dim3(block_threads), plan.lds_bytes, a.stream, a.frame, queue, a.small, a.scene, a.scene.primitive_geometry, a.d_rgba8, a.d_rgb_f32, a.d_counters, item_sums,
-									   reinterpret_cast<uint32_t*>(a.rolling.accum));
-					return;
-				}
+				if (build.lights)
+					return render_queue<tree ? scan_bvh_lights : scan_resident_lights, SM, false, NP, GC>;
+				if (build.adaptive)
+					return render_queue<tree ? scan_bvh_adapt : scan_resident_adapt, SM, false, NP, GC>;
+				if (build.pass)
+					return render_queue<tree ? scan_bvh_pass : scan_resident_pass, SM, false, NP, GC>;
 			}
 #endif
 			if constexpr (!SM) // (the sm table keeps whole chunks: one set of kernels fewer to build)
-			{
-				if (plan.build.sub_chunk_items)
-				{
-					hipLaunchKernelGGL((render_queue<NS, SM, true, NP, GC>), grid, dim3(block_threads), plan.lds_bytes, a.stream, a.frame, plan.queue, a.small, a.scene, a.scene.primitive_geometry, a.d_rgba8, a.d_rgb_f32, a.d_counters, item_sums, a.rolling.pixel_done);
-					return;
-				}
-			}
-			hipLaunchKernelGGL((render_queue<NS, SM, false, NP, GC>), grid, dim3(block_threads), plan.lds_bytes, a.stream, a.frame, plan.queue, a.small, a.scene, a.scene.primitive_geometry, a.d_rgba8, a.d_rgb_f32, a.d_counters, item_sums, a.rolling.pixel_done);
+				if (build.sub_chunk_items)
+					return render_queue<NS, SM, true, NP, GC>;
+			return render_queue<NS, SM, false, NP, GC>;
 		}
 
 		template <int NS, int NP = 0, bool GC = false>
-		void launch_queue(const launch_arguments& a)
+		queue_kernel table_of(const kernel_build& build)
 		{
 #ifndef RT_HIP_FAST_BUILD // (the API refuses RT_HIP_FLAG_FAST together with RT_HIP_FLAG_SM_MATERIALS)
-			if (a.plan.build.sm_table)
-				launch_queue_sm<NS, true, NP, GC>(a);
-			else
+			if (build.sm_table)
+				return build_of<NS, true, NP, GC>(build);
 #endif
-				launch_queue_sm<NS, false, NP, GC>(a);
+			return build_of<NS, false, NP, GC>(build);
+		}
+
+		// the scalar-register builds there are: (spheres, planes) with spheres + planes <= scalar_max_spheres, planes <= scalar_max_planes
+		// (choose_kernel admits no others), each for the eye form (GC) and for the pinhole
+		struct small_builds
+		{
+			int spheres, planes;
+			queue_kernel (*general_camera)(const kernel_build&);
+			queue_kernel (*pinhole)(const kernel_build&);
+		};
+		constexpr small_builds small_kernels[] = {
+			{ 1, 0, table_of<1, 0, true>, table_of<1, 0, false> },
+			{ 2, 0, table_of<2, 0, true>, table_of<2, 0, false> },
+			{ 3, 0, table_of<3, 0, true>, table_of<3, 0, false> },
+			{ 4, 0, table_of<4, 0, true>, table_of<4, 0, false> },
+			{ 5, 0, table_of<5, 0, true>, table_of<5, 0, false> },
+			{ 6, 0, table_of<6, 0, true>, table_of<6, 0, false> },
+			{ 7, 0, table_of<7, 0, true>, table_of<7, 0, false> },
+			{ 8, 0, table_of<8, 0, true>, table_of<8, 0, false> },
+			{ 1, 1, table_of<1, 1, true>, table_of<1, 1, false> },
+			{ 2, 1, table_of<2, 1, true>, table_of<2, 1, false> },
+			{ 3, 1, table_of<3, 1, true>, table_of<3, 1, false> },
+			{ 4, 1, table_of<4, 1, true>, table_of<4, 1, false> },
+			{ 5, 1, table_of<5, 1, true>, table_of<5, 1, false> },
+			{ 6, 1, table_of<6, 1, true>, table_of<6, 1, false> },
+			{ 7, 1, table_of<7, 1, true>, table_of<7, 1, false> },
+			{ 1, 2, table_of<1, 2, true>, table_of<1, 2, false> },
+			{ 2, 2, table_of<2, 2, true>, table_of<2, 2, false> },
+			{ 3, 2, table_of<3, 2, true>, table_of<3, 2, false> },
+			{ 4, 2, table_of<4, 2, true>, table_of<4, 2, false> },
+			{ 5, 2, table_of<5, 2, true>, table_of<5, 2, false> },
+			{ 6, 2, table_of<6, 2, true>, table_of<6, 2, false> },
+			{ 1, 3, table_of<1, 3, true>, table_of<1, 3, false> },
+			{ 2, 3, table_of<2, 3, true>, table_of<2, 3, false> },
+			{ 3, 3, table_of<3, 3, true>, table_of<3, 3, false> },
+			{ 4, 3, table_of<4, 3, true>, table_of<4, 3, false> },
+			{ 5, 3, table_of<5, 3, true>, table_of<5, 3, false> },
+		};
+
+		// the instantiation `build` names; nullptr for a scalar-register build that does not exist (nothing is launched then)
+		queue_kernel select_kernel(const kernel_build& build)
+		{
+			if (build.scan > 0) // the scalar-register kernels: build.scan spheres, then build.planes planes
+			{
+				const int spheres = std::min(build.scan, static_cast<int>(scalar_max_spheres)), planes = std::min(build.planes, static_cast<int>(scalar_max_planes));
+				for (const small_builds& known : small_kernels)
+					if (known.spheres == spheres && known.planes == planes)
+						return build.general_camera ? known.general_camera(build) : known.pinhole(build);
+				return nullptr;
+			}
+			switch (build.scan)
+			{
+#ifndef RT_HIP_FAST_BUILD // (the API refuses RT_HIP_FLAG_FAST together with RT_HIP_FLAG_BVH)
+				case scan_bvh: return table_of<scan_bvh>(build);
+#endif
+				case scan_resident:
+					if (build.planes) // (the scalar-load scan: one build for every camera form)
+						return table_of<scan_resident, 1, false>(build);
+					return build.general_camera ? table_of<scan_resident, 0, true>(build) : table_of<scan_resident, 0, false>(build);
+				case scan_streamed_dense: return table_of<scan_streamed_dense>(build);
+				case scan_streamed: return table_of<scan_streamed>(build);
+				default: return table_of<scan_tiled>(build);
+			}
+		}
+
+		// the aliased argument words of a launch, packed as the builds read them (the contract: kernels.hpp, rolling_buffers; the device's
+		// side: queue_build.hpp, unpack_words)
+		struct kernel_words
+		{
+			queue_params queue;			   // block_items: [pass builds] the pass's first chunk
+			unsigned long long* item_sums; // [scan_bvh and its builds] the hierarchy's descriptor(s)
+			uint32_t* pixel_done;		   // [pass builds] the accumulator (adaptive: the block that starts with it)
+		};
+		kernel_words pack_words(const rolling_buffers& rolling, const launch_plan& plan)
+		{
+			const kernel_build& build = plan.build;
+			kernel_words words = { plan.queue, rolling.item_sums, rolling.pixel_done };
+			if (build.scan == scan_bvh)
+				words.item_sums = reinterpret_cast<unsigned long long*>(const_cast<device_bvh*>(rolling.bvh));
+#ifndef RT_HIP_FAST_BUILD
+			// (the pass builds, as build_of selects them)
+			if ((build.scan == scan_resident || build.scan == scan_bvh) && !build.boxes && !build.lights && (build.adaptive || build.pass))
+			{
+				words.queue.block_items = plan.first_chunk;
+				words.pixel_done = reinterpret_cast<uint32_t*>(rolling.accum);
+			}
+#endif
+			return words;
 		}
 	}
 
 	// picks the instantiation plan.build names and launches it: every decision is the plan's (launch_plan.hpp)
-	uint32_t launch_render(const frame_params& frame,
-						   const device_scene& scene,
-						   const small_scene& small,
-						   const launch_plan& plan,
-						   uint32_t* d_rgba8,
-						   float* d_rgb_f32,
-						   device_counters* d_counters,
-						   const rolling_buffers& rolling,
-						   uint32_t compute_units,
-						   launch_cache& cache,
-						   hipStream_t stream)
+	uint32_t launch_render(const launch_arguments& a)
 	{
+		const launch_plan& plan = a.plan;
 		if (plan.variant == RT_HIP_KERNEL_NONE)
 			return RT_HIP_KERNEL_NONE;
-		const launch_arguments a = { frame, scene, small, plan, d_rgba8, d_rgb_f32, d_counters, rolling, compute_units, cache, stream };
-		const kernel_build& build = plan.build;
-		if (build.scan > 0) // the scalar-register kernels: build.scan spheres, then build.planes planes
-		{
-#define RT_HIP_LAUNCH_SMALL(N, P) (build.general_camera ? launch_queue<N, P, true>(a) : launch_queue<N, P, false>(a))
-#define RT_HIP_LAUNCH_SMALL_SPHERES(P, N_MAX)                                                                                        \
-	switch (build.scan)                                                                                                              \
-	{                                                                                                                                \
-		case 1: RT_HIP_LAUNCH_SMALL(1, P); break;                                                                                    \
-		case 2: RT_HIP_LAUNCH_SMALL(2, P); break;                                                                                    \
-		case 3: RT_HIP_LAUNCH_SMALL(3, P); break;                                                                                    \
-		case 4: RT_HIP_LAUNCH_SMALL(4, P); break;                                                                                    \
-		case 5: RT_HIP_LAUNCH_SMALL(5, P); break;                                                                                    \
-		case 6: if constexpr (N_MAX >= 6) RT_HIP_LAUNCH_SMALL(6, P); break;                                                          \
-		case 7: if constexpr (N_MAX >= 7) RT_HIP_LAUNCH_SMALL(7, P); break;                                                          \
-		default: if constexpr (N_MAX >= 8) RT_HIP_LAUNCH_SMALL(8, P); break;                                                         \
-	}
-			switch (build.planes) // (choose_kernel admits n_spheres + n_planes <= 8 only)
-			{
-				case 0: RT_HIP_LAUNCH_SMALL_SPHERES(0, 8); break;
-				case 1: RT_HIP_LAUNCH_SMALL_SPHERES(1, 7); break;
-				case 2: RT_HIP_LAUNCH_SMALL_SPHERES(2, 6); break;
-				default: RT_HIP_LAUNCH_SMALL_SPHERES(3, 5); break;
-			}
-#undef RT_HIP_LAUNCH_SMALL_SPHERES
-#undef RT_HIP_LAUNCH_SMALL
+		const queue_kernel kernel = select_kernel(plan.build);
+		if (!kernel)
 			return plan.variant;
-		}
-		switch (build.scan)
+		dim3 grid(plan.grid_x, plan.grid_y); // small scenes: the grid of tiles; big scenes: x = the most workgroups the items can occupy
+		if (scan_is_persistent(plan.build.scan))
 		{
-#ifndef RT_HIP_FAST_BUILD // (the API refuses RT_HIP_FLAG_FAST together with RT_HIP_FLAG_BVH)
-			case scan_bvh: launch_queue<scan_bvh>(a); break;
-#endif
-			case scan_resident:
-				if (build.planes) // (the scalar-load scan: one build for every camera form)
-					launch_queue<scan_resident, 1, false>(a);
-				else if (build.general_camera)
-					launch_queue<scan_resident, 0, true>(a);
-				else
-					launch_queue<scan_resident, 0, false>(a);
-				break;
-			case scan_streamed_dense: launch_queue<scan_streamed_dense>(a); break;
-			case scan_streamed: launch_queue<scan_streamed>(a); break;
-			default: launch_queue<scan_tiled>(a); break;
+			// persistent launch: exactly what the device keeps resident (surplus workgroups would only find the queue dry).
+			// The answer is remembered per context (= per device and host thread of use), per kernel and LDS size.
+			launch_cache::entry& known = a.cache.persistent[plan.persistent_slot];
+			if (known.lds_bytes != plan.lds_bytes || known.per_cu < 1)
+			{
+				int per_cu = 0;
+				if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, static_cast<int>(block_threads), plan.lds_bytes) != hipSuccess || per_cu < 1)
+					per_cu = 4;
+				// Not more workgroups than the kernels were compiled for (5 waves per SIMD = 5 workgroups per CU), even when the
+				// register allocation of a build happens to leave room for a sixth (round 4 saw 6 144 waves instead of 5 120
+				// on one build): the launch's shape should not depend on that.  Measured, it makes no difference either way
+				// (config 5: 5.479 against 5.476 s, profiles/r04/persistent_waves_ab.txt).
+				per_cu = std::min(per_cu, plan.per_cu_cap);
+				(void)hipGetLastError();
+				known.lds_bytes = plan.lds_bytes;
+				known.per_cu = per_cu;
+			}
+			grid = dim3(std::min(grid.x, a.compute_units * static_cast<uint32_t>(known.per_cu)));
 		}
+		const kernel_words words = pack_words(a.rolling, plan);
+		hipLaunchKernelGGL(kernel, grid, dim3(block_threads), plan.lds_bytes, a.stream, a.frame, words.queue, a.small, a.scene, a.scene.primitive_geometry, a.d_rgba8, a.d_rgb_f32, a.d_counters, words.item_sums, words.pixel_done);
 		return plan.variant;
 	}
 

@@ -82,21 +82,31 @@ namespace rt_hip
 		uint32_t scatter[scalar_max_spheres]; // scatter_*
 	};
 
-	// What the big-scene kernels exchange chunk sums through (owned by the context, grown on demand):
-	//   item_sums   16 bytes per item of this rank's rows (a chunk sum on its way to the lane that folds the pixel);
-	//               not needed when a pixel is one chunk.  With sub-chunk items: 16 bytes per SAMPLE
-	//   pixel_done  one arrival counter per pixel; zeroed on the launch's own stream in front of every launch (render.hip)
+	// What the big-scene kernels exchange chunk sums through (owned by the context, grown on demand), and what the other builds are handed
+	// in the same two kernel arguments — render_queue has ONE argument block, which no build changes by a byte, so a value only some builds
+	// need travels in a word those builds do not otherwise read.  WHICH BUILD READS WHICH WORD, the whole contract (packed on the host by
+	// pack_words, kernels.hip; unpacked on the device by unpack_words, queue_build.hpp — nothing else casts these words):
+	//   argument `item_sums`    rolling builds (scan_tiled, scan_streamed, scan_streamed_dense): item_sums.  scan_bvh and its pass / box /
+	//                           light builds: `bvh`; scan_bvh_boxtree reads the box hierarchy's descriptor box_bvh_descriptor_offset bytes
+	//                           behind it (box_bvh_scan.hpp).  Every other build: not read.
+	//   argument `pixel_done`   rolling builds: pixel_done.  Pass and adaptive builds (scan_*_pass, scan_*_adapt): `accum`; the adaptive
+	//                           builds find their state words and pass sums behind it (rt_hip.h, rt_hip_adaptive_pass_device).  Every
+	//                           other build: not read.
+	//   queue_params::block_items   rolling builds: items a wave draws at a time.  Pass and adaptive builds: launch_plan::first_chunk.
+	//                           Every other build: not read.
 	struct rolling_buffers
 	{
+		// 16 bytes per item of this rank's rows (a chunk sum on its way to the lane that folds the pixel); not needed when a pixel is one
+		// chunk.  With sub-chunk items: 16 bytes per SAMPLE
 		unsigned long long* item_sums = nullptr;
+		// one arrival counter per pixel; zeroed on the launch's own stream in front of every launch (render.hip)
 		uint32_t* pixel_done = nullptr;
-		// RT_HIP_FLAG_BVH: the hierarchy's descriptor in device memory.  The BVH kernel keeps no sums in HBM; it is handed this in
-		// the item_sums argument's place (render_queue), so that no kernel's argument block changes.
+		// RT_HIP_FLAG_BVH: the hierarchy's descriptor in device memory (the BVH kernel keeps no sums in HBM); under RT_HIP_FLAG_BOX_BVH the
+		// pair of descriptors (render.hip)
 		const device_bvh* bvh = nullptr;
-		// A pass of a progressive frame (launch_plan::build.pass; render_queue<scan_*_pass, ..>): the pixels' running sums, 3 floats per pixel laid out
-		// like the float mean.  The pass builds are tile-per-wave kernels, which have no arrival counters: the accumulator is handed over in
-		// the pixel_done argument's place, and the pass's first chunk in queue_params::block_items, a word only the rolling kernels read —
-		// again no kernel's argument block changes.
+		// A pass of a progressive frame (launch_plan::build.pass; render_queue<scan_*_pass, ..>): the pixels' running sums, 3 floats per pixel
+		// laid out like the float mean (the pass builds are tile-per-wave kernels, which have no arrival counters); an adaptive pass: the
+		// block of accumulator, state words, pass sums and moments
 		float* accum = nullptr;
 	};
 
@@ -135,32 +145,27 @@ namespace rt_hip
 		entry persistent[persistent_cache_slots]; // indexed by launch_plan::persistent_slot
 	};
 
-	// launches what `plan` says (plan_launch, made by the caller, who has prepared the buffers from the same plan); returns the
-	// kernel variant launched (RT_HIP_KERNEL_*)
-	uint32_t launch_render(const frame_params& frame,
-						   const device_scene& scene,
-						   const small_scene& small, // valid when the plan's variant is RT_HIP_KERNEL_SMALL; tables already chosen by flag
-						   const launch_plan& plan,
-						   uint32_t* d_rgba8,
-						   float* d_rgb_f32,
-						   device_counters* d_counters,
-						   const rolling_buffers& rolling, // big scenes: sized as the plan says, pixel_done zeroed in front of the launch
-						   uint32_t compute_units, // of the device: the big-scene kernels are launched persistent
-						   launch_cache& cache,
-						   hipStream_t stream);
+	// what a render launch is made of: the caller has made `plan` (plan_launch) and prepared the buffers from the same plan
+	struct launch_arguments
+	{
+		const frame_params& frame;
+		const device_scene& scene; // (the light builds: a copy whose per-primitive shading / scatter pointers are the light variant's, render.hip)
+		const small_scene& small;  // valid when the plan's variant is RT_HIP_KERNEL_SMALL; tables already chosen by flag
+		const launch_plan& plan;
+		uint32_t* d_rgba8;
+		float* d_rgb_f32;
+		device_counters* d_counters;
+		const rolling_buffers& rolling; // big scenes: sized as the plan says, pixel_done zeroed in front of the launch
+		uint32_t compute_units;			// of the device: the big-scene kernels are launched persistent
+		launch_cache& cache;
+		hipStream_t stream;
+	};
+
+	// launches what the plan says; returns the kernel variant launched (RT_HIP_KERNEL_*)
+	uint32_t launch_render(const launch_arguments& a);
 
 	// the same with RT_HIP_FLAG_FAST's arithmetic (kernels.hip built with RT_HIP_FAST_BUILD); mg scatter table only
-	uint32_t launch_render_fast(const frame_params& frame,
-								const device_scene& scene,
-								const small_scene& small,
-								const launch_plan& plan,
-								uint32_t* d_rgba8,
-								float* d_rgb_f32,
-								device_counters* d_counters,
-								const rolling_buffers& rolling,
-								uint32_t compute_units,
-								launch_cache& cache,
-								hipStream_t stream);
+	uint32_t launch_render_fast(const launch_arguments& a);
 
 	// RT_HIP_FLAG_PREVIEW: one ray per pixel, reference src/renderers/rasterizer.cpp:24-85
 	void launch_preview(const frame_params& frame, const device_scene& scene, uint32_t* d_rgba8, float* d_rgb_f32, device_counters* d_counters, hipStream_t stream);

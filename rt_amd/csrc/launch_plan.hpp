@@ -17,7 +17,7 @@
 #define RT_HIP_WAVES_DENSE 6
 #endif
 #ifndef RT_HIP_PERSISTENT_WAVES_CAP
-#define RT_HIP_PERSISTENT_WAVES_CAP 5 // workgroups per CU of the persistent (big-scene) launches: see launch_queue_sm
+#define RT_HIP_PERSISTENT_WAVES_CAP 5 // workgroups per CU of the persistent (big-scene) launches: see launch_render
 #endif
 
 namespace rt_hip
@@ -206,7 +206,7 @@ namespace rt_hip
 		bool big_scene;	  // a rolling kernel (tiled / streamed): items drawn from device_counters::next_item, which must start at 0
 		queue_params queue;
 		kernel_build build;
-		uint32_t grid_x, grid_y; // workgroups; a persistent launch is capped to what the device keeps resident at launch (launch_queue_sm)
+		uint32_t grid_x, grid_y; // workgroups; a persistent launch is capped to what the device keeps resident at launch (launch_render)
 		size_t table_bytes;		 // LDS: the primitive tables / the tiled kernel's tile / the BVH kernel's stacks ...
 		size_t slot_bytes;		 // ... and the chunk-sum slots of the workgroup's four tiles (small scenes)
 		size_t lds_bytes;		 // = table_bytes + slot_bytes

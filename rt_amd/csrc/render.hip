@@ -193,17 +193,17 @@ rt_hip_status render_device(rt_hip_ctx* ctx, uint32_t width, uint32_t height, ui
 	if (flags & RT_HIP_FLAG_PREVIEW)
 		launch_preview(f, ctx->scene, d_rgba8, d_rgb_f32, counters, s);
 	else if (flags & RT_HIP_FLAG_FAST)
-		variant = launch_render_fast(f, ctx->scene, ctx->small, plan, d_rgba8, d_rgb_f32, counters, rolling, ctx->compute_units, ctx->cache, s);
+		variant = launch_render_fast({ f, ctx->scene, ctx->small, plan, d_rgba8, d_rgb_f32, counters, rolling, ctx->compute_units, ctx->cache, s });
 	else if (plan.build.lights)
 	{
 		// the light builds read the SAME device_scene words: a copy whose four per-primitive shading / scatter pointers point at the light variant
 		device_scene lit = ctx->scene;
 		lit.primitive_shading = ctx->light_shading, lit.primitive_scatter = ctx->light_scatter;
 		lit.primitive_shading_sm = ctx->light_shading_sm, lit.primitive_scatter_sm = ctx->light_scatter_sm;
-		variant = launch_render(f, lit, (flags & RT_HIP_FLAG_SM_MATERIALS) ? ctx->small_sm : ctx->small, plan, d_rgba8, d_rgb_f32, counters, rolling, ctx->compute_units, ctx->cache, s);
+		variant = launch_render({ f, lit, (flags & RT_HIP_FLAG_SM_MATERIALS) ? ctx->small_sm : ctx->small, plan, d_rgba8, d_rgb_f32, counters, rolling, ctx->compute_units, ctx->cache, s });
 	}
 	else
-		variant = launch_render(f, ctx->scene, (flags & RT_HIP_FLAG_SM_MATERIALS) ? ctx->small_sm : ctx->small, plan, d_rgba8, d_rgb_f32, counters, rolling, ctx->compute_units, ctx->cache, s);
+		variant = launch_render({ f, ctx->scene, (flags & RT_HIP_FLAG_SM_MATERIALS) ? ctx->small_sm : ctx->small, plan, d_rgba8, d_rgb_f32, counters, rolling, ctx->compute_units, ctx->cache, s });
 	RT_HIP_TRY(hipGetLastError());
 	ctx->launched = true;
 	ctx->last_stream = s;

@@ -35,7 +35,7 @@ int main()
 			continue;
 		}
 		const queue_params& q = p.queue;
-		// (launch_queue_sm, kernels.hip: the box tree before the box builds before the pass builds)
+		// (build_of, kernels.hip: the box tree before the box builds before the pass builds)
 		const bool tile_per_wave = p.build.scan == scan_resident || p.build.scan == scan_bvh;
 		const int build = !tile_per_wave ? p.build.scan
 						  : p.build.box_tree ? static_cast<int>(scan_bvh_boxtree)

@@ -360,7 +360,7 @@ def test_random_scenes_are_bit_exact(tracer, case):
 
 def test_a_published_sum_keeps_its_value_until_the_store_has_read_it(tracer):
     """Regression pin (profiles/r04/case0_bisect.txt).  The rolling kernels hand a chunk sum to another wave with ONE
-    hand-written `global_store_dwordx4 ... sc1` (kernels.hip publish_sum).  A VMEM store of more than 64 bits reads its data
+    hand-written `global_store_dwordx4 ... sc1` (handover.hpp publish_sum).  A VMEM store of more than 64 bits reads its data
     registers AFTER issue; the compiler pads its own stores against the gfx940+ "VMEM store data hazard", but cannot see into
     inline assembly: in round 4 the sm kernels' next instruction recycled the value's upper half for an address and z arrived
     as a pointer's low word — on exactly this scene (case 0 of the random scenes: 3 spheres, 1 plane, 59 x 68, 32 spp = two

@@ -4,7 +4,7 @@
 
 The scene of a row: a ground sphere, `spheres - 1` small ones in front of the camera (a third of them metal), `planes` planes
 (a floor just under the ground sphere's top, then walls behind and beside).  One process per library, min of <frames> kernel
-times (HIP events).  Used to pick, per build, the waves-per-SIMD budget and the probe group size (kernels.hip): which build
+times (HIP events).  Used to pick, per build, the waves-per-SIMD budget and the probe group size (queue_build.hpp, kernels.hip): which build
 spills how much moves with every change of the source (tools/kernel_registers.py)."""
 import os, subprocess, sys
 w, h, spp, frames = (int(v) for v in sys.argv[1:5])
