@@ -17,7 +17,7 @@ HIPFLAGS += -fvisibility=hidden
 # basic + plane 2.74 -> 2.62, tilted camera 2.80 -> 2.62 (profiles/r05/codegen_ab.txt).
 HIPFLAGS += -fno-slp-vectorize
 API_UNITS := context scene frame render passes multi group denoise temporal adaptive
-HIP_HDR  := rt_amd/csrc/kernels.hpp rt_amd/csrc/launch_plan.hpp rt_amd/csrc/progressive.hpp rt_amd/csrc/denoise.hpp rt_amd/csrc/denoise_rules.hpp rt_amd/csrc/temporal.hpp rt_amd/csrc/reproject_rules.hpp rt_amd/csrc/adaptive.hpp rt_amd/csrc/adaptive_rules.hpp rt_amd/csrc/lights.hpp rt_amd/csrc/centre_ray.hpp rt_amd/csrc/frame_setup.hpp rt_amd/csrc/contract.hpp rt_amd/csrc/scan.hpp rt_amd/csrc/bvh_scan.hpp rt_amd/csrc/bvh.hpp rt_amd/csrc/box_bvh.hpp rt_amd/csrc/box_bvh_scan.hpp rt_amd/csrc/scan_streamed.hpp rt_amd/csrc/handover.hpp rt_amd/csrc/pixel_output.hpp rt_amd/csrc/lane_state.hpp rt_amd/csrc/queue_build.hpp rt_amd/csrc/camera_forms.hpp rt_amd/csrc/bvh_build.hpp rt_amd/csrc/bvh_build_device.hpp rt_amd/csrc/frame_group.hpp rt_amd/csrc/delivery.hpp rt_amd/csrc/internal.hpp include/rt_hip.h
+HIP_HDR  := rt_amd/csrc/kernels.hpp rt_amd/csrc/launch_plan.hpp rt_amd/csrc/progressive.hpp rt_amd/csrc/denoise.hpp rt_amd/csrc/denoise_rules.hpp rt_amd/csrc/temporal.hpp rt_amd/csrc/reproject_rules.hpp rt_amd/csrc/adaptive.hpp rt_amd/csrc/adaptive_rules.hpp rt_amd/csrc/lights.hpp rt_amd/csrc/sky_band.hpp rt_amd/csrc/centre_ray.hpp rt_amd/csrc/frame_setup.hpp rt_amd/csrc/contract.hpp rt_amd/csrc/scan.hpp rt_amd/csrc/bvh_scan.hpp rt_amd/csrc/bvh.hpp rt_amd/csrc/box_bvh.hpp rt_amd/csrc/box_bvh_scan.hpp rt_amd/csrc/scan_streamed.hpp rt_amd/csrc/handover.hpp rt_amd/csrc/pixel_output.hpp rt_amd/csrc/lane_state.hpp rt_amd/csrc/queue_build.hpp rt_amd/csrc/camera_forms.hpp rt_amd/csrc/bvh_build.hpp rt_amd/csrc/bvh_build_device.hpp rt_amd/csrc/frame_group.hpp rt_amd/csrc/delivery.hpp rt_amd/csrc/internal.hpp include/rt_hip.h
 HOST_SRC := rt_amd/host/host_capi.cpp rt_amd/host/scene.cpp rt_amd/host/toml_subset.cpp
 HOST_HDR := $(wildcard rt_amd/host/*.hpp) rt_amd/host/host_capi.h rt_amd/host/named_colours.inc include/rt_hip.h
 
@@ -27,7 +27,7 @@ all: $(LIBDIR)/librt_hip.so $(LIBDIR)/librt_hip_kat.so $(LIBDIR)/librt_host.so r
 # (-DRT_HIP_FAST_BUILD -ffp-contract=fast: only launch_render_fast comes out of that one)
 FASTFLAGS := $(filter-out -ffp-contract=off,$(HIPFLAGS)) -ffp-contract=fast -DRT_HIP_FAST_BUILD
 OBJDIR   := build/obj$(NAME)
-HIP_OBJS := $(OBJDIR)/kernels.o $(OBJDIR)/kernels_fast.o $(API_UNITS:%=$(OBJDIR)/%.o) $(OBJDIR)/delivery.o $(OBJDIR)/bvh.o $(OBJDIR)/box_bvh.o $(OBJDIR)/bvh_build.o $(OBJDIR)/launch_plan.o $(OBJDIR)/frame_setup.o $(OBJDIR)/progressive.o $(OBJDIR)/denoise_params.o $(OBJDIR)/temporal_params.o $(OBJDIR)/adaptive_params.o $(OBJDIR)/lights.o
+HIP_OBJS := $(OBJDIR)/kernels.o $(OBJDIR)/kernels_fast.o $(API_UNITS:%=$(OBJDIR)/%.o) $(OBJDIR)/delivery.o $(OBJDIR)/bvh.o $(OBJDIR)/box_bvh.o $(OBJDIR)/bvh_build.o $(OBJDIR)/launch_plan.o $(OBJDIR)/frame_setup.o $(OBJDIR)/progressive.o $(OBJDIR)/denoise_params.o $(OBJDIR)/temporal_params.o $(OBJDIR)/adaptive_params.o $(OBJDIR)/lights.o $(OBJDIR)/sky_band.o $(OBJDIR)/sky_band_rule.o
 
 $(OBJDIR)/kernels.o: rt_amd/csrc/kernels.hip $(HIP_HDR)
 	@mkdir -p $(OBJDIR)
@@ -83,6 +83,13 @@ $(OBJDIR)/adaptive_params.o: rt_amd/csrc/adaptive.cpp rt_amd/csrc/adaptive.hpp r
 # emissive materials' host-only rules (the emission table's checks, rt_hip_lights_from_spec): plain C++17 too, and the same source is
 # built into tests/native/light_plan_dump and the program of `make sanitize-lights` on the CPU
 $(OBJDIR)/lights.o: rt_amd/csrc/lights.cpp rt_amd/csrc/lights.hpp include/rt_hip.h
+	@mkdir -p $(OBJDIR)
+	$(CXX) -std=c++17 -O2 -fPIC -fvisibility=hidden -Wall -Wextra $(DEFS) -c $< -o $@
+
+# the sky band's rule (sky_band_rows: how many rows from the top of a frame provably see nothing): plain C++17 too, and the same
+# source is built into tests/native/sky_band_dump and the program of `make sanitize-sky-band` on the CPU.  (sky_band.o is the band's kernel,
+# sky_band.hip, by the pattern rule above.)
+$(OBJDIR)/sky_band_rule.o: rt_amd/csrc/sky_band.cpp rt_amd/csrc/sky_band.hpp rt_amd/csrc/frame_setup.hpp rt_amd/csrc/launch_plan.hpp include/rt_hip.h
 	@mkdir -p $(OBJDIR)
 	$(CXX) -std=c++17 -O2 -fPIC -fvisibility=hidden -Wall -Wextra $(DEFS) -c $< -o $@
 
@@ -190,6 +197,14 @@ sanitize-lights: tests/native/light_spec_sanitize.cpp rt_amd/csrc/lights.cpp rt_
 	$(CXX) -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer $< rt_amd/csrc/lights.cpp -o build/light_spec_sanitize
 	build/light_spec_sanitize
 
+# `make sanitize-sky-band`: the sky band's rule behind the main() of tests/native/sky_band_dump.cpp, fed the constructed cases of
+# tests/test_sky_band_rule.py from tests/golden/sky_band_cases.txt (written by `python -m tests.test_sky_band_rule`, held to it by that file's tests), under AddressSanitizer and UndefinedBehaviorSanitizer.  CPU only, nothing is
+# loaded into python; the binary goes to build/ and is run at once
+sanitize-sky-band: tests/native/sky_band_dump.cpp rt_amd/csrc/sky_band.cpp rt_amd/csrc/sky_band.hpp rt_amd/csrc/frame_setup.cpp rt_amd/csrc/frame_setup.hpp
+	@mkdir -p build
+	$(CXX) -O1 -g -std=c++17 -ffp-contract=off -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer $< rt_amd/csrc/sky_band.cpp rt_amd/csrc/frame_setup.cpp -o build/sky_band_sanitize
+	build/sky_band_sanitize < tests/golden/sky_band_cases.txt > /dev/null
+
 oracle:
 	$(MAKE) -C oracle
 
@@ -208,4 +223,4 @@ clean:
 	rm -f $(LIBDIR)/*.so rt_amd/bin/rt_headless tests/native/lbvh_reference tests/native/libbox_reference.so tests/native/libdenoise_reference.so tests/native/libreproject_reference.so tests/native/libadaptive_reference.so tests/native/liblight_reference.so
 	$(MAKE) -C oracle clean
 
-.PHONY: all oracle clean variant sanitize-temporal sanitize-box-bvh sanitize-adaptive sanitize-lights
+.PHONY: all oracle clean variant sanitize-temporal sanitize-box-bvh sanitize-adaptive sanitize-lights sanitize-sky-band

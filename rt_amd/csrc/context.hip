@@ -91,6 +91,10 @@ extern "C" rt_hip_status rt_hip_create(rt_hip_ctx** out_ctx, int device)
 		if (end != knob && v >= -1 && v < 1024)
 			ctx->numa_node = static_cast<int>(v);
 	}
+	if (const char* knob = std::getenv("RT_HIP_SKY_BAND")) // (the sky band, DESIGN.md §5: on unless this says 0)
+		ctx->sky_band_enabled = std::strcmp(knob, "0") != 0;
+	if (const char* knob = std::getenv("RT_HIP_SKY_BAND_LOG"))
+		ctx->sky_band_log = std::strcmp(knob, "1") == 0;
 	hipError_t e = ctx->counters.reserve(sizeof(device_counters));
 	if (e == hipSuccess)
 		e = hipEventCreate(&ctx->render_begin);

@@ -32,6 +32,7 @@
 #include "progressive.hpp"
 #include "adaptive.hpp"
 #include "lights.hpp"
+#include "sky_band.hpp"
 
 #include <rccl/rccl.h>
 
@@ -352,6 +353,21 @@ struct rt_hip_ctx
 	rt_hip::temporal_state temporal;		  // the history of rt_hip_render_temporal (temporal.hip)
 	rt_hip::adaptive_accumulation adaptive;	  // the accumulation of rt_hip_render_adaptive (adaptive.hip)
 
+	// ---- the sky band (sky_band.hpp, render.hip) ----
+	bool sky_band_enabled = true;		 // RT_HIP_SKY_BAND=0 in the environment at creation: no frame of this context takes a band
+	bool sky_band_log = false;			 // RT_HIP_SKY_BAND_LOG=1 at creation: one line per launch on stderr with the band's rows
+	std::vector<float> sphere_table;	 // host copy of the resident scene's (c, r^2) rows (scene.hip; empty beyond sky_band_max_spheres)
+	// the rule's last answer and what it was asked: the resident scene, the launch's flags and kernel, the frame's constants without its seed
+	struct
+	{
+		bool valid = false;
+		uint64_t scene_uploads = 0;
+		uint32_t flags = 0;
+		int scan = 0;
+		rt_hip::frame_params frame{};
+		uint32_t rows = 0;
+	} sky_band_asked;
+
 	rt_hip_ctx() = default;
 	rt_hip_ctx(const rt_hip_ctx&) = delete;
 	rt_hip_ctx& operator=(const rt_hip_ctx&) = delete;
@@ -407,6 +423,8 @@ namespace rt_hip
 	// it NOTHING but the kernel is enqueued (the plug-in's call: rt_hip_render with stats == NULL).
 	// host_frame: d_rgba8 is page-locked host memory (a mapped frame): the tiles are cut for PCIe writes (choose_queue).
 	// pass: one pass of a progressive frame instead of the whole frame (NULL: the whole frame, as ever)
+	// sky_band: the caller renders one whole frame in this one launch and takes a sky band where the rule finds one (rt_hip_render's
+	// single-GPU path and rt_hip_render_device; the multi-GPU, frame-group, progressive, adaptive, temporal and denoise paths do not)
 	struct render_pass
 	{
 		uint32_t first_sample, n_samples; // whole chunks, or up to the scene's samples_per_pixel (checked by the caller)
@@ -414,7 +432,7 @@ namespace rt_hip
 		bool adaptive = false;			  // an adaptive pass (adaptive.hip): d_accum is the whole block — accum, state, pass_sum, moments — and no pixel is stored
 	};
 	rt_hip_status render_device(rt_hip_ctx* ctx, uint32_t width, uint32_t height, uint64_t seed, uint32_t flags, const rt_hip_partition* part, uint32_t* d_rgba8, float* d_rgb_f32, void* stream, bool whole_frame_buffers, bool keep_stats, bool host_frame,
-								const render_pass* pass = nullptr);
+								const render_pass* pass = nullptr, bool sky_band = false);
 	rt_hip_status fetch_member_stats(rt_hip_ctx* ctx);
 	rt_hip_stats stats_of_group_rank(const rt_hip_ctx* ctx, uint32_t rank);
 	void sum_group_stats(const rt_hip_ctx* ctx, rt_hip_stats* out);

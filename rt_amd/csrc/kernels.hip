@@ -202,9 +202,14 @@ namespace rt_hip
 			const uint32_t tile_h = (1u << q.pixels_log2) >> q.tile_w_log2;
 
 			// one tile per wave: workgroups are handed out bottom row first — the lower part of a frame is usually the
-			// expensive one (ground under sky), and starting with it keeps the cheap sky tiles for the tail
+			// expensive one (ground under sky), and starting with it keeps the cheap sky tiles for the tail.
+			// Below a SKY BAND (sky_band.hpp; render.hip) the grid covers the rows under the band only, and the band's height — the first row
+			// of this launch — arrives in q.block_items, a word the tile-per-wave builds that are no pass do not otherwise read (0 in every
+			// other launch of theirs: kernels.hpp, rolling_buffers).  One scalar addition in front of the loop: every row this kernel
+			// then speaks of is an image row, checked against p.local_rows = the frame's height.  (In global_row, where a multi-GPU
+			// rank's rows become image rows, the same offset moved the register table of 126 of the 326 builds: DESIGN.md §5.)
 			const uint32_t tile_x0 = (blockIdx.x * 4u + wave) * tile_w;
-			const uint32_t tile_y0 = (gridDim.y - 1u - blockIdx.y) * tile_h;
+			const uint32_t tile_y0 = (gridDim.y - 1u - blockIdx.y) * tile_h + ((!ROLLING && !PASS) ? q.block_items : 0u);
 			uint32_t next_item = 0; // wave-uniform queue head
 			// [ADAPT] bit i: pixel i of this wave's tile has stopped — not traced, not folded (wave-uniform: one ballot of the tile's state words)
 			unsigned long long tile_stopped = 0;
@@ -1427,14 +1432,17 @@ namespace rt_hip
 		// side: queue_build.hpp, unpack_words)
 		struct kernel_words
 		{
-			queue_params queue;			   // block_items: [pass builds] the pass's first chunk
+			queue_params queue;			   // block_items: [pass builds] the pass's first chunk; [other tile-per-wave builds] the launch's first image row
 			unsigned long long* item_sums; // [scan_bvh and its builds] the hierarchy's descriptor(s)
 			uint32_t* pixel_done;		   // [pass builds] the accumulator (adaptive: the block that starts with it)
 		};
-		kernel_words pack_words(const rolling_buffers& rolling, const launch_plan& plan)
+		kernel_words pack_words(const rolling_buffers& rolling, const launch_plan& plan, uint32_t first_row)
 		{
 			const kernel_build& build = plan.build;
 			kernel_words words = { plan.queue, rolling.item_sums, rolling.pixel_done };
+			// a tile-per-wave launch (below: unless it is a pass) starts at image row first_row: the rows under a sky band (render.hip)
+			if (!scan_is_persistent(build.scan))
+				words.queue.block_items = first_row;
 			if (build.scan == scan_bvh)
 				words.item_sums = reinterpret_cast<unsigned long long*>(const_cast<device_bvh*>(rolling.bvh));
 #ifndef RT_HIP_FAST_BUILD
@@ -1480,7 +1488,7 @@ namespace rt_hip
 			}
 			grid = dim3(std::min(grid.x, a.compute_units * static_cast<uint32_t>(known.per_cu)));
 		}
-		const kernel_words words = pack_words(a.rolling, plan);
+		const kernel_words words = pack_words(a.rolling, plan, a.first_row);
 		hipLaunchKernelGGL(kernel, grid, dim3(block_threads), plan.lds_bytes, a.stream, a.frame, words.queue, a.small, a.scene, a.scene.primitive_geometry, a.d_rgba8, a.d_rgb_f32, a.d_counters, words.item_sums, words.pixel_done);
 		return plan.variant;
 	}

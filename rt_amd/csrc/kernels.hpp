@@ -93,7 +93,8 @@ namespace rt_hip
 	//                           builds find their state words and pass sums behind it (rt_hip.h, rt_hip_adaptive_pass_device).  Every
 	//                           other build: not read.
 	//   queue_params::block_items   rolling builds: items a wave draws at a time.  Pass and adaptive builds: launch_plan::first_chunk.
-	//                           Every other build: not read.
+	//                           Every other build (tile-per-wave, no pass): launch_arguments::first_row, the image row the grid starts at —
+	//                           0, or the height of the frame's sky band.
 	struct rolling_buffers
 	{
 		// 16 bytes per item of this rank's rows (a chunk sum on its way to the lane that folds the pixel); not needed when a pixel is one
@@ -159,6 +160,7 @@ namespace rt_hip
 		uint32_t compute_units;			// of the device: the big-scene kernels are launched persistent
 		launch_cache& cache;
 		hipStream_t stream;
+		uint32_t first_row = 0; // a tile-per-wave launch that is no pass: the image row its grid starts at (the rows under a sky band; frame.local_rows is then the frame's height)
 	};
 
 	// launches what the plan says; returns the kernel variant launched (RT_HIP_KERNEL_*)
@@ -166,6 +168,9 @@ namespace rt_hip
 
 	// the same with RT_HIP_FLAG_FAST's arithmetic (kernels.hip built with RT_HIP_FAST_BUILD); mg scatter table only
 	uint32_t launch_render_fast(const launch_arguments& a);
+
+	// the sky band (sky_band.hip): rows [0, band.local_rows) of a frame, every sample of which is one segment that ends in the sky
+	void launch_sky_band(const frame_params& band, uint32_t* d_rgba8, float* d_rgb_f32, device_counters* d_counters, hipStream_t stream);
 
 	// RT_HIP_FLAG_PREVIEW: one ray per pixel, reference src/renderers/rasterizer.cpp:24-85
 	void launch_preview(const frame_params& frame, const device_scene& scene, uint32_t* d_rgba8, float* d_rgb_f32, device_counters* d_counters, hipStream_t stream);

@@ -38,7 +38,7 @@ extern "C" rt_hip_status rt_hip_render_device(rt_hip_ctx* ctx,
 											  float* d_rgb_f32,
 											  void* stream)
 {
-	return render_device(ctx, width, height, seed, flags, part, d_rgba8, d_rgb_f32, stream, false, true, ctx && d_rgba8 && is_host_memory(ctx, d_rgba8));
+	return render_device(ctx, width, height, seed, flags, part, d_rgba8, d_rgb_f32, stream, false, true, ctx && d_rgba8 && is_host_memory(ctx, d_rgba8), nullptr, true);
 }
 
 // one pass of a progressive frame at the device level (rt_hip.h): samples [first_sample, first_sample + n_samples) of the
@@ -78,7 +78,7 @@ extern "C" rt_hip_status rt_hip_render_pass_device(rt_hip_ctx* ctx,
 namespace rt_hip
 {
 rt_hip_status render_device(rt_hip_ctx* ctx, uint32_t width, uint32_t height, uint64_t seed, uint32_t flags, const rt_hip_partition* part, uint32_t* d_rgba8, float* d_rgb_f32, void* stream, bool whole_frame_buffers, bool keep_stats, bool host_frame,
-							const render_pass* pass)
+							const render_pass* pass, bool sky_band)
 {
 	if (!ctx || !d_rgba8)
 		return fail(RT_HIP_INVALID_ARGUMENT, "rt_hip_render_device: NULL argument");
@@ -114,6 +114,7 @@ rt_hip_status render_device(rt_hip_ctx* ctx, uint32_t width, uint32_t height, ui
 	// every decision of the launch is made here, once: the buffers below are prepared from the plan the launch code then follows
 	launch_plan plan{}; // (the preview: nothing to plan)
 	rolling_buffers rolling;
+	uint32_t band_rows = 0, band_variant = RT_HIP_KERNEL_NONE; // the sky band's rows (0: none) and the kernel variant the frame reports with one
 	if (!(flags & RT_HIP_FLAG_PREVIEW))
 	{
 		launch_request request{};
@@ -180,6 +181,37 @@ rt_hip_status render_device(rt_hip_ctx* ctx, uint32_t width, uint32_t height, ui
 			rolling.item_sums = ctx->item_sums.as<unsigned long long>();
 			rolling.pixel_done = ctx->pixel_done.as<uint32_t>();
 		}
+		// The sky band (sky_band.hpp): the rows from the top of the image that provably see nothing go to a scene-free
+		// kernel of their own, and the plan's kernel is launched over the rows below — planned as any shorter launch is.  The rule
+		// is asked once per (scene, camera, size, flags): an unmoved camera's further frames pay a comparison.  Only the two callers that
+		// render one whole frame in one launch offer a band (`sky_band`), and never for a pass: a pass build reads its first chunk where
+		// the other tile-per-wave builds read the band's height, and its accumulator is no business of the band's kernel.
+		if (ctx->sky_band_enabled && sky_band && !pass)
+		{
+			frame_params asked = f;
+			asked.frame_key_a = asked.frame_key_b = 0u; // (the seed does not move a ray)
+			auto& last = ctx->sky_band_asked;
+			if (!(last.valid && last.scene_uploads == ctx->scene_uploads && last.flags == flags && last.scan == plan.build.scan && std::memcmp(&last.frame, &asked, sizeof(asked)) == 0))
+			{
+				const sky_band_request rule = { ctx->sphere_table.data(), ctx->scene.n_spheres, ctx->scene.n_planes, flags, false, false, plan.build.scan, &f };
+				last.rows = sky_band_rows(rule);
+				last.valid = true, last.scene_uploads = ctx->scene_uploads, last.flags = flags, last.scan = plan.build.scan, last.frame = asked;
+			}
+			if (last.rows)
+			{
+				request.local_rows = f.local_rows - last.rows;
+				const launch_plan below = plan_launch(request);
+				const bool tile_per_wave = below.build.scan > 0 || below.build.scan == scan_resident;
+				if (!below.refusal[0] && below.slot_bytes <= max_slot_bytes && !below.item_sums_bytes && tile_per_wave)
+				{
+					band_rows = last.rows;
+					band_variant = plan.variant; // (what the frame reports: the kernel of its scene, also where every row is sky)
+					plan = below;
+				}
+			}
+		}
+		if (ctx->sky_band_log)
+			std::fprintf(stderr, "rt_hip sky band: rows %u of %u (%ux%u, flags 0x%x)\n", band_rows, height, width, height, flags);
 	}
 	device_counters* const counters = ctx->counters.as<device_counters>();
 	if (keep_stats)
@@ -190,6 +222,18 @@ rt_hip_status render_device(rt_hip_ctx* ctx, uint32_t width, uint32_t height, ui
 	else if (plan.big_scene) // the persistent big-scene kernels draw items from a sequence whose head must start at 0
 		RT_HIP_TRY(hipMemsetAsync(&counters->next_item, 0, sizeof(counters->next_item), s)); // (seconds-long launches: not launch-bound)
 	uint32_t variant = RT_HIP_KERNEL_PREVIEW;
+	// (inside the event pair that yields render_ms, in front of the scene's kernel; an experiment build with RT_HIP_SKY_BAND_LAST puts it
+	// behind instead: measured)
+	const auto launch_band = [&]()
+	{
+		frame_params band = f;
+		band.local_rows = band_rows;
+		launch_sky_band(band, d_rgba8, d_rgb_f32, counters, s);
+	};
+#ifndef RT_HIP_SKY_BAND_LAST
+	if (band_rows)
+		launch_band();
+#endif
 	if (flags & RT_HIP_FLAG_PREVIEW)
 		launch_preview(f, ctx->scene, d_rgba8, d_rgb_f32, counters, s);
 	else if (flags & RT_HIP_FLAG_FAST)
@@ -203,7 +247,13 @@ rt_hip_status render_device(rt_hip_ctx* ctx, uint32_t width, uint32_t height, ui
 		variant = launch_render({ f, lit, (flags & RT_HIP_FLAG_SM_MATERIALS) ? ctx->small_sm : ctx->small, plan, d_rgba8, d_rgb_f32, counters, rolling, ctx->compute_units, ctx->cache, s });
 	}
 	else
-		variant = launch_render({ f, ctx->scene, (flags & RT_HIP_FLAG_SM_MATERIALS) ? ctx->small_sm : ctx->small, plan, d_rgba8, d_rgb_f32, counters, rolling, ctx->compute_units, ctx->cache, s });
+		variant = launch_render({ f, ctx->scene, (flags & RT_HIP_FLAG_SM_MATERIALS) ? ctx->small_sm : ctx->small, plan, d_rgba8, d_rgb_f32, counters, rolling, ctx->compute_units, ctx->cache, s, band_rows }); // (below a band: the plan's grid covers rows [band_rows, height), the kernel is told the first)
+#ifdef RT_HIP_SKY_BAND_LAST
+	if (band_rows)
+		launch_band();
+#endif
+	if (band_rows)
+		variant = band_variant;
 	RT_HIP_TRY(hipGetLastError());
 	ctx->launched = true;
 	ctx->last_stream = s;
@@ -457,7 +507,7 @@ extern "C" rt_hip_status rt_hip_render(rt_hip_ctx* ctx,
 			RT_HIP_TRY(ctx->staging_rgb.reserve(rgb_bytes));
 		}
 		drain.armed = true; // from here on the device may be storing into host memory: no return before the stream has drained
-		if (const rt_hip_status st = render_device(ctx, width, height, seed, flags & render_flag_mask, nullptr, d_frame, rgb_f32 ? ctx->frame_rgb.as<float>() : nullptr, ctx->stream, false, keep_stats, true))
+		if (const rt_hip_status st = render_device(ctx, width, height, seed, flags & render_flag_mask, nullptr, d_frame, rgb_f32 ? ctx->frame_rgb.as<float>() : nullptr, ctx->stream, false, keep_stats, true, nullptr, true))
 			return st;
 		if (staged.delivery)
 			staged.delivery->launched();

@@ -312,6 +312,14 @@ namespace rt_hip
 			ctx->box_columns_print = box_print;
 			ctx->small = r.small;
 			ctx->small_sm = r.small_sm;
+			// the sphere rows of the geometry table, as the kernels read them, for the sky band's rule (sky_band.hpp)
+			ctx->sphere_table.clear();
+			if (s.n_spheres <= sky_band_max_spheres)
+			{
+				ctx->sphere_table.resize(static_cast<size_t>(s.n_spheres) * 4u);
+				if (s.n_spheres)
+					std::memcpy(ctx->sphere_table.data(), r.image + L.geometry, ctx->sphere_table.size() * sizeof(float));
+			}
 
 			unsigned char* base = ctx->scene_columns.as<unsigned char>();
 			device_scene& d = ctx->scene;

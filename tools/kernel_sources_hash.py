@@ -7,7 +7,8 @@ from pathlib import Path
 ROOT = Path(__file__).resolve().parent.parent
 FILES = ["rt_amd/csrc/kernels.hip", "rt_amd/csrc/kernels.hpp", "rt_amd/csrc/contract.hpp", "rt_amd/csrc/scan.hpp", "rt_amd/csrc/bvh_scan.hpp",
          "rt_amd/csrc/box_bvh_scan.hpp", "rt_amd/csrc/scan_streamed.hpp", "rt_amd/csrc/handover.hpp", "rt_amd/csrc/pixel_output.hpp", "rt_amd/csrc/lane_state.hpp",
-         "rt_amd/csrc/queue_build.hpp", "rt_amd/csrc/camera_forms.hpp", "rt_amd/csrc/launch_plan.hpp", "rt_amd/csrc/launch_plan.cpp", "rt_amd/csrc/frame_setup.hpp"]
+         "rt_amd/csrc/queue_build.hpp", "rt_amd/csrc/camera_forms.hpp", "rt_amd/csrc/launch_plan.hpp", "rt_amd/csrc/launch_plan.cpp", "rt_amd/csrc/frame_setup.hpp",
+         "rt_amd/csrc/sky_band.hip", "rt_amd/csrc/sky_band.hpp", "rt_amd/csrc/sky_band.cpp"]
 
 
 def kernel_sources_sha16(root: Path = ROOT) -> str:
