@@ -50,6 +50,13 @@ GPU_SCENES = {  # name: (named scene, toml, camera)
 GPU_ROWS = {("basic", 113): 48, ("dielectric", 113): 24, ("up", 113): 112, ("floating", 113): 32, ("basic", 40): 16, ("dielectric", 40): 8, ("up", 40): 40, ("floating", 40): 8,
             ("many", 113): 48, ("many", 40): 16}
 
+# The frames of tests/test_gpu_sky_band_sweep.py, tiny and ragged on purpose, and the rows the rule gives them: (scene, (W, H)) -> R.
+# 67 x 27: 67 is ragged against tile widths 2, 4, 8 and 16 and leaves the last band workgroup three lanes; 19 (or, looking up, 3) rows
+# stay below the band.  13 x 43: narrower than one band workgroup.  1 x 40: one column.  65 x 35: the last band workgroup has one lane.
+# 63 x 24, looking up: every row is sky at a height that is a whole number of strips — no scene kernel is launched.
+SWEEP_ROWS = {("basic", (67, 27)): 8, ("many", (67, 27)): 8, ("basic", (13, 43)): 16, ("many", (13, 43)): 16, ("basic", (1, 40)): 16, ("basic", (65, 35)): 16,
+              ("up", (67, 27)): 24, ("up", (63, 24)): 24}
+
 
 def gpu_scene(name):
     named, toml, camera = GPU_SCENES[name]
@@ -242,6 +249,20 @@ def test_rows_of_the_gpu_tests_scenes(dump):
     assert GPU_ROWS[("up", 40)] == 40 and 0 < GPU_ROWS[("floating", 113)] < GPU_ROWS[("basic", 113)]
 
 
+def test_rows_of_the_gpu_sweeps_frames(dump):
+    """tests/test_gpu_sky_band_sweep.py holds the band's log line to SWEEP_ROWS; here the table is held to the rule, and the rule to the oracle."""
+    for (name, size), rows in SWEEP_ROWS.items():
+        pod = gpu_scene(name).describe(*size)
+        assert band_rows(dump, pod, size) == rows, (name, size)
+        assert band_rows(dump, pod, size, scan=SCAN_RESIDENT) == rows, (name, size)
+        assert_rows_are_sky(pod, size, rows, f"{name} {size[0]}x{size[1]}")
+    # what the GPU frames rely on: a band and an odd number of rows below it — ragged against every tile height — or no row below it at all
+    for (name, size), rows in SWEEP_ROWS.items():
+        if size in ((67, 27), (13, 43), (65, 35)):
+            assert 0 < rows < size[1] and (size[1] - rows) % 2 == 1, (name, size, rows)
+    assert SWEEP_ROWS[("up", (63, 24))] == 24 and SWEEP_ROWS[("up", (67, 27))] == 24 and 0 < SWEEP_ROWS[("basic", (1, 40))] < 40
+
+
 def sanitizer_lines():
     """the input of `make sanitize-sky-band` (tests/golden/sky_band_cases.txt): cases of this file, gates and non-finite spheres included.
     `python -m tests.test_sky_band_rule` writes the file; test_the_sanitizer_input_is_this_files_cases holds it to this function."""
@@ -251,6 +272,9 @@ def sanitizer_lines():
     for name in GPU_SCENES:
         for size in GPU_SIZES + [(1920, 1080)]:
             lines.append(request_line(gpu_scene(name).describe(*size), size))
+    for name, size in SWEEP_ROWS:
+        lines.append(request_line(gpu_scene(name).describe(*size), size))
+        lines.append(request_line(gpu_scene(name).describe(*size), size, scan=SCAN_RESIDENT))
     pod = rt_amd.Scene.named("basic").describe(*MIDDLE)
     for flag in EXCLUDED_FLAGS:
         lines.append(request_line(pod, MIDDLE, flags=getattr(capi, f"RT_HIP_FLAG_{flag}")))
