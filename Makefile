@@ -21,7 +21,7 @@ HIP_HDR  := rt_amd/csrc/kernels.hpp rt_amd/csrc/launch_plan.hpp rt_amd/csrc/prog
 HOST_SRC := rt_amd/host/host_capi.cpp rt_amd/host/scene.cpp rt_amd/host/toml_subset.cpp
 HOST_HDR := $(wildcard rt_amd/host/*.hpp) rt_amd/host/host_capi.h rt_amd/host/named_colours.inc include/rt_hip.h
 
-all: $(LIBDIR)/librt_hip.so $(LIBDIR)/librt_hip_kat.so $(LIBDIR)/librt_host.so rt_amd/bin/rt_headless tests/native/lbvh_reference tests/native/libbox_reference.so tests/native/libdenoise_reference.so tests/native/libreproject_reference.so tests/native/libadaptive_reference.so tests/native/liblight_reference.so oracle
+all: $(LIBDIR)/librt_hip.so $(LIBDIR)/librt_hip_kat.so $(LIBDIR)/librt_host.so rt_amd/bin/rt_headless tests/native/lbvh_reference tests/native/libbox_reference.so tests/native/libdenoise_reference.so tests/native/libreproject_reference.so tests/native/libadaptive_reference.so tests/native/liblight_reference.so tests/native/libdirect_reference.so oracle
 
 # kernels.hip is compiled twice: the parity contract (contraction off), and RT_HIP_FLAG_FAST's arithmetic
 # (-DRT_HIP_FAST_BUILD -ffp-contract=fast: only launch_render_fast comes out of that one)
@@ -205,6 +205,11 @@ sanitize-sky-band: tests/native/sky_band_dump.cpp rt_amd/csrc/sky_band.cpp rt_am
 	$(CXX) -O1 -g -std=c++17 -ffp-contract=off -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer $< rt_amd/csrc/sky_band.cpp rt_amd/csrc/frame_setup.cpp -o build/sky_band_sanitize
 	build/sky_band_sanitize < tests/golden/sky_band_cases.txt > /dev/null
 
+# the CPU restatement of RT_HIP_FLAG_DIRECT_LIGHT: light_reference.cpp's way — the oracle's own translation unit, only the
+# trace loop restated — with the vertex rule of rt_amd/csrc/direct_light_rules.hpp, the text the device runs; tests/direct_reference.py binds it
+tests/native/libdirect_reference.so: tests/native/direct_reference.cpp rt_amd/csrc/direct_light_rules.hpp oracle/cpu_ref.cpp oracle/cpu_ref.h include/rt_hip.h
+	$(CXX) -O2 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -fno-math-errno -mfma -Wall -Wextra -shared $< -o $@ -lpthread
+
 oracle:
 	$(MAKE) -C oracle
 
@@ -220,7 +225,7 @@ oracle/_ref/soagen_columns: tests/native/soagen_columns.cpp $(LIBDIR)/librt_hip.
 endif
 
 clean:
-	rm -f $(LIBDIR)/*.so rt_amd/bin/rt_headless tests/native/lbvh_reference tests/native/libbox_reference.so tests/native/libdenoise_reference.so tests/native/libreproject_reference.so tests/native/libadaptive_reference.so tests/native/liblight_reference.so
+	rm -f $(LIBDIR)/*.so rt_amd/bin/rt_headless tests/native/lbvh_reference tests/native/libbox_reference.so tests/native/libdenoise_reference.so tests/native/libreproject_reference.so tests/native/libadaptive_reference.so tests/native/liblight_reference.so tests/native/libdirect_reference.so
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean variant sanitize-temporal sanitize-box-bvh sanitize-adaptive sanitize-lights sanitize-sky-band

@@ -303,7 +303,26 @@ enum
 	 * RT_HIP_FLAG_TRACE_BOXES and RT_HIP_FLAG_BOX_BVH, and by both progressive entry points, both adaptive entry points,
 	 * rt_hip_render_temporal, rt_hip_denoise_progressive and rt_hip_guide_device.  A library older than this flag refuses the bit
 	 * (unknown flag bits): that is how a caller finds out whether it is there. */
-	RT_HIP_FLAG_EMISSION = 1u << 16
+	RT_HIP_FLAG_EMISSION = 1u << 16,
+	/* DIRECT LIGHT SAMPLING (opt-in): modifies RT_HIP_FLAG_EMISSION — refused without it (RT_HIP_UNSUPPORTED, by
+	 * this flag's name) and wherever that flag is refused.  A sphere whose material is a light and whose radius is finite and > 0
+	 * is a SAMPLED LIGHT; at most the first 256 of them in sphere order are sampled, every other light (planes, further spheres,
+	 * degenerate spheres) counts on hit as under RT_HIP_FLAG_EMISSION alone.  At every hit whose scatter function is lambert (under
+	 * the scatter table in force) the path draws ONE more generator step, picks a sampled light and a point on it (an octahedral
+	 * map over the hemisphere that faces the vertex, or over the whole sphere from inside), and if the unchanged closest-hit query
+	 * from the vertex toward that point returns this very sphere adds throughput * attenuation * emission * weight to the sample;
+	 * then the scatter runs as ever.  A sampled light that the NEXT segment of such a vertex hits is worth 0 (the vertex has
+	 * accounted for it); after a metal or dielectric vertex, and from the camera, it counts on hit.  A shadow query consumes no
+	 * bounce and IS a segment: rt_hip_stats keeps its layout and `segments` counts shadow queries too.  The PROMISE: frame, float
+	 * mean and `segments` are bit for bit those of the CPU restatement (tests/native/direct_reference.cpp over
+	 * rt_amd/csrc/direct_light_rules.hpp).  With no sampled light the frame is the RT_HIP_FLAG_EMISSION frame in every respect.
+	 * THIS IS NOT A LOWER-VARIANCE WAY TO THE RT_HIP_FLAG_EMISSION IMAGE: the contract's lambert scatter draws its directions from
+	 * the positive octant (as the reference does), so the light a path finds by running into it is skewed, while the sampled term
+	 * is the physically standard one — the two frames converge to DIFFERENT images where a sampled light illuminates lambert
+	 * surfaces.  Nothing is promised about speed.  Works wherever RT_HIP_FLAG_EMISSION works; ignored with RT_HIP_FLAG_PREVIEW;
+	 * refused by name by both progressive entry points, both adaptive entry points, rt_hip_render_temporal,
+	 * rt_hip_denoise_progressive and rt_hip_guide_device.  A library older than this flag refuses the bit (unknown flag bits). */
+	RT_HIP_FLAG_DIRECT_LIGHT = 1u << 17
 };
 
 typedef struct rt_hip_ctx rt_hip_ctx;

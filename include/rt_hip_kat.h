@@ -127,6 +127,14 @@ RT_HIP_API rt_hip_status rt_hip_kat_sqrt_div(rt_hip_ctx* ctx, uint32_t n, const 
  * k = 0 sqrt, 1 reciprocal, 2 reciprocal of sqrt.  All three counts must be 0. */
 RT_HIP_API rt_hip_status rt_hip_kat_exhaustive_math(rt_hip_ctx* ctx, uint64_t out_mismatches[3], uint32_t out_first[3]);
 
+/* RT_HIP_FLAG_DIRECT_LIGHT's rules (rt_amd/csrc/direct_light_rules.hpp) as the device computes them; both must equal
+ * the same header compiled with g++ (tests/native/direct_reference.cpp) bit for bit.
+ * The octahedral map: out[4 i ..] = (p.x, p.y, p.z, dot(p, p)) of the numerators (ka[i], kb[i]), each below 2^24. */
+RT_HIP_API rt_hip_status rt_hip_kat_direct_octahedral(rt_hip_ctx* ctx, uint32_t n, const uint32_t* ka, const uint32_t* kb, float* out);
+/* The aim and its weight: in[9 i ..] = vertex x, its normal, the light's centre (3 floats each); radius[i]; n_lights (1 .. 256) ->
+ * out[5 i ..] = (w.x, w.y, w.z, weight, aimed as 0 / 1). */
+RT_HIP_API rt_hip_status rt_hip_kat_direct_aim(rt_hip_ctx* ctx, uint32_t n, const uint32_t* ka, const uint32_t* kb, const float* in, const float* radius, uint32_t n_lights, float* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,6 +33,7 @@ RT_HIP_FLAG_BVH_DEVICE_BUILD = 1 << 11  # with RT_HIP_FLAG_BVH: the hierarchy is
 RT_HIP_FLAG_TRACE_BOXES = 1 << 13  # the traced frame hits the scene's boxes too; bit 12 is unassigned
 RT_HIP_FLAG_BOX_BVH = 1 << 14  # with RT_HIP_FLAG_TRACE_BOXES: the boxes through a hierarchy of their own, no 256-box cap, same frame
 RT_HIP_FLAG_EMISSION = 1 << 16  # materials with a row > 0 in the context's emission table are lights; bit 15 is unassigned
+RT_HIP_FLAG_DIRECT_LIGHT = 1 << 17  # with RT_HIP_FLAG_EMISSION: lambert vertices sample the sphere lights directly
 RT_HIP_MULTI_PEER_COPY = 1 << 0
 RT_HIP_MULTI_DIRECT_FRAME = 1 << 1
 RT_HIP_TRANSPORT_NONE, RT_HIP_TRANSPORT_RCCL_GATHER, RT_HIP_TRANSPORT_PEER_COPY, RT_HIP_TRANSPORT_DIRECT_FRAME = 0, 1, 2, 3
@@ -291,6 +292,8 @@ RT_HIP_KAT_SYMBOLS = [
     ("rt_hip_kat_box_bvh_builds", C.c_int, [C.c_void_p, C.c_void_p]),
     ("rt_hip_kat_sqrt_div", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rt_hip_kat_exhaustive_math", C.c_int, [C.c_void_p, C.POINTER(C.c_uint64 * 3), C.POINTER(C.c_uint32 * 3)]),
+    ("rt_hip_kat_direct_octahedral", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("rt_hip_kat_direct_aim", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
 ]
 
 RT_HOST_SYMBOLS = [

@@ -191,6 +191,12 @@ namespace rt_hip
 	__device__ __forceinline__ float divide(float a, float b) { return a / b; }
 #endif
 
+	// (as a function object: what direct_light_rules.hpp is handed on the device)
+	struct contract_inv_sqrt
+	{
+		__device__ __forceinline__ float operator()(float x) const { return inv_sqrt_rn(x); }
+	};
+
 	// normalize(v) = v * inv_sqrt(dot(v,v))
 	__device__ __forceinline__ vec3 normalize(vec3 v)
 	{

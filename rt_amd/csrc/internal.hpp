@@ -239,7 +239,7 @@ namespace rt_hip
 	struct frame_delivery; // below: the module-owned frame and the threads that carry it to the caller's buffer
 
 	// (RT_HIP_FLAG_PERSISTENT_FRAME and RT_HIP_FLAG_STATS are rt_hip_render's own: they do not travel to the launch)
-	constexpr uint32_t render_flag_mask = RT_HIP_FLAG_FORCE_TILED | RT_HIP_FLAG_FORCE_RESIDENT | RT_HIP_FLAG_SM_MATERIALS | RT_HIP_FLAG_PREVIEW | RT_HIP_FLAG_FORCE_STREAMED | RT_HIP_FLAG_FAST | RT_HIP_FLAG_FORCE_HALF_CHUNKS | RT_HIP_FLAG_FORCE_WHOLE_CHUNKS | RT_HIP_FLAG_BVH | RT_HIP_FLAG_BVH_DEVICE_BUILD | RT_HIP_FLAG_TRACE_BOXES | RT_HIP_FLAG_BOX_BVH | RT_HIP_FLAG_EMISSION;
+	constexpr uint32_t render_flag_mask = RT_HIP_FLAG_FORCE_TILED | RT_HIP_FLAG_FORCE_RESIDENT | RT_HIP_FLAG_SM_MATERIALS | RT_HIP_FLAG_PREVIEW | RT_HIP_FLAG_FORCE_STREAMED | RT_HIP_FLAG_FAST | RT_HIP_FLAG_FORCE_HALF_CHUNKS | RT_HIP_FLAG_FORCE_WHOLE_CHUNKS | RT_HIP_FLAG_BVH | RT_HIP_FLAG_BVH_DEVICE_BUILD | RT_HIP_FLAG_TRACE_BOXES | RT_HIP_FLAG_BOX_BVH | RT_HIP_FLAG_EMISSION | RT_HIP_FLAG_DIRECT_LIGHT;
 
 }
 
@@ -331,6 +331,13 @@ struct rt_hip_ctx
 	const uint32_t* light_scatter = nullptr;
 	const float4* light_shading_sm = nullptr;
 	const uint32_t* light_scatter_sm = nullptr;
+	// RT_HIP_FLAG_DIRECT_LIGHT: the SAMPLED-LIGHT LIST lies in the same block, in FRONT of the light variant's shading table
+	// (direct_list_bytes before light_shading: a count word, then two float4 per sampled light — the direct builds find it from the
+	// variant pointer, kernels.hpp), built and invalidated with the tables.  The scatter tables exist a second time with
+	// scatter_emit_sampled in the sampled lights' rows: the frames of RT_HIP_FLAG_EMISSION alone go on reading the tables above.
+	uint32_t sampled_lights = 0; // n of the resident scene under the table (valid with the tables)
+	const uint32_t* light_scatter_direct = nullptr;
+	const uint32_t* light_scatter_sm_direct = nullptr;
 	// Opt-in (RT_HIP_FLAG_PERSISTENT_FRAME, frame groups): the CALLER's buffer, page-locked and mapped into the GPU's address
 	// space while it keeps arriving at the same address: the kernel renders straight into it.  The caller then owes the
 	// module rt_hip_forget_frame before that memory is unmapped (rt_hip.h).

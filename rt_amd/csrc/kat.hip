@@ -15,6 +15,7 @@
 #include "box_bvh_scan.hpp"
 #include "bvh_build.hpp"
 #include "bvh_build_device.hpp"
+#include "direct_light_rules.hpp"
 
 #include <algorithm>
 #include <vector>
@@ -258,6 +259,28 @@ namespace
 		}
 	}
 
+	// RT_HIP_FLAG_DIRECT_LIGHT's rules header as the render kernels run it (the contract's inv_sqrt_rn handed in)
+	__global__ void kat_direct_octahedral(uint32_t n, const uint32_t* __restrict__ ka, const uint32_t* __restrict__ kb, float* __restrict__ out)
+	{
+		const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+		if (i < n)
+		{
+			float l2;
+			const vec3 p = direct_light::octahedral_point<vec3>(ka[i], kb[i], l2);
+			out[4u * i + 0u] = p.x, out[4u * i + 1u] = p.y, out[4u * i + 2u] = p.z, out[4u * i + 3u] = l2;
+		}
+	}
+	__global__ void kat_direct_aim(uint32_t n, const uint32_t* __restrict__ ka, const uint32_t* __restrict__ kb, const float* __restrict__ in, const float* __restrict__ radius, uint32_t n_lights, float* __restrict__ out)
+	{
+		const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+		if (i < n)
+		{
+			const float* const v = in + 9u * i;
+			const direct_light::aim<vec3> a = direct_light::aim_at(ka[i], kb[i], vec3{ v[0], v[1], v[2] }, vec3{ v[3], v[4], v[5] }, vec3{ v[6], v[7], v[8] }, radius[i], n_lights, contract_inv_sqrt{});
+			out[5u * i + 0u] = a.w.x, out[5u * i + 1u] = a.w.y, out[5u * i + 2u] = a.w.z, out[5u * i + 3u] = a.weight, out[5u * i + 4u] = a.aimed ? 1.0f : 0.0f;
+		}
+	}
+
 	// every one of the 2^32 binary32 bit patterns through sqrt_rn / rcp_rn / inv_sqrt_rn against hipcc's general
 	// correctly rounded expansions (inv_sqrt_rn: against the contract's definition, evaluated through binary64);
 	// result[2k] = mismatches, result[2k+1] = smallest mismatching input + 1
@@ -335,6 +358,15 @@ static void launch_kat_sqrt_div(uint32_t n, const float* d_a, const float* d_b, 
 {
 	const dim3 grid((n + block_threads - 1) / block_threads);
 	hipLaunchKernelGGL(kat_sqrt_div, grid, dim3(block_threads), 0, stream, n, d_a, d_b, d_sqrt, d_div);
+}
+
+static void launch_kat_direct(uint32_t n, const uint32_t* d_ka, const uint32_t* d_kb, const float* d_in, const float* d_radius, uint32_t n_lights, float* d_out, hipStream_t stream)
+{
+	const dim3 grid((n + block_threads - 1) / block_threads);
+	if (d_in)
+		hipLaunchKernelGGL(kat_direct_aim, grid, dim3(block_threads), 0, stream, n, d_ka, d_kb, d_in, d_radius, n_lights, d_out);
+	else
+		hipLaunchKernelGGL(kat_direct_octahedral, grid, dim3(block_threads), 0, stream, n, d_ka, d_kb, d_out);
 }
 
 static void launch_kat_exhaustive_math(unsigned long long* d_result, hipStream_t stream)
@@ -722,6 +754,49 @@ extern "C" rt_hip_status rt_hip_kat_sqrt_div(rt_hip_ctx* ctx, uint32_t n, const 
 	std::memcpy(out_sqrt, out.host.ptr, bytes);
 	std::memcpy(out_div, out.host.as<unsigned char>() + bytes, bytes);
 	return RT_HIP_OK;
+}
+
+// both entries of RT_HIP_FLAG_DIRECT_LIGHT's rules: in = NULL is the octahedral map (4 floats out per item), else the aim (5 floats out)
+static rt_hip_status kat_direct(const char* name, rt_hip_ctx* ctx, uint32_t n, const uint32_t* ka, const uint32_t* kb, const float* in, const float* radius, uint32_t n_lights, float* out)
+{
+	if (!ctx || !n || !ka || !kb || !out || (in && (!radius || n_lights < 1u || n_lights > direct_light::max_sampled_lights)))
+		return kat_fail(RT_HIP_INVALID_ARGUMENT, "%s: invalid argument", name);
+	for (uint32_t i = 0; i < n; i++)
+		if ((ka[i] | kb[i]) >> 24)
+			return kat_fail(RT_HIP_INVALID_ARGUMENT, "%s: item %u: a numerator must be below 2^24", name, i);
+	RT_HIP_KAT_TRY(hipSetDevice(ctx->device));
+	const size_t words = static_cast<size_t>(n) * 4u, in_bytes = 2u * words + (in ? static_cast<size_t>(n) * 40u : 0u), out_bytes = static_cast<size_t>(n) * (in ? 20u : 16u);
+	scratch input, output;
+	RT_HIP_KAT_TRY(input.reserve(in_bytes));
+	RT_HIP_KAT_TRY(output.reserve(out_bytes));
+	unsigned char* const host = input.host.as<unsigned char>();
+	std::memcpy(host, ka, words);
+	std::memcpy(host + words, kb, words);
+	if (in)
+	{
+		std::memcpy(host + 2u * words, in, static_cast<size_t>(n) * 36u);
+		std::memcpy(host + 2u * words + static_cast<size_t>(n) * 36u, radius, words);
+	}
+	RT_HIP_KAT_TRY(hipMemcpy(input.device.ptr, input.host.ptr, in_bytes, hipMemcpyHostToDevice));
+	const unsigned char* const d = input.device.as<unsigned char>();
+	launch_kat_direct(n, reinterpret_cast<const uint32_t*>(d), reinterpret_cast<const uint32_t*>(d + words), in ? reinterpret_cast<const float*>(d + 2u * words) : nullptr,
+					  in ? reinterpret_cast<const float*>(d + 2u * words + static_cast<size_t>(n) * 36u) : nullptr, n_lights, output.device.as<float>(), nullptr);
+	RT_HIP_KAT_TRY(hipGetLastError());
+	RT_HIP_KAT_TRY(hipMemcpy(output.host.ptr, output.device.ptr, out_bytes, hipMemcpyDeviceToHost));
+	std::memcpy(out, output.host.ptr, out_bytes);
+	return RT_HIP_OK;
+}
+
+extern "C" rt_hip_status rt_hip_kat_direct_octahedral(rt_hip_ctx* ctx, uint32_t n, const uint32_t* ka, const uint32_t* kb, float* out)
+{
+	return kat_direct("rt_hip_kat_direct_octahedral", ctx, n, ka, kb, nullptr, nullptr, 1u, out);
+}
+
+extern "C" rt_hip_status rt_hip_kat_direct_aim(rt_hip_ctx* ctx, uint32_t n, const uint32_t* ka, const uint32_t* kb, const float* in, const float* radius, uint32_t n_lights, float* out)
+{
+	if (!in)
+		return kat_fail(RT_HIP_INVALID_ARGUMENT, "rt_hip_kat_direct_aim: invalid argument");
+	return kat_direct("rt_hip_kat_direct_aim", ctx, n, ka, kb, in, radius, n_lights, out);
 }
 
 extern "C" rt_hip_status rt_hip_kat_exhaustive_math(rt_hip_ctx* ctx, uint64_t out_mismatches[3], uint32_t out_first[3])

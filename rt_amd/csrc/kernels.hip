@@ -54,6 +54,7 @@
 #include "pixel_output.hpp"
 #include "lane_state.hpp"
 #include "queue_build.hpp"
+#include "direct_light_rules.hpp"
 #include "camera_forms.hpp"
 
 #ifdef RT_HIP_FAST_BUILD
@@ -132,7 +133,7 @@ namespace rt_hip
 			// what this build is (queue_build.hpp has the why of each)
 			using build = queue_build<SCAN, HALF, NP, GC>;
 			constexpr int NS = build::NS;
-			constexpr bool PASS = build::PASS, ADAPT = build::ADAPT, BOXES = build::BOXES, BOXTREE = build::BOXTREE, LIGHTS = build::LIGHTS;
+			constexpr bool PASS = build::PASS, ADAPT = build::ADAPT, BOXES = build::BOXES, BOXTREE = build::BOXTREE, LIGHTS = build::LIGHTS, DIRECT = build::DIRECT;
 			constexpr bool RESIDENT = build::RESIDENT, RESIDENT_SCALAR_SCAN = build::RESIDENT_SCALAR_SCAN, BVH = build::BVH, ROLLING = build::ROLLING;
 			constexpr bool INDEXED = build::INDEXED, SCALAR_SEGMENTS = build::SCALAR_SEGMENTS;
 			constexpr uint32_t slot_floats = build::slot_floats;
@@ -192,6 +193,15 @@ namespace rt_hip
 			device_box_bvh box_tree{};
 			if constexpr (BOXTREE)
 				box_tree = *words.box_tree;
+			// [DIRECT] the sampled-light list in front of the light variant's shading table, and its count (wave-uniform: >= 1, the plan's rule)
+			const float4* direct_list = nullptr;
+			uint32_t direct_n = 0;
+			if constexpr (DIRECT)
+			{
+				const unsigned char* const list = reinterpret_cast<const unsigned char*>(s.primitive_shading) - direct_list_bytes;
+				direct_n = *reinterpret_cast<const uint32_t*>(list);
+				direct_list = reinterpret_cast<const float4*>(list + direct_list_header_bytes);
+			}
 			const uint32_t lane = threadIdx.x & 63u;
 			const uint32_t wave = threadIdx.x >> 6;
 			const uint32_t chunk_items = q.chunks << q.pixels_log2;	   // chunks of one pixel tile: P x K
@@ -259,6 +269,12 @@ namespace rt_hip
 			// vector instruction count, 42 % more scalar ones, 2.64 -> 2.85 ms — profiles/r04/ab_mode_masks.txt, HISTORY.md.)
 			enum : uint32_t { lane_free = 0, lane_restart = 1, lane_retired = 3, lane_trace = 4 };
 			uint32_t mode = lane_free;
+			// [DIRECT] what a lane carries besides: the direct light of the sample in flight; across a shadow query the contribution
+			// that is added if the aimed sphere is visible, that sphere, and the vertex's normal; whether the query in flight IS a shadow query;
+			// and whether the vertex the segment in flight leaves has sampled the lights itself
+			vec3 direct_sum = { 0.0f, 0.0f, 0.0f }, pending = { 0.0f, 0.0f, 0.0f }, kept_normal = { 0.0f, 0.0f, 0.0f };
+			uint32_t pending_sphere = 0;
+			bool shadow = false, sampled_before = false;
 #define RT_HIP_IS(m) ((m) == lane_trace ? mode >= lane_trace : mode == (m))
 #define RT_HIP_BECOME(m) (mode = (m))
 
@@ -470,6 +486,12 @@ namespace rt_hip
 			// `colour += trace(...)` (:193) for the sample in flight, then the next sample of the chunk or the end of the item
 			const auto end_sample = [&](vec3 contribution)
 			{
+				if constexpr (DIRECT) // `return direct + X`
+				{
+					contribution = direct_sum + contribution;
+					direct_sum = { 0.0f, 0.0f, 0.0f };
+					sampled_before = false;
+				}
 				if (HALF && ROLLING)
 				{
 					publish_sum(item_sums + 2u * (static_cast<size_t>(slot) * p.samples_per_pixel + st.sample), contribution);
@@ -596,6 +618,7 @@ namespace rt_hip
 				}
 
 				bool shade = false;
+				[[maybe_unused]] bool from_shadow = false; // [DIRECT] the lane shades behind its shadow query: it has aimed already
 				vec3 normal; // meaningful only where `shade` holds: deliberately not initialised
 				float4 shading;
 				uint32_t scatter_kind = scatter_lambert;
@@ -607,6 +630,7 @@ namespace rt_hip
 					uint32_t kind;
 					float distance;
 					uint32_t small_index = 0;
+					[[maybe_unused]] uint32_t direct_index = 0; // [DIRECT] the accepted hit's index among its kind
 					if (NS == scan_tiled)
 					{
 						uint32_t index;
@@ -758,14 +782,35 @@ namespace rt_hip
 						{
 							kind = select_hit(spheres, planes, distance, index);
 							fetch_hit<SM>(s, st.origin, st.dir, kind, distance, index, normal, shading, scatter_kind);
+							if constexpr (DIRECT)
+								direct_index = index;
 						}
 					}
-					if (!kind)
+					if (DIRECT && shadow)
+					{
+						// the answer of a shadow query: the light is visible iff the accepted hit is the aimed sphere (no distance is compared).  The
+						// lane then scatters as the lambert vertex it is, from the unchanged origin; its throughput holds the attenuation already.
+						if (kind == 1u && direct_index == pending_sphere)
+							direct_sum = direct_sum + pending;
+						shadow = false;
+						from_shadow = true;
+						sampled_before = true;
+						shade = true;
+						normal = kept_normal;
+						shading = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
+						scatter_kind = scatter_lambert;
+					}
+					else if (!kind)
 					{
 						RT_HIP_REGION(4); // miss: sky, end of sample
 						end_sample(st.throughput * sky(st.dir.y)); // miss (:163-164)
 					}
-					else if (LIGHTS && scatter_kind == scatter_emit)
+					else if (DIRECT && scatter_kind == scatter_emit_sampled && sampled_before)
+					{
+						// a sampled light behind a vertex that has sampled the lights itself: worth 0 (§3.13)
+						end_sample({ 0.0f, 0.0f, 0.0f });
+					}
+					else if (LIGHTS && (scatter_kind == scatter_emit || (DIRECT && scatter_kind == scatter_emit_sampled)))
 					{
 						// the accepted hit's material is a light: the sample is throughput * emission and the path ends — no draw, no scatter (§3.12)
 						end_sample(st.throughput * vec3{ shading.x, shading.y, shading.z });
@@ -951,6 +996,40 @@ namespace rt_hip
 					float toward2;
 					if (SM)
 						toward2 = 1.0f;
+					if constexpr (DIRECT)
+					{
+						if (shade && !from_shadow && scatter_kind == scatter_lambert)
+						{
+							// the VERTEX RULE (§3.13; direct_light_rules.hpp) with the step just drawn: the light from its third numerator, the point on
+							// it from the first two.  Gather loads: every lane reads the light it chose.
+							const uint32_t chosen = direct_light::choose_light((word * step_mul_c) >> 8, direct_n);
+							const float4 ball = direct_list[2u * chosen], glow = direct_list[2u * chosen + 1u];
+							const direct_light::aim<vec3> a =
+								direct_light::aim_at(word_a >> 8, word_b >> 8, st.origin, normal, vec3{ ball.x, ball.y, ball.z }, ball.w, direct_n, contract_inv_sqrt{});
+							sampled_before = true;
+							if (a.aimed)
+							{
+								// an aiming lane: the shadow query is its next, from the unchanged origin; it consumes no bounce
+								st.throughput = st.throughput * vec3{ shading.x, shading.y, shading.z };
+								pending = (st.throughput * vec3{ glow.x, glow.y, glow.z }) * a.weight;
+								pending_sphere = __float_as_uint(glow.w);
+								kept_normal = normal;
+								st.dir = a.w;
+								shadow = true;
+								shade = false;
+							}
+							else
+							{
+								// aims at nothing: the lane scatters in this trip, with a step of its own
+								word = next_step_word(st.counter, st.keys);
+								word_a = word * step_mul_a, word_b = word * step_mul_b;
+								d0 = step_numerator(word_a);
+								d1 = step_numerator(word_b);
+							}
+						}
+						else if (shade && !from_shadow)
+							sampled_before = false; // a metal or dielectric vertex samples nothing
+					}
 					if (shade && SM && scatter_kind == scatter_dielectric)
 					{
 						// dielectric_scatter, sm_ray_tracer.cpp:181-219 (refract :161-172, schlick :174-179); shading.w = the
@@ -1341,12 +1420,14 @@ namespace rt_hip
 							return render_queue<scan_bvh_boxtree, SM, false, NP, GC>;
 					return render_queue<tree ? scan_bvh_boxes : scan_resident_boxes, SM, false, NP, GC>;
 				}
-				if (build.lights)
+				if (build.lights && !build.direct)
 					return render_queue<tree ? scan_bvh_lights : scan_resident_lights, SM, false, NP, GC>;
 				if (build.adaptive)
 					return render_queue<tree ? scan_bvh_adapt : scan_resident_adapt, SM, false, NP, GC>;
 				if (build.pass)
 					return render_queue<tree ? scan_bvh_pass : scan_resident_pass, SM, false, NP, GC>;
+				if (build.direct) // (RT_HIP_FLAG_DIRECT_LIGHT with a sampled light: implies lights, never a pass; named last — the order of mention is the code object's)
+					return render_queue<tree ? scan_bvh_direct : scan_resident_direct, SM, false, NP, GC>;
 			}
 #endif
 			if constexpr (!SM) // (the sm table keeps whole chunks: one set of kernels fewer to build)

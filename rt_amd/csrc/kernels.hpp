@@ -69,9 +69,19 @@ namespace rt_hip
 		scatter_lambert = 0,	// mg_ray_tracer.cpp:110-123
 		scatter_metal = 1,		// mg_ray_tracer.cpp:126-140
 		scatter_dielectric = 2,	// sm_ray_tracer.cpp:181-219 (opt-in)
-		scatter_emit = 3		// a light (RT_HIP_FLAG_EMISSION): no scatter at all — the row's shading.rgb is the emission and the path ends; only
+		scatter_emit = 3,		// a light (RT_HIP_FLAG_EMISSION): no scatter at all — the row's shading.rgb is the emission and the path ends; only
 								// the light variant of the per-primitive tables holds it, and only the light builds read that
+		scatter_emit_sampled = 4 // a SAMPLED light (RT_HIP_FLAG_DIRECT_LIGHT): scatter_emit, except that the segment behind a lambert vertex —
+								// which has sampled the lights itself — finds it worth 0; only the direct variant of the scatter tables holds it
 	};
+
+	// RT_HIP_FLAG_DIRECT_LIGHT: the sampled-light list lies direct_list_bytes IN FRONT of the light variant's (mg) shading table, which the
+	// direct builds are handed as device_scene::primitive_shading — found from that pointer, the way box_bvh_descriptor_offset works, so
+	// that no kernel argument is added or moved.  A header of 256 bytes whose first word is n, then per sampled light two float4:
+	// (centre.xyz, radius) and (emission.rgb, sphere index as bits).
+	constexpr uint32_t direct_max_lights = 256; // (direct_light::max_sampled_lights)
+	constexpr size_t direct_list_header_bytes = 256;
+	constexpr size_t direct_list_bytes = direct_list_header_bytes + direct_max_lights * 2u * sizeof(float4);
 
 	// the whole scene of the `small` kernel, passed by value as a kernel argument (-> SGPRs); host copy kept by the context
 	// (scalar_max_spheres: launch_plan.hpp)

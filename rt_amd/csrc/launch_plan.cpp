@@ -241,6 +241,7 @@ namespace rt_hip
 		plan.build.boxes = boxes;
 		plan.build.box_tree = box_tree;
 		plan.build.lights = lights;
+		plan.build.direct = lights && request.n_sampled_lights != 0u; // (the caller counts sampled lights under RT_HIP_FLAG_DIRECT_LIGHT only)
 		plan.first_chunk = pass ? request.pass_first_sample / sample_chunk : 0u;
 
 		// small scenes: one wave per tile, four tiles side by side per workgroup.  Big scenes: a persistent launch — what

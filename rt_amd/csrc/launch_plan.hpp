@@ -128,18 +128,23 @@ namespace rt_hip
 		// the LIGHT builds of the same two scans (kernel_build::lights; RT_HIP_FLAG_EMISSION with at least one light): a hit
 		// whose scatter row says scatter_emit ends the sample with throughput * the row's shading.rgb — the same scan, whole chunks only
 		scan_resident_lights = -12,
-		scan_bvh_lights = -13
+		scan_bvh_lights = -13,
+		// the DIRECT builds of the light builds (kernel_build::direct; RT_HIP_FLAG_DIRECT_LIGHT with at least one sampled light):
+		// a lambert vertex aims a shadow segment at a sampled sphere light before it scatters — light builds in everything else
+		scan_resident_direct = -14,
+		scan_bvh_direct = -15
 	};
-	constexpr bool scan_has_lights(int code) { return code == scan_resident_lights || code == scan_bvh_lights; }
+	constexpr bool scan_has_direct(int code) { return code == scan_resident_direct || code == scan_bvh_direct; }
+	constexpr bool scan_has_lights(int code) { return code == scan_resident_lights || code == scan_bvh_lights || scan_has_direct(code); }
 	constexpr bool scan_is_adaptive(int code) { return code == scan_resident_adapt || code == scan_bvh_adapt; }
 	constexpr bool scan_is_pass(int code) { return code == scan_resident_pass || code == scan_bvh_pass || scan_is_adaptive(code); }
 	constexpr bool scan_has_boxes(int code) { return code == scan_resident_boxes || code == scan_bvh_boxes || code == scan_bvh_boxtree; }
 	constexpr bool scan_has_box_tree(int code) { return code == scan_bvh_boxtree; }
 	constexpr int scan_of(int code) // the scan a build's code stands for
 	{
-		return (code == scan_resident_pass || code == scan_resident_boxes || code == scan_resident_adapt || code == scan_resident_lights)
+		return (code == scan_resident_pass || code == scan_resident_boxes || code == scan_resident_adapt || code == scan_resident_lights || code == scan_resident_direct)
 				   ? static_cast<int>(scan_resident)
-				   : ((code == scan_bvh_pass || code == scan_bvh_boxes || code == scan_bvh_boxtree || code == scan_bvh_adapt || code == scan_bvh_lights) ? static_cast<int>(scan_bvh) : code);
+				   : ((code == scan_bvh_pass || code == scan_bvh_boxes || code == scan_bvh_boxtree || code == scan_bvh_adapt || code == scan_bvh_lights || code == scan_bvh_direct) ? static_cast<int>(scan_bvh) : code);
 	}
 	// the rolling kernels are launched persistent: as many workgroups as the device keeps resident (launch_cache, kernels.hpp)
 	constexpr bool scan_is_persistent(int scan) { return scan == scan_tiled || scan == scan_streamed || scan == scan_streamed_dense; }
@@ -177,6 +182,9 @@ namespace rt_hip
 		// default: "no lights"), a frame is planned as it always was, field for field; with at least one it is planned like a box frame,
 		// onto the light builds of the two tile-per-wave kernels.
 		uint32_t n_lights = 0;
+		// RT_HIP_FLAG_DIRECT_LIGHT: how many SAMPLED lights the resident scene has under that table.  With none the frame is
+		// planned as the RT_HIP_FLAG_EMISSION frame, field for field — the plan looks at this count, not at the flag.
+		uint32_t n_sampled_lights = 0;
 	// LDS bytes a workgroup of the device may ask for (the context reads it off the device's properties); 0: workgroup_lds_bytes.  A plan
 	// of a tile-per-wave kernel whose tables and chunk sums need more is refused, whatever the build: only the hierarchy kernel's — 24 KiB
 	// of stacks in front of the slots — can, from 3409 samples (a frame's, or a pass's) at a limit of 64 KiB.
@@ -197,6 +205,7 @@ namespace rt_hip
 		bool box_tree;		  // ... and RT_HIP_FLAG_BOX_BVH: the hierarchy kernel's scan_bvh_boxtree build (`boxes` is set too)
 		bool adaptive;		  // an adaptive pass: the scan's ADAPT build (scan_resident_adapt / scan_bvh_adapt; implies `pass`)
 		bool lights;		  // RT_HIP_FLAG_EMISSION with at least one light: the scan's LIGHT build (scan_resident_lights / scan_bvh_lights)
+		bool direct;		  // ... and at least one sampled light (RT_HIP_FLAG_DIRECT_LIGHT): its DIRECT build (scan_resident_direct / scan_bvh_direct; `lights` is set too)
 	};
 
 	struct launch_plan

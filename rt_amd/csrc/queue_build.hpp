@@ -33,8 +33,12 @@
 namespace rt_hip
 {
 	// waves per SIMD a build is compiled for (the RT_HIP_WAVES_* above)
-	constexpr int waves_per_simd(int NS, int NP)
+	// (direct: a direct build of RT_HIP_FLAG_DIRECT_LIGHT, which carries the sample's direct sum, the pending contribution, the aimed sphere and
+	// the vertex's normal across the shadow query — about ten more live registers than its light build: a case of its own, one wave fewer)
+	constexpr int waves_per_simd(int NS, int NP, bool direct = false)
 	{
+		if (direct)
+			return NS == scan_bvh ? RT_HIP_WAVES_BVH - 1 : RT_HIP_WAVES_RESIDENT - 2;
 		if (NS == scan_bvh)
 			return RT_HIP_WAVES_BVH;
 		if (NS == scan_streamed_dense)
@@ -71,7 +75,7 @@ namespace rt_hip
 		// still fit 64 VGPRs — they keep running 8 waves — and use the extra scalar registers: the lane-mask bookkeeping of
 		// the divergent loop no longer spills to VGPR lanes (3.12 -> 3.05 ms).  6 waves are slower everywhere.  The
 		// big-scene modes get the registers of 5 waves per SIMD.
-		static constexpr int waves = waves_per_simd(NS, NP);
+		static constexpr int waves = waves_per_simd(NS, NP, scan_has_direct(SCAN));
 
 		// HALF (small and resident kernels, short launches; see choose_queue): the unit of work is HALF a chunk, 8 samples.
 		// The chunk sum stays what the contract says — sixteen samples added in sample order — so the lane that traces a
@@ -160,6 +164,17 @@ namespace rt_hip
 		// tail such a lane is what a lane that ended on the sky is: it draws nothing for the old sample and its stream stands where next_sample
 		// puts it.  No argument is added or moved; every other instantiation keeps its symbol and its instructions.
 		static constexpr bool LIGHTS = scan_has_lights(SCAN);
+
+		// DIRECT (RT_HIP_FLAG_DIRECT_LIGHT; scan_resident_direct, scan_bvh_direct): a LIGHTS build whose lambert vertices sample the
+		// sphere lights.  A lambert lane that would shade takes one trip as an AIMING lane instead: the fused tail's generator step is the vertex
+		// rule's (direct_light_rules.hpp), the lane multiplies its throughput by the attenuation at once (the later scatter multiplies by 1),
+		// keeps the pending contribution, the aimed sphere and the hit's normal, and its next query is the shadow query from the unchanged origin.
+		// After that query it adds the pending contribution if the accepted hit is that very sphere and goes through the tail as an ordinary
+		// lambert scatter.  A lane whose rule aims at nothing scatters in the aiming trip itself, with a second step under its own mask.
+		// end_sample adds the sample's direct sum in front.  The sampled-light list (at most 256 entries of two float4) is read with per-lane
+		// gather loads — each lane picks its own light — from direct_list_bytes in front of the light variant's shading table (kernels.hpp):
+		// no argument is added or moved, no LDS is taken; every other instantiation keeps its symbol and its instructions.
+		static constexpr bool DIRECT = scan_has_direct(SCAN);
 
 		static_assert(!PASS || !HALF, "passes are built for whole chunks only");
 		static_assert(!BOXES || !HALF, "the box builds are built for whole chunks only");

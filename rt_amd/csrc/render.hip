@@ -126,6 +126,15 @@ rt_hip_status render_device(rt_hip_ctx* ctx, uint32_t width, uint32_t height, ui
 		request.flags = flags, request.host_frame = host_frame, request.fast_arithmetic = (flags & RT_HIP_FLAG_FAST) != 0;
 		request.n_boxes = ctx->scene.n_boxes;
 		request.n_lights = (flags & RT_HIP_FLAG_EMISSION) ? ctx->emission_lights : 0u;
+		// RT_HIP_FLAG_DIRECT_LIGHT: the plan looks at how many SAMPLED lights the resident scene has under the table, and the list's builder counts
+		// them (scene.hip: the light variant of the tables, built if missing or stale — a table build like the hierarchy's, nothing is enqueued)
+		if ((flags & RT_HIP_FLAG_DIRECT_LIGHT) && request.n_lights != 0u && !pass)
+		{
+			if (const rt_hip_status st = ensure_light_tables(ctx))
+				return st;
+			RT_HIP_TRY(hipSetDevice(ctx->device));
+			request.n_sampled_lights = ctx->sampled_lights;
+		}
 		request.lds_limit = ctx->workgroup_lds_bytes;
 		plan = plan_launch(request);
 		// the refusals of the plan come before anything is enqueued — the hierarchy's build included
@@ -244,6 +253,8 @@ rt_hip_status render_device(rt_hip_ctx* ctx, uint32_t width, uint32_t height, ui
 		device_scene lit = ctx->scene;
 		lit.primitive_shading = ctx->light_shading, lit.primitive_scatter = ctx->light_scatter;
 		lit.primitive_shading_sm = ctx->light_shading_sm, lit.primitive_scatter_sm = ctx->light_scatter_sm;
+		if (plan.build.direct) // (the scatter tables that tell a sampled light from a light that counts on hit; the list lies in front of light_shading)
+			lit.primitive_scatter = ctx->light_scatter_direct, lit.primitive_scatter_sm = ctx->light_scatter_sm_direct;
 		variant = launch_render({ f, lit, (flags & RT_HIP_FLAG_SM_MATERIALS) ? ctx->small_sm : ctx->small, plan, d_rgba8, d_rgb_f32, counters, rolling, ctx->compute_units, ctx->cache, s });
 	}
 	else

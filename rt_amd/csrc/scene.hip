@@ -465,6 +465,8 @@ namespace rt_hip
 		ctx->light_tables_uploads = 0;
 		ctx->light_shading = ctx->light_shading_sm = nullptr;
 		ctx->light_scatter = ctx->light_scatter_sm = nullptr;
+		ctx->light_scatter_direct = ctx->light_scatter_sm_direct = nullptr;
+		ctx->sampled_lights = 0;
 		const size_t n_primitives = static_cast<size_t>(d.n_spheres) + d.n_planes + d.n_boxes;
 		std::vector<uint32_t> material(n_primitives, 0u);
 		std::vector<float> box_bounds(static_cast<size_t>(d.n_boxes) * 8u);
@@ -479,8 +481,11 @@ namespace rt_hip
 				std::memcpy(&material[static_cast<size_t>(d.n_spheres) + d.n_planes + i], &box_bounds[static_cast<size_t>(i) * 8u + 3u], 4);
 		}
 		const size_t shading_bytes = align_up(n_primitives * sizeof(float4), 256), scatter_bytes = align_up(n_primitives * 4u, 256);
-		const size_t shading_at = 0, scatter_at = shading_bytes, shading_sm_at = scatter_at + scatter_bytes, scatter_sm_at = shading_sm_at + shading_bytes;
-		const size_t total = std::max<size_t>(scatter_sm_at + scatter_bytes, 256);
+		// (RT_HIP_FLAG_DIRECT_LIGHT, DESIGN.md §3.13: the sampled-light list in FRONT of the shading table — kernels.hpp, direct_list_bytes — and the two
+		// scatter tables a second time, with scatter_emit_sampled in the sampled lights' rows)
+		const size_t list_at = 0, shading_at = direct_list_bytes, scatter_at = shading_at + shading_bytes, shading_sm_at = scatter_at + scatter_bytes, scatter_sm_at = shading_sm_at + shading_bytes;
+		const size_t scatter_direct_at = scatter_sm_at + scatter_bytes, scatter_sm_direct_at = scatter_direct_at + scatter_bytes;
+		const size_t total = scatter_sm_direct_at + scatter_bytes;
 		std::vector<unsigned char> image(total, 0);
 		if (n_primitives)
 		{
@@ -504,6 +509,34 @@ namespace rt_hip
 			for (const size_t at : { scatter_at, scatter_sm_at })
 				std::memcpy(image.data() + at + i * 4u, &emit, 4);
 		}
+		// the direct variant of the scatter tables and the list: a sphere whose material is a light and whose radius is finite and > 0 is a
+		// SAMPLED light, the first direct_max_lights of them in sphere order; every other light keeps scatter_emit
+		std::memcpy(image.data() + scatter_direct_at, image.data() + scatter_at, n_primitives * 4u);
+		std::memcpy(image.data() + scatter_sm_direct_at, image.data() + scatter_sm_at, n_primitives * 4u);
+		uint32_t n_sampled = 0;
+		if (d.n_spheres)
+		{
+			std::vector<float> columns(static_cast<size_t>(d.n_spheres) * 4u);
+			const float* const sources[4] = { d.sphere_cx, d.sphere_cy, d.sphere_cz, d.sphere_r };
+			for (size_t c = 0; c < 4; c++)
+				RT_HIP_TRY(hipMemcpy(columns.data() + c * d.n_spheres, sources[c], static_cast<size_t>(d.n_spheres) * 4u, hipMemcpyDeviceToHost));
+			for (uint32_t i = 0; i < d.n_spheres && n_sampled < direct_max_lights; i++)
+			{
+				const float* const rgb = ctx->emission.data() + static_cast<size_t>(material[i]) * 3u;
+				const float radius = columns[3u * static_cast<size_t>(d.n_spheres) + i];
+				if (!is_light(rgb) || !std::isfinite(radius) || !(radius > 0.0f))
+					continue;
+				const uint32_t sampled = scatter_emit_sampled;
+				const float rows[8] = { columns[i], columns[static_cast<size_t>(d.n_spheres) + i], columns[2u * static_cast<size_t>(d.n_spheres) + i], radius, rgb[0], rgb[1], rgb[2], 0.0f };
+				unsigned char* const entry = image.data() + list_at + direct_list_header_bytes + static_cast<size_t>(n_sampled) * sizeof rows;
+				std::memcpy(entry, rows, sizeof rows);
+				std::memcpy(entry + 28, &i, 4); // (the sphere's index as bits, in the emission row's spare lane)
+				std::memcpy(image.data() + scatter_direct_at + static_cast<size_t>(i) * 4u, &sampled, 4);
+				std::memcpy(image.data() + scatter_sm_direct_at + static_cast<size_t>(i) * 4u, &sampled, 4);
+				n_sampled++;
+			}
+		}
+		std::memcpy(image.data() + list_at, &n_sampled, 4);
 		RT_HIP_TRY(ctx->light_tables.reserve(total));
 		RT_HIP_TRY(hipMemcpy(ctx->light_tables.ptr, image.data(), total, hipMemcpyHostToDevice));
 		const unsigned char* const base = ctx->light_tables.as<unsigned char>();
@@ -511,6 +544,9 @@ namespace rt_hip
 		ctx->light_scatter = reinterpret_cast<const uint32_t*>(base + scatter_at);
 		ctx->light_shading_sm = reinterpret_cast<const float4*>(base + shading_sm_at);
 		ctx->light_scatter_sm = reinterpret_cast<const uint32_t*>(base + scatter_sm_at);
+		ctx->light_scatter_direct = reinterpret_cast<const uint32_t*>(base + scatter_direct_at);
+		ctx->light_scatter_sm_direct = reinterpret_cast<const uint32_t*>(base + scatter_sm_direct_at);
+		ctx->sampled_lights = n_sampled;
 		ctx->light_tables_uploads = ctx->scene_uploads;
 		ctx->light_tables_version = ctx->emission_version;
 		ctx->stats.upload_ms += static_cast<float>(seconds_since(t0) * 1e3);

@@ -213,6 +213,18 @@ namespace
 	// column, so the table comes from this text and the scene's material names (rt_hip_lights_from_spec: a KEY is a material's name, or its
 	// index) and is handed to the context (rt_hip_set_emission) — again whenever the materials change.  Unset or empty: no lights.  One-shot
 	// frames only: progressive, adaptive and temporal frames refuse the flag by name.  (Not for the preview, which ignores it.)
+	// RT_HIP_DIRECT_LIGHT=1 (rt_headless --direct-light) adds RT_HIP_FLAG_DIRECT_LIGHT to those frames: lambert surfaces sample the sphere lights
+	// directly.  Without RT_HIP_LIGHTS it does nothing.
+	bool direct_light_wanted()
+	{
+		static const bool wanted = []
+		{
+			const char* direct = std::getenv("RT_HIP_DIRECT_LIGHT");
+			return direct && *direct && std::string_view{ direct } != "0";
+		}();
+		return wanted;
+	}
+
 	const char* lights_spec()
 	{
 		static const char* const spec = []
@@ -261,7 +273,7 @@ namespace
 				}
 				lights_set = true;
 			}
-			flags = RT_HIP_FLAG_EMISSION;
+			flags = RT_HIP_FLAG_EMISSION | (direct_light_wanted() ? static_cast<uint32_t>(RT_HIP_FLAG_DIRECT_LIGHT) : static_cast<uint32_t>(RT_HIP_FLAG_NONE));
 			return true;
 		}
 

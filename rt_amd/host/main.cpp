@@ -32,6 +32,8 @@
 //                           light (exported to the renderer as RT_HIP_LIGHTS, the items joined with ';': rt_hip_lights_from_spec,
 //                           rt_hip_set_emission, RT_HIP_FLAG_EMISSION).  Hip renderers only; not with --progressive, --adaptive,
 //                           --temporal, --denoise or --boxes
+//   --direct-light          with --light: lambert surfaces sample the sphere lights directly (exported as RT_HIP_DIRECT_LIGHT=1:
+//                           RT_HIP_FLAG_DIRECT_LIGHT).  Not without --light, and not where --light is refused
 //   --dolly DX,DY,DZ        the camera moves by that much in world space before every frame after the first (camera::pose)
 //   --shared-frame NAME --rank R --world N   this process is rank R of N rt_headless processes that render ONE frame
 //                together (one per GPU: RT_HIP_DEVICE picks this one's): the back buffer is every process's mapping of the
@@ -146,6 +148,7 @@ namespace
 int main(int argc, char** argv)
 {
 	std::string scene_path, renderer_name, out_path, shared_name, lights;
+	bool direct_light = false;
 	unsigned width = 800, height = 600, spp = 0, bounces = 0, frames = 1, rank = 0, world = 1, progressive = 0;
 	bool frames_given = false;
 	bool list = false;
@@ -243,6 +246,11 @@ int main(int argc, char** argv)
 			lights += (lights.empty() ? "" : ";") + std::string{ value() };
 			::setenv("RT_HIP_LIGHTS", lights.c_str(), 1); // (read by the plug-in: the emission table from the scene's material names, RT_HIP_FLAG_EMISSION)
 		}
+		else if (arg == "--direct-light"sv)
+		{
+			direct_light = true;
+			::setenv("RT_HIP_DIRECT_LIGHT", "1", 1); // (read by the plug-in: RT_HIP_FLAG_DIRECT_LIGHT next to RT_HIP_FLAG_EMISSION)
+		}
 		else if (arg == "--dolly"sv)
 		{
 			char trailing = 0;
@@ -261,7 +269,7 @@ int main(int argc, char** argv)
 			world = static_cast<unsigned>(std::strtoul(value(), nullptr, 10));
 		else if (arg == "--help"sv || arg == "-h"sv)
 		{
-			log("usage: rt_headless [--list] [--scene file.toml] [--renderer name] [--size WxH] [--spp N] [--bounces N] [--seed N] [--frames N] [--out file.ppm] [--progressive SAMPLES] [--denoise] [--boxes [--box-bvh]] [--temporal] [--adaptive THRESHOLD] [--light KEY=R,G,B]... [--dolly DX,DY,DZ] [--shared-frame NAME --rank R --world N]");
+			log("usage: rt_headless [--list] [--scene file.toml] [--renderer name] [--size WxH] [--spp N] [--bounces N] [--seed N] [--frames N] [--out file.ppm] [--progressive SAMPLES] [--denoise] [--boxes [--box-bvh]] [--temporal] [--adaptive THRESHOLD] [--light KEY=R,G,B]... [--direct-light] [--dolly DX,DY,DZ] [--shared-frame NAME --rank R --world N]");
 			return 0;
 		}
 		else
@@ -302,6 +310,11 @@ int main(int argc, char** argv)
 	if (!lights.empty() && (progressive || adaptive || temporal || denoise || boxes || std::string_view{ desc->name }.substr(0, 3) != "hip"sv))
 	{
 		error("--light makes materials lights in one-shot frames of a hip renderer (not with --progressive, --adaptive, --temporal, --denoise or --boxes, not '", desc->name, "')");
+		return 2;
+	}
+	if (direct_light && lights.empty())
+	{
+		error("--direct-light says how the lights of --light are found: lambert surfaces sample the sphere lights directly (not without --light)");
 		return 2;
 	}
 	if (box_bvh && (!boxes || temporal))

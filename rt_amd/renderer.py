@@ -457,6 +457,24 @@ class HipRayTracer:
         capi.check_kat(capi.kat_lib().rt_hip_kat_sqrt_div(self._ctx, a.size, a.ctypes.data, b.ctypes.data, s.ctypes.data, q.ctypes.data))
         return s, q
 
+    def kat_direct_octahedral(self, ka: np.ndarray, kb: np.ndarray) -> np.ndarray:
+        """rt_amd/csrc/direct_light_rules.hpp's octahedral_point on the device: float32[n, 4] = (p.xyz, dot(p, p))."""
+        ka = np.ascontiguousarray(ka, dtype=np.uint32)
+        kb = np.ascontiguousarray(kb, dtype=np.uint32)
+        out = np.empty((ka.size, 4), dtype=np.float32)
+        capi.check_kat(capi.kat_lib().rt_hip_kat_direct_octahedral(self._ctx, ka.size, ka.ctypes.data, kb.ctypes.data, out.ctypes.data))
+        return out
+
+    def kat_direct_aim(self, ka: np.ndarray, kb: np.ndarray, vectors: np.ndarray, radius: np.ndarray, n_lights: int) -> np.ndarray:
+        """... and its aim_at: vectors float32[n, 9] = (x, normal, centre) -> float32[n, 5] = (w.xyz, weight, aimed)."""
+        ka = np.ascontiguousarray(ka, dtype=np.uint32)
+        kb = np.ascontiguousarray(kb, dtype=np.uint32)
+        vectors = np.ascontiguousarray(vectors, dtype=np.float32).reshape(ka.size, 9)
+        radius = np.ascontiguousarray(radius, dtype=np.float32)
+        out = np.empty((ka.size, 5), dtype=np.float32)
+        capi.check_kat(capi.kat_lib().rt_hip_kat_direct_aim(self._ctx, ka.size, ka.ctypes.data, kb.ctypes.data, vectors.ctypes.data, radius.ctypes.data, n_lights, out.ctypes.data))
+        return out
+
     def kat_exhaustive_math(self):
         """All 2^32 float bit patterns through the kernels' sqrt / reciprocal / reciprocal-sqrt sequences vs the
         compiler's correctly rounded expansions: ([mismatch counts], [first mismatching input bits])."""
