@@ -18,6 +18,9 @@ from tests.light_reference import table_of
 
 LIBRARY = ROOT / "tests" / "native" / "libdirect_reference.so"
 MAX_SAMPLED_LIGHTS = 256
+# the restatement's own events, in the order of direct_reference.cpp's own_event (direct_ref_render_census fills one count per name)
+OWN_EVENTS = ["vertex_aimed", "vertex_not_aimed", "shadow_visible", "shadow_occluded", "zero_word_k", "fold_below", "inside_light", "sampled_light_after_sampling_vertex", "sampled_light_after_other_vertex",
+              "light_on_primary", "chose_last_of_256", "first_vertex_aimed", "first_vertex_not_aimed", "sampled_light_after_other_vertex_later"]
 
 
 @functools.lru_cache(maxsize=None)
@@ -27,6 +30,11 @@ def lib() -> C.CDLL:
     l = C.CDLL(str(LIBRARY))
     l.direct_ref_render.restype = C.c_int
     l.direct_ref_render.argtypes = [C.POINTER(RtHipScene), C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.POINTER(RtHipPartition), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(OracleStats), C.c_void_p, C.c_uint32, C.c_int]
+    l.direct_ref_render_census.restype = C.c_int
+    l.direct_ref_render_census.argtypes = l.direct_ref_render.argtypes + [C.c_void_p, C.c_void_p, C.c_int64, C.c_uint32, C.c_void_p]
+    l.direct_ref_own_events.restype = C.c_int
+    l.direct_ref_own_events.argtypes = []
+    assert l.direct_ref_own_events() == len(OWN_EVENTS)
     l.direct_ref_count.restype = C.c_int
     l.direct_ref_count.argtypes = [C.POINTER(RtHipScene), C.c_void_p, C.c_uint32]
     l.direct_ref_vertex.restype = C.c_int
@@ -51,6 +59,26 @@ def render(scene: RtHipScene, width: int, height: int, emission=None, seed: int 
     if rc != 0:
         raise RuntimeError(f"direct_ref_render failed ({rc})")
     return rgba, rgb, stats.as_dict()
+
+
+def render_census(scene: RtHipScene, width: int, height: int, emission=None, seed: int = 1, threads: int = 0, sm_materials: bool = False, direct: bool = True, rare_rules: bool = True, watch=None):
+    """direct_ref_render_census: render()'s frame with both censuses — (rgba, rgb, stats dict, {oracle event: count}, {own event: count},
+    {own event: count of the watched sample} | None).  `watch` is (pixel, sample): the one sample whose own events are counted apart.
+    rare_rules=False is oracle.render_census's test-only mode (no re-draw of a zero vector, no approx_zero replacement) under this loop."""
+    rgba = np.zeros((height, width), dtype=np.uint32)
+    rgb = np.zeros((height, width, 3), dtype=np.float32)
+    stats = OracleStats()
+    table = table_of(emission, scene.n_materials)
+    census = np.zeros(len(oracle.CENSUS_EVENTS), dtype=np.uint64)
+    own = np.zeros(len(OWN_EVENTS), dtype=np.uint64)
+    watched = np.zeros(len(OWN_EVENTS), dtype=np.uint64)
+    mode = oracle.TRACE_ITERATIVE | (oracle.MATERIALS_SM if sm_materials else 0) | (0 if rare_rules else oracle.TEST_NO_RARE_RULES)
+    rc = lib().direct_ref_render_census(C.byref(scene), width, height, seed, mode, None, rgba.ctypes.data, rgb.ctypes.data, threads or oracle.default_threads(), C.byref(stats), table.ctypes.data, len(table), int(direct),
+                                        census.ctypes.data, own.ctypes.data, -1 if watch is None else watch[0], 0 if watch is None else watch[1], watched.ctypes.data)
+    if rc != 0:
+        raise RuntimeError(f"direct_ref_render_census failed ({rc})")
+    named = lambda names, counts: {name: int(n) for name, n in zip(names, counts)}
+    return rgba, rgb, stats.as_dict(), named(oracle.CENSUS_EVENTS, census), named(OWN_EVENTS, own), None if watch is None else named(OWN_EVENTS, watched)
 
 
 def count(scene: RtHipScene, emission) -> int:

@@ -5,6 +5,8 @@
 // Everything but the trace loop IS the oracle (this file includes oracle/cpu_ref.cpp through the tag-overload trick light_reference.cpp
 // explains), and the vertex rule IS rt_amd/csrc/direct_light_rules.hpp, the text the device runs.  It adds
 //     direct_ref_render   light_ref_render's arguments plus `direct` (0: the RT_HIP_FLAG_EMISSION frame; else the flag's frame)
+//     direct_ref_render_census   direct_ref_render with the oracle's branch census (note() fires inside the included oracle code under this
+//                         loop too) and the restatement's OWN events, counted here only — oracle/cpu_ref.* know nothing of them
 //     direct_ref_vertex   test only: the vertex rule N times at one point, visibility query included -> mean and mean square of the weight
 //     direct_ref_octahedral, direct_ref_aim   the rules header's two known answers as g++ compiles them (tests/test_gpu_direct_light.py)
 // With no sampled light the frame is light_ref_render's bit for bit (tests/test_direct_reference.py).
@@ -90,6 +92,46 @@ namespace
 		}
 	}
 
+	// ---- the restatement's own census (direct_ref_render_census; tests/direct_reference.py OWN_EVENTS has the names, in this order) ----
+	// Counted into atomics shared by the pool's threads, and only while a census render is in flight: with `own_on` false nothing below
+	// is touched.  The counting reads what the loop computes anyway (or recomputes it from the step's numerators) and changes none of it.
+	enum own_event
+	{
+		OWN_VERTEX_AIMED,	  // a lambert vertex's rule aimed: a shadow query ran
+		OWN_VERTEX_NOT_AIMED, // ... aimed at nothing: no shadow segment
+		OWN_SHADOW_VISIBLE,
+		OWN_SHADOW_OCCLUDED,
+		OWN_ZERO_WORD_K,	 // k.a == k.b == k.c == 0: light 0, the octahedral corner u = v = -1, the fold with sgn
+		OWN_FOLD_BELOW,		 // z < 0
+		OWN_INSIDE_LIGHT,	 // the vertex lies inside the light it chose
+		OWN_SAMPLED_LIGHT_AFTER_SAMPLING_VERTEX, // `return direct + 0`
+		OWN_SAMPLED_LIGHT_AFTER_OTHER_VERTEX,	 // a sampled light met behind a metal / dielectric vertex: throughput * E
+		OWN_LIGHT_ON_PRIMARY,					 // a primary ray met a light
+		OWN_CHOSE_LAST_OF_256,					 // choose_light gave 255 of 256
+		OWN_FIRST_VERTEX_AIMED,					 // the sample's FIRST vertex is lambert and aimed (what a watched sample is asked)
+		OWN_FIRST_VERTEX_NOT_AIMED,
+		OWN_SAMPLED_LIGHT_AFTER_OTHER_VERTEX_LATER, // ... behind a metal / dielectric vertex that FOLLOWS one that sampled: `sampled_before` had to be cleared
+		OWN_EVENTS
+	};
+	std::atomic<uint64_t> own_counts[OWN_EVENTS], watch_counts[OWN_EVENTS];
+	bool own_on = false;
+	// the one (pixel, sample) whose events are ALSO counted into watch_counts: its stream is known by its key and by where its counter
+	// stands when the trace loop is entered (after the jitter's step, which sample 0 does not draw)
+	struct
+	{
+		bool on = false;
+		uint32_t key = 0, counter = 0;
+	} watch;
+
+	inline void own(int event, bool watched)
+	{
+		if (!own_on)
+			return;
+		own_counts[event].fetch_add(1, std::memory_order_relaxed);
+		if (watched)
+			watch_counts[event].fetch_add(1, std::memory_order_relaxed);
+	}
+
 	[[maybe_unused]] vec3 (*const oracle_trace_iterative)(const frame&, ray, uint32_t, random_stream&, counters&, direct_ref::without_direct) = trace_iterative;
 
 	struct contract_inv_sqrt
@@ -99,19 +141,38 @@ namespace
 
 	// the vertex rule (§3.13) at x with the hit's stored normal: one generator step, the rules header, the unchanged closest-hit query.
 	// Returns whether the light is visible, with the weight and the light's emission E; counts the shadow segment.
-	inline bool vertex_rule(const rt_hip_scene& scene, vec3 x, vec3 nrm, random_stream& rng, counters& c, vec3& E, float& weight)
+	inline bool vertex_rule(const rt_hip_scene& scene, vec3 x, vec3 nrm, random_stream& rng, counters& c, vec3& E, float& weight, bool watched = false, bool first = false)
 	{
 		const random_stream::step k = rng.next_step();
 		const uint32_t n = static_cast<uint32_t>(sampled.size());
-		const sampled_light& light = sampled[rt_hip::direct_light::choose_light(k.c, n)];
+		const uint32_t chosen = rt_hip::direct_light::choose_light(k.c, n);
+		const sampled_light& light = sampled[chosen];
 		E = light.emission;
 		const rt_hip::direct_light::aim<vec3> a = rt_hip::direct_light::aim_at(k.a, k.b, x, nrm, light.centre, light.radius, n, contract_inv_sqrt());
 		weight = a.weight;
+		if (own_on) // the census: the rule's inner branches, from the numerators and the header's own functions once more
+		{
+			float l2;
+			const vec3 d0 = x - light.centre;
+			if (k.a == 0u && k.b == 0u && k.c == 0u)
+				own(OWN_ZERO_WORD_K, watched);
+			if (rt_hip::direct_light::octahedral_point<vec3>(k.a, k.b, l2).z < 0.0f)
+				own(OWN_FOLD_BELOW, watched);
+			if (rt_hip::direct_light::dot3(d0, d0) < light.radius * light.radius)
+				own(OWN_INSIDE_LIGHT, watched);
+			if (n == rt_hip::direct_light::max_sampled_lights && chosen == n - 1u)
+				own(OWN_CHOSE_LAST_OF_256, watched);
+			own(a.aimed ? OWN_VERTEX_AIMED : OWN_VERTEX_NOT_AIMED, watched);
+			if (first)
+				own(a.aimed ? OWN_FIRST_VERTEX_AIMED : OWN_FIRST_VERTEX_NOT_AIMED, watched);
+		}
 		if (!a.aimed)
 			return false;
 		c.segments++;
 		const hit_result shadow = closest_hit(scene, ray{ x, a.w });
-		return shadow && shadow.kind == 1u && shadow.index == light.sphere; // (no distance is compared)
+		const bool visible = shadow && shadow.kind == 1u && shadow.index == light.sphere; // (no distance is compared)
+		own(visible ? OWN_SHADOW_VISIBLE : OWN_SHADOW_OCCLUDED, watched);
+		return visible;
 	}
 
 	// trace_iterative of light_reference.cpp with §3.13's `direct` and `sampled_before`
@@ -120,6 +181,9 @@ namespace
 		vec3 throughput = { 1.0f, 1.0f, 1.0f };
 		vec3 direct = { 0.0f, 0.0f, 0.0f };
 		bool sampled_before = false;
+		const bool watched = own_on && watch.on && rng.function_key == watch.key && rng.counter == watch.counter;
+		bool first = true;		   // no vertex yet
+		bool ever_sampled = false; // (the census: a vertex of this path has run the rule)
 		while (true)
 		{
 			if (!(max_bounces--))
@@ -133,6 +197,14 @@ namespace
 				return direct + throughput * sky(r.dir.y);
 			if (is_light(hit.material))
 			{
+				if (first)
+					own(OWN_LIGHT_ON_PRIMARY, watched);
+				else if (hit.kind == 1u && is_sampled[hit.index])
+				{
+					own(sampled_before ? OWN_SAMPLED_LIGHT_AFTER_SAMPLING_VERTEX : OWN_SAMPLED_LIGHT_AFTER_OTHER_VERTEX, watched);
+					if (!sampled_before && ever_sampled)
+						own(OWN_SAMPLED_LIGHT_AFTER_OTHER_VERTEX_LATER, watched);
+				}
 				if (hit.kind == 1u && is_sampled[hit.index] && sampled_before)
 					return direct + vec3{ 0, 0, 0 }; // the previous vertex has accounted for this light
 				const float* const e = emission_table + static_cast<size_t>(hit.material) * 3u;
@@ -144,12 +216,14 @@ namespace
 			{
 				vec3 E;
 				float weight;
-				if (vertex_rule(*f.scene, r.at(hit.distance), hit.normal, rng, c, E, weight))
+				if (vertex_rule(*f.scene, r.at(hit.distance), hit.normal, rng, c, E, weight, watched, first))
 					direct = direct + ((throughput * m.attenuation) * E) * weight;
 				sampled_before = true;
+				ever_sampled = true;
 			}
 			else
 				sampled_before = false;
+			first = false;
 			vec3 attenuation;
 			ray scattered;
 			if (!scatter(f, r, hit, rng, scattered, attenuation))
@@ -170,6 +244,25 @@ namespace
 	}
 }
 
+namespace
+{
+	int render_with(const rt_hip_scene* scene, uint32_t width, uint32_t height, uint64_t seed, int mode, const rt_hip_partition* part, uint32_t* rgba8, float* rgb_f32, int n_threads, oracle_stats* stats, const float* emission_rgb,
+					uint32_t n_emission, int direct, uint64_t* census)
+	{
+		if (!scene || (mode & ORACLE_TRACE_RECURSIVE) || check_table(scene, emission_rgb, n_emission))
+			return 1;
+		emission_table = emission_rgb;
+		emission_rows = emission_rgb ? n_emission : 0u;
+		list_sampled_lights(*scene, direct != 0);
+		const int rc = render_frame(scene, width, height, seed, mode, part, rgba8, rgb_f32, n_threads, stats, census);
+		emission_table = nullptr;
+		emission_rows = 0;
+		sampled.clear();
+		is_sampled.clear();
+		return rc;
+	}
+}
+
 // light_ref_render's arguments plus `direct`.  1: a bad argument (as light_ref_render)
 extern "C" int direct_ref_render(const rt_hip_scene* scene,
 								 uint32_t width,
@@ -185,18 +278,63 @@ extern "C" int direct_ref_render(const rt_hip_scene* scene,
 								 uint32_t n_emission,
 								 int direct)
 {
-	if (!scene || (mode & ORACLE_TRACE_RECURSIVE) || check_table(scene, emission_rgb, n_emission))
-		return 1;
-	emission_table = emission_rgb;
-	emission_rows = emission_rgb ? n_emission : 0u;
-	list_sampled_lights(*scene, direct != 0);
-	const int rc = render_frame(scene, width, height, seed, mode, part, rgba8, rgb_f32, n_threads, stats, nullptr);
-	emission_table = nullptr;
-	emission_rows = 0;
-	sampled.clear();
-	is_sampled.clear();
+	return render_with(scene, width, height, seed, mode, part, rgba8, rgb_f32, n_threads, stats, emission_rgb, n_emission, direct, nullptr);
+}
+
+// direct_ref_render with the censuses.  census: ORACLE_CENSUS_EVENTS words, the oracle's events (cpu_ref.h) under this trace loop;
+// own_census: direct_ref_own_events() words, the events counted in this file.  watch_pixel >= 0: watch_census (as many words) gets the
+// own events of the ONE sample (watch_pixel, watch_sample), so that a test can ask what a constructed vertex did.  With `census` null the
+// call IS direct_ref_render (nothing is counted; the own arrays, if given, are zeroed).  ORACLE_TEST_NO_RARE_RULES in `mode` is honoured as
+// oracle_render_census honours it — render_frame reads it where a census is open — so sensitivity can be shown under the direct loop too.
+extern "C" int direct_ref_render_census(const rt_hip_scene* scene,
+										uint32_t width,
+										uint32_t height,
+										uint64_t seed,
+										int mode,
+										const rt_hip_partition* part,
+										uint32_t* rgba8,
+										float* rgb_f32,
+										int n_threads,
+										oracle_stats* stats,
+										const float* emission_rgb,
+										uint32_t n_emission,
+										int direct,
+										uint64_t* census,
+										uint64_t* own_census,
+										int64_t watch_pixel,
+										uint32_t watch_sample,
+										uint64_t* watch_census)
+{
+	for (int e = 0; e < OWN_EVENTS; e++)
+	{
+		own_counts[e] = 0, watch_counts[e] = 0;
+		if (own_census)
+			own_census[e] = 0;
+		if (watch_census)
+			watch_census[e] = 0;
+	}
+	own_on = census != nullptr;
+	watch.on = own_on && watch_pixel >= 0 && watch_census;
+	if (watch.on)
+	{
+		const random_stream at_entry(make_frame_keys(seed), static_cast<uint32_t>(watch_pixel), watch_sample);
+		watch.key = at_entry.function_key;
+		watch.counter = at_entry.counter + (watch_sample ? at_entry.stride : 0u); // (sample 0 draws no jitter)
+	}
+	const int rc = render_with(scene, width, height, seed, mode, part, rgba8, rgb_f32, n_threads, stats, emission_rgb, n_emission, direct, census);
+	for (int e = 0; own_on && e < OWN_EVENTS; e++)
+	{
+		if (own_census)
+			own_census[e] = own_counts[e].load();
+		if (watch_census)
+			watch_census[e] = watch_counts[e].load();
+	}
+	own_on = false;
+	watch.on = false;
 	return rc;
 }
+
+extern "C" int direct_ref_own_events() { return OWN_EVENTS; }
 
 // how many sampled lights the scene has under the table (what the device's list must hold)
 extern "C" int direct_ref_count(const rt_hip_scene* scene, const float* emission_rgb, uint32_t n_emission)

@@ -214,3 +214,81 @@ def test_segments_count_shadow_queries_in_longer_paths():
     _, _, direct = direct_ref.render(pod, 48, 27, light_ref.LIGHTS_TABLE, seed=7, want_rgb=False)
     _, _, implicit = light_ref.render(pod, 48, 27, light_ref.LIGHTS_TABLE, seed=7, want_rgb=False)
     assert direct["segments"] > implicit["segments"] and direct["primary_samples"] == implicit["primary_samples"]
+
+
+# ---- the census of the restatement (direct_ref_render_census) ---------------------------------------------------------------------------
+def without_seconds(stats):
+    return {k: v for k, v in stats.items() if k != "seconds"}
+
+
+@pytest.mark.parametrize("sm", [False, True])
+def test_a_census_render_is_direct_ref_renders_bytes(sm):
+    """lights.toml at 64x36: frame, float mean and stats of direct_ref_render byte for byte — and through the C entry point with the
+    census pointer null it is that function too (nothing is counted)."""
+    import ctypes as C
+
+    pod = light_ref.lights_scene().describe(64, 36)
+    rgba, rgb, stats = direct_ref.render(pod, 64, 36, light_ref.LIGHTS_TABLE, seed=5, sm_materials=sm)
+    c_rgba, c_rgb, c_stats, counts, own, watched = direct_ref.render_census(pod, 64, 36, light_ref.LIGHTS_TABLE, seed=5, sm_materials=sm)
+    assert rgba.tobytes() == c_rgba.tobytes() and rgb.tobytes() == c_rgb.tobytes() and without_seconds(stats) == without_seconds(c_stats)
+    assert list(counts) == oracle.CENSUS_EVENTS and list(own) == direct_ref.OWN_EVENTS and watched is None
+    n_rgba, n_rgb, n_stats = np.zeros_like(rgba), np.zeros_like(rgb), oracle.OracleStats()
+    own_words = np.full(len(direct_ref.OWN_EVENTS), 7, dtype=np.uint64)
+    table = light_ref.LIGHTS_TABLE
+    rc = direct_ref.lib().direct_ref_render_census(C.byref(pod), 64, 36, 5, oracle.MATERIALS_SM if sm else 0, None, n_rgba.ctypes.data, n_rgb.ctypes.data, 2, C.byref(n_stats), table.ctypes.data, len(table), 1, None,
+                                                   own_words.ctypes.data, -1, 0, None)
+    assert rc == 0 and rgba.tobytes() == n_rgba.tobytes() and rgb.tobytes() == n_rgb.tobytes() and without_seconds(stats) == without_seconds(n_stats.as_dict())
+    assert (own_words == 0).all()
+    # bookkeeping the counts must satisfy: every segment is a sample's first, follows a scatter that went on, or is a shadow query
+    scatters = counts["lambert_rule"] + counts["lambert_near_zero"] + counts["lambert_ordinary"] + counts["metal_scattered"] + counts["dielectric_total_internal"] + counts["dielectric_reflected"] + counts["dielectric_refracted"]
+    assert stats["segments"] == stats["primary_samples"] + scatters - counts["out_of_bounces"] + own["vertex_aimed"]
+    assert own["vertex_aimed"] == own["shadow_visible"] + own["shadow_occluded"]
+    # every lambert vertex that goes on to scatter ran the rule once (a lambert scatter never absorbs)
+    assert own["vertex_aimed"] + own["vertex_not_aimed"] == counts["lambert_rule"] + counts["lambert_near_zero"] + counts["lambert_ordinary"]
+    for event in ("vertex_aimed", "vertex_not_aimed", "shadow_visible", "shadow_occluded", "fold_below", "sampled_light_after_sampling_vertex", "light_on_primary", "first_vertex_aimed", "first_vertex_not_aimed"):
+        assert own[event] > 0, event
+    assert own["inside_light"] == 0 and own["chose_last_of_256"] == 0 and own["zero_word_k"] == 0
+    assert (own["sampled_light_after_other_vertex"] > 0) or not sm  # (behind the glass sphere under the sm table, behind the brass one under both)
+
+
+def test_the_census_of_a_frame_without_the_flag_counts_no_vertex():
+    """`direct` off: light_ref_render's frame, the oracle's events under the loop, and none of the rule's."""
+    pod = light_ref.lights_scene().describe(64, 36)
+    want_rgba, want_rgb, want = light_ref.render(pod, 64, 36, light_ref.LIGHTS_TABLE, seed=5)
+    rgba, rgb, stats, counts, own, _ = direct_ref.render_census(pod, 64, 36, light_ref.LIGHTS_TABLE, seed=5, direct=False)
+    assert rgba.tobytes() == want_rgba.tobytes() and rgb.tobytes() == want_rgb.tobytes() and stats["segments"] == want["segments"]
+    assert counts["lambert_ordinary"] > 0 and own["light_on_primary"] > 0
+    assert all(own[e] == 0 for e in direct_ref.OWN_EVENTS if e != "light_on_primary"), own
+
+
+def test_the_watched_sample_is_one_sample_of_the_frame():
+    """watch = (pixel, sample): the own events of that sample alone — at most one first vertex, and summed over every (pixel, sample) of a
+    small frame the watched counts are the frame's."""
+    width, height, spp = 6, 4, 3
+    pod = light_ref.lights_scene(spp=spp).describe(width, height)
+    _, _, _, _, own, _ = direct_ref.render_census(pod, width, height, light_ref.LIGHTS_TABLE, seed=8)
+    total = dict.fromkeys(direct_ref.OWN_EVENTS, 0)
+    for pixel in range(width * height):
+        for sample in range(spp):
+            _, _, _, _, again, watched = direct_ref.render_census(pod, width, height, light_ref.LIGHTS_TABLE, seed=8, watch=(pixel, sample), threads=1)
+            assert again == own and watched["first_vertex_aimed"] + watched["first_vertex_not_aimed"] + watched["light_on_primary"] <= 1
+            for event, n in watched.items():
+                total[event] += n
+    assert total == own and own["vertex_aimed"] > 0
+
+
+def test_the_rare_rules_switch_is_honoured_under_the_direct_loop():
+    """ORACLE_TEST_NO_RARE_RULES reaches render_frame through direct_ref_render_census as through oracle_render_census: lambert's
+    approx_zero replacement off changes a frame whose plane faces a unit vector exactly; direct_ref_render ignores the bit."""
+    import ctypes as C
+
+    from tests import light_rare_cases as lrc
+
+    case = lrc.case("direct_approx_zero_exact_lamp_in_front")
+    pod, table = case.pod(), case.table()
+    on = direct_ref.render_census(pod, lrc.W, lrc.H, table, seed=case.seed)
+    off = direct_ref.render_census(pod, lrc.W, lrc.H, table, seed=case.seed, rare_rules=False)
+    assert on[3]["lambert_rule"] == off[3]["lambert_rule"] == 1 and on[1].tobytes() != off[1].tobytes()
+    rgba, rgb = np.zeros((lrc.H, lrc.W), dtype=np.uint32), np.zeros((lrc.H, lrc.W, 3), dtype=np.float32)
+    assert direct_ref.lib().direct_ref_render(C.byref(pod), lrc.W, lrc.H, case.seed, oracle.TEST_NO_RARE_RULES, None, rgba.ctypes.data, rgb.ctypes.data, 1, None, table.ctypes.data, len(table), 1) == 0
+    assert rgb.tobytes() == on[1].tobytes()

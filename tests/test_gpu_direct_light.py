@@ -185,6 +185,32 @@ def test_the_list_follows_the_table_and_the_scene(tracer, camera):
     assert np.array_equal(first, again)
 
 
+def test_a_multi_gpu_context_builds_the_list_on_every_member(camera):
+    """rt_hip_create_multi with two members — over two devices where two are visible, else twice the one device (peer copies, as
+    tests/test_gpu_lights.py does): the sampled-light list is built per member (§3.13), so the assembled frame is the restatement's whole
+    frame and both members ran the resident kernel; and it FOLLOWS the table and the scene on every member — another table, then a scene
+    with another sphere count, each frame again the restatement's."""
+    width, height = 96, 54
+    pod = light_ref.lights_scene().describe(width, height)
+    other = np.zeros((5, 3), dtype=np.float32)
+    other[2] = (0.5, 2, 0.5)  # the clay sphere glows instead
+    wide = rt_amd.Scene.named("basic").describe(width, height)
+    two_spheres = light_ref.scene_pod(wide, spheres=[(0, 0.5, 0, 0.5, 1), (1, 0.5, 0.5, 0.5, 0)], planes=[(0, 1, 0, 0, 0)])
+    assert two_spheres.n_spheres != pod.n_spheres and direct_ref.count(pod, other) == 1 and direct_ref.count(two_spheres, one_light(which=1)) == 1
+    two = rt_amd.renderer.device_count() >= 2
+    with rt_amd.HipRayTracer(devices=[0, 1] if two else [0, 0], peer_copy=not two) as multi:
+        frames = []
+        for scene, table in ((pod, light_ref.LIGHTS_TABLE), (pod, other), (two_spheres, one_light(which=1)), (pod, light_ref.LIGHTS_TABLE)):
+            want_rgba, _, want = direct_ref.render(scene, width, height, table, seed=19, want_rgb=False)
+            multi.set_emission(table)
+            rgba, _, stats = multi.render(scene, width, height, seed=19, flags=DIRECT)
+            assert np.array_equal(rgba, want_rgba), f"{(rgba != want_rgba).sum()} of {rgba.size} pixels differ from the restatement's"
+            assert stats["segments"] == want["segments"]
+            assert all(multi.member_stats(rank)["kernel"] == "resident" for rank in range(2))
+            frames.append(rgba)
+        assert (frames[0] != frames[1]).mean() > 0.05 and np.array_equal(frames[0], frames[3])
+
+
 def test_refusals_name_the_flag_and_launch_nothing(tracer):
     import torch
 

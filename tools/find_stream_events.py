@@ -14,7 +14,14 @@ One position in 2^32 per (seed, pixel).  The tuples worth keeping are those a sm
     step 3 of a sample > 0   ... at the SECOND scatter (if the first took one step)                   kind "redraw_second_scatter"
     step 1 / 2 of sample 0   sample 0 draws no jitter: its first / second scatter                     kinds as above
 About 3e-8 of the (seed, pixel) pairs qualify; the search below runs over whole blocks of seeds in numpy, a few million pairs per
-second.  Recorded results only: the fixture holds no code."""
+second.  Recorded results only: the fixture holds no code.
+
+--direct keeps steps 4 and 5 of a sample > 0 as well and writes tests/golden/stream_events_direct.json, a fixture of its own (the one
+above is not regenerated).  Under RT_HIP_FLAG_DIRECT_LIGHT a lambert vertex draws a step k before its scatter's u, so
+a sample's steps run jitter, k, u, k, u over two lambert vertices and jitter, u, k, u over a metal and a lambert one:
+    step 4 of a sample > 0   kind "zero_word_step_4": the second scatter's u behind a metal first vertex (or the second vertex's k)
+    step 5 of a sample > 0   kind "zero_word_step_5": the second scatter's u behind two lambert vertices
+What such a word IS in a given scene is for the scene's census to say (tests/test_light_rare_branches.py)."""
 import argparse
 import json
 import sys
@@ -70,7 +77,15 @@ def kind_of(sample, step):
     return {0: "zero_jitter", 1: "redraw_first_scatter", 2: "redraw_second_scatter"}.get(scatter)
 
 
-def search(width, height, max_sample, first_seed, seeds, block=1 << 16):
+DIRECT_KINDS = ("zero_word_step_4", "zero_word_step_5")
+
+
+def direct_kind_of(sample, step):
+    """the kinds --direct adds: steps 4 and 5 of a sample > 0, named by their place in the stream"""
+    return f"zero_word_step_{step}" if sample > 0 and step in (4, 5) else None
+
+
+def search(width, height, max_sample, first_seed, seeds, block=1 << 16, max_step=3, kind_of=kind_of):
     pixels = np.arange(width * height, dtype=U32)
     found = []
     with np.errstate(over="ignore"):
@@ -78,7 +93,7 @@ def search(width, height, max_sample, first_seed, seeds, block=1 << 16):
             block_seeds = np.arange(start, min(start + block, first_seed + seeds), dtype=np.uint64)
             position = zero_word_positions(block_seeds, pixels)
             sample, step = position >> U32(12), position & U32(4095)
-            keep = (sample <= U32(max_sample)) & (step >= U32(1)) & (step <= U32(3))
+            keep = (sample <= U32(max_sample)) & (step >= U32(1)) & (step <= U32(max_step))
             for i, j in zip(*np.nonzero(keep)):
                 kind = kind_of(int(sample[i, j]), int(step[i, j]))
                 if kind is not None:
@@ -102,11 +117,16 @@ def main():
     ap.add_argument("--first-seed", type=int, default=0)
     ap.add_argument("--seeds", type=int, default=8_000_000)
     ap.add_argument("--per-kind", type=int, default=4, help="how many entries of each kind the fixture keeps (the lowest seeds)")
-    ap.add_argument("--out", default=str(ROOT / "tests" / "golden" / "stream_events.json"))
+    ap.add_argument("--direct", action="store_true", help="keep steps 4 and 5 of a sample > 0 instead, for tests/golden/stream_events_direct.json")
+    ap.add_argument("--out", default=None, help="default: tests/golden/stream_events.json, with --direct tests/golden/stream_events_direct.json")
     args = ap.parse_args()
-    found = search(args.width, args.height, args.max_sample, args.first_seed, args.seeds)
+    args.out = args.out or str(ROOT / "tests" / "golden" / ("stream_events_direct.json" if args.direct else "stream_events.json"))
+    if args.direct:
+        found = search(args.width, args.height, args.max_sample, args.first_seed, args.seeds, max_step=5, kind_of=direct_kind_of)
+    else:
+        found = search(args.width, args.height, args.max_sample, args.first_seed, args.seeds)
     kept = []
-    for kind in ("redraw_first_scatter", "redraw_second_scatter", "zero_jitter"):
+    for kind in DIRECT_KINDS if args.direct else ("redraw_first_scatter", "redraw_second_scatter", "zero_jitter"):
         of_kind = [e for e in found if e["kind"] == kind]
         print(f"{kind}: {len(of_kind)} found in {args.seeds} seeds x {args.width * args.height} pixels")
         kept += of_kind[: args.per_kind]
