@@ -853,6 +853,8 @@ RT_HIP_API rt_hip_status rt_hip_adaptive_update_device(rt_hip_ctx* ctx,
  *               words [4P, 7P)  pass_sum  scratch, rewritten by every pass for the pixels it traced
  *               words [7P, 9P)  moments   S1, S2
  *   d_rgba8, d_rgb_f32 (nullable), d_active_pixels (nullable): as rt_hip_adaptive_update_device's outputs.
+ *   rt_hip_stats_fetch after it: THIS PASS — primary_samples = pixels that were active x n_samples (counted on the device by the
+ *   update step: the host does not know the state words), segments = the pass's.
  */
 RT_HIP_API rt_hip_status rt_hip_adaptive_pass_device(rt_hip_ctx* ctx,
 									uint32_t width,

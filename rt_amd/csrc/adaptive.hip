@@ -49,10 +49,10 @@ namespace
 
 	__global__ __launch_bounds__(block_threads) void adaptive_update(const uint32_t width, const uint32_t height, const uint32_t pass_samples, const uint32_t first_pass, const uint32_t whole_pass, const rt_hip_adaptive_params k,
 																	   const float* __restrict__ accum, const float* __restrict__ pass_sum, const float* __restrict__ moments, const uint32_t* __restrict__ state, float* __restrict__ moments_out, uint32_t* __restrict__ state_out, uint32_t* __restrict__ out_rgba, float* __restrict__ out_rgb,
-																	   uint32_t* __restrict__ active)
+																	   uint32_t* __restrict__ active, uint32_t* __restrict__ traced)
 	{
 		__shared__ uint32_t verdicts[halo][halo]; // 1: converged, or outside the frame
-		__shared__ uint32_t wave_active[block_threads / 64u];
+		__shared__ uint32_t wave_active[block_threads / 64u], wave_traced[block_threads / 64u];
 		const int32_t x0 = static_cast<int32_t>(blockIdx.x * tile), y0 = static_cast<int32_t>(blockIdx.y * tile);
 		const uint32_t tx = threadIdx.x & (tile - 1u), ty = threadIdx.x / tile;
 		const uint32_t x = blockIdx.x * tile + tx, y = blockIdx.y * tile + ty;
@@ -108,37 +108,56 @@ namespace
 		// (One per wave, as reproject_frame counts, was measured first: 32 400 atomics on one address at 1920 x 1080 serialise at about
 		// 12 ns each and made this kernel take 380 us with every pixel active against 187 us with most of them stopped —
 		// profiles/r16/kernel_stats_first.txt.)
+		// `traced` (nullable), counted the same way: the pixels that were active IN this pass — what the render kernel in front of this
+		// one traced (state_word is 0 in the first pass), for the stats of rt_hip_adaptive_pass_device.
 		const unsigned long long going_on = __ballot(still_active); // (every lane of the wave is here)
+		const unsigned long long were_active = __ballot(alive && !adaptive::is_stopped(state_word));
 		if ((threadIdx.x & 63u) == 0u)
-			wave_active[threadIdx.x >> 6] = static_cast<uint32_t>(__popcll(going_on));
-		__syncthreads();
-		if (active && threadIdx.x == 0u)
 		{
-			uint32_t total = 0;
+			wave_active[threadIdx.x >> 6] = static_cast<uint32_t>(__popcll(going_on));
+			wave_traced[threadIdx.x >> 6] = static_cast<uint32_t>(__popcll(were_active));
+		}
+		__syncthreads();
+		if ((active || traced) && threadIdx.x == 0u)
+		{
+			uint32_t total = 0, total_traced = 0;
 			for (uint32_t w = 0; w < block_threads / 64u; w++)
-				total += wave_active[w];
-			if (total)
+				total += wave_active[w], total_traced += wave_traced[w];
+			if (active && total)
 				atomicAdd(active, total);
+			if (traced && total_traced)
+				atomicAdd(traced, total_traced);
 		}
 	}
 
 	// one update step on device buffers (everything checked by the caller; ctx->device is current)
 	rt_hip_status launch_update(rt_hip_ctx* ctx, uint32_t width, uint32_t height, uint32_t pass_samples, bool first_pass, bool whole_pass, const rt_hip_adaptive_params& params, const float* d_accum, const float* d_pass_sum, float* d_moments, uint32_t* d_state,
-								uint32_t* d_rgba8, float* d_rgb, uint32_t* d_active, hipStream_t stream)
+								uint32_t* d_rgba8, float* d_rgb, uint32_t* d_active, hipStream_t stream, bool count_traced = false)
 	{
 		if (d_active)
 			RT_HIP_TRY(hipMemsetAsync(d_active, 0, sizeof(uint32_t), stream));
 		const size_t pixels = static_cast<size_t>(width) * height;
-		RT_HIP_TRY(ctx->adaptive.scratch.reserve(pixels * 3u * sizeof(uint32_t)));
+		RT_HIP_TRY(ctx->adaptive.scratch.reserve((pixels * 3u + 1u) * sizeof(uint32_t))); // (the last word: the pixels traced, where they are counted)
 		uint32_t* const state_out = ctx->adaptive.scratch.as<uint32_t>();
 		float* const moments_out = ctx->adaptive.scratch.as<float>() + pixels;
+		uint32_t* const d_traced = count_traced ? state_out + pixels * 3u : nullptr;
+		if (d_traced)
+			RT_HIP_TRY(hipMemsetAsync(d_traced, 0, sizeof(uint32_t), stream));
 		const dim3 grid((width + tile - 1u) / tile, (height + tile - 1u) / tile);
 		hipLaunchKernelGGL(adaptive_update, grid, dim3(block_threads), 0, stream, width, height, pass_samples, first_pass ? 1u : 0u, whole_pass ? 1u : 0u, params, d_accum, d_pass_sum, d_moments, d_state, moments_out, state_out, d_rgba8, d_rgb,
-						   d_active);
+						   d_active, d_traced);
 		RT_HIP_TRY(hipGetLastError());
 		RT_HIP_TRY(hipMemcpyAsync(d_state, state_out, pixels * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
 		if (whole_pass)
 			RT_HIP_TRY(hipMemcpyAsync(d_moments, moments_out, pixels * 2u * sizeof(float), hipMemcpyDeviceToDevice, stream));
+		if (d_traced)
+		{
+			// the count follows the pass's counters to the host on the same stream; fetch_member_stats (render.hip) waits for both
+			RT_HIP_TRY(ctx->adaptive.traced.reserve(sizeof(uint32_t)));
+			RT_HIP_TRY(hipMemcpyAsync(ctx->adaptive.traced.ptr, d_traced, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+			RT_HIP_TRY(hipEventRecord(ctx->counters_copied, stream));
+			ctx->adaptive.traced_pass_samples = pass_samples;
+		}
 		return ok();
 	}
 
@@ -165,7 +184,7 @@ namespace
 
 	// render + update (everything checked by the caller)
 	rt_hip_status adaptive_pass(rt_hip_ctx* ctx, uint32_t width, uint32_t height, uint64_t seed, uint32_t flags, uint32_t first_sample, uint32_t n_samples, bool whole_pass, const rt_hip_adaptive_params& params, float* d_block,
-								uint32_t* d_rgba8, float* d_rgb_f32, uint32_t* d_active, hipStream_t stream, bool keep_stats)
+								uint32_t* d_rgba8, float* d_rgb_f32, uint32_t* d_active, hipStream_t stream, bool keep_stats, bool count_traced = false)
 	{
 		render_pass pass = { first_sample, n_samples, d_block };
 		pass.adaptive = true;
@@ -173,7 +192,7 @@ namespace
 		if (const rt_hip_status st = render_device(ctx, width, height, seed, flags & pass_flag_mask, nullptr, d_rgba8, nullptr, stream, false, keep_stats, false, &pass))
 			return st;
 		const block_view b = view_of(d_block, static_cast<size_t>(width) * height);
-		return launch_update(ctx, width, height, n_samples, first_sample == 0u, whole_pass, params, b.accum, b.pass_sum, b.moments, b.state, d_rgba8, d_rgb_f32, d_active, stream);
+		return launch_update(ctx, width, height, n_samples, first_sample == 0u, whole_pass, params, b.accum, b.pass_sum, b.moments, b.state, d_rgba8, d_rgb_f32, d_active, stream, count_traced && keep_stats);
 	}
 }
 }
@@ -304,8 +323,9 @@ extern "C" rt_hip_status rt_hip_adaptive_pass_device(rt_hip_ctx* ctx,
 		return fail(RT_HIP_INVALID_ARGUMENT, "rt_hip_adaptive_pass_device: an output overlaps d_block");
 	try
 	{
-		// (RT_HIP_FLAG_STATS asks for what this call keeps anyway, as rt_hip_render_pass_device does)
-		return adaptive_pass(ctx, width, height, seed, flags, first_sample, n_samples, whole_pass, p, d_block, d_rgba8, d_rgb_f32, d_active_pixels, static_cast<hipStream_t>(stream), true);
+		// (RT_HIP_FLAG_STATS asks for what this call keeps anyway, as rt_hip_render_pass_device does; which pixels were active only the
+		// device knows: the update kernel counts them for the stats' primary_samples)
+		return adaptive_pass(ctx, width, height, seed, flags, first_sample, n_samples, whole_pass, p, d_block, d_rgba8, d_rgb_f32, d_active_pixels, static_cast<hipStream_t>(stream), true, true);
 	}
 	catch (const std::exception& e)
 	{

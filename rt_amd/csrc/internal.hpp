@@ -221,6 +221,8 @@ namespace rt_hip
 		device_buffer active;		 // one word: the pixels still active after the last pass
 		device_buffer scratch;		 // the update kernel's output words on their way back (12 bytes per pixel; the device-level call's too)
 		pinned_buffer staging;		 // the results' landing place on the host
+		pinned_buffer traced;		 // one word: the pixels the last rt_hip_adaptive_pass_device traced, for its stats
+		uint32_t traced_pass_samples = 0; // != 0: the most recent launch was that call's, a pass of so many samples (render_device clears it)
 		std::vector<uint32_t> frame; // the complete frame, kept on the host for calls that come after it
 		hipEvent_t end = nullptr;	 // behind the update (passes that keep stats)
 		void release()
@@ -228,6 +230,8 @@ namespace rt_hip
 			for (device_buffer* b : { &block, &active, &scratch })
 				b->release();
 			staging.release();
+			traced.release();
+			traced_pass_samples = 0;
 			if (end)
 				(void)hipEventDestroy(end);
 			end = nullptr;

@@ -276,6 +276,7 @@ rt_hip_status render_device(rt_hip_ctx* ctx, uint32_t width, uint32_t height, ui
 		RT_HIP_TRY(hipEventRecord(ctx->counters_copied, s));
 	}
 	ctx->render_recorded = keep_stats;
+	ctx->adaptive.traced_pass_samples = 0; // (rt_hip_adaptive_pass_device sets it behind its update)
 	ctx->stats.kernel_variant = variant;
 	ctx->stats.primary_samples = static_cast<uint64_t>(f.local_rows) * width * ((flags & RT_HIP_FLAG_PREVIEW) ? 1u : (pass ? pass->n_samples : f.samples_per_pixel));
 	if (!keep_stats) // the counters of this frame were not kept: nothing stale may be reported for it
@@ -328,6 +329,9 @@ namespace rt_hip
 			ctx->stats.segments = segments;
 			ctx->stats.sphere_tests = segments * ctx->scene.n_spheres;
 			ctx->stats.plane_tests = segments * ctx->scene.n_planes;
+			// a device-level adaptive pass: the pixels that were active, counted by the update kernel, x the pass's samples
+			if (ctx->adaptive.traced_pass_samples)
+				ctx->stats.primary_samples = static_cast<uint64_t>(*ctx->adaptive.traced.as<uint32_t>()) * ctx->adaptive.traced_pass_samples;
 #ifdef RT_HIP_BVH_CHECK // (experiment builds: tools/bvh_sweep.py --check reads this line)
 			std::fprintf(stderr, "bvh_check: %llu queries, %llu disagreements\n", ctx->counters_host->bvh_checked, ctx->counters_host->bvh_disagreements);
 #endif
