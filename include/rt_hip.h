@@ -775,6 +775,92 @@ RT_HIP_API rt_hip_status rt_hip_render_temporal(rt_hip_ctx* ctx,
 									rt_hip_stats* stats,
 									rt_hip_temporal_info* out_info);
 
+/* ---- guided upsampling: trace a smaller frame, rebuild the full one ------------------------------------------------------- */
+/*
+ * Every entry point above traces every pixel of the full-size frame.  These trace FEWER PIXELS: a low frame of w x h pixels seen
+ * through the same matrix covers exactly the view of the W x H frame (the NDC mapping depends on the size through 2 / width and
+ * 2 / height alone), and a joint-bilateral kernel rebuilds the full frame from it: every full pixel takes its four bilinear low
+ * taps, each weighted by how well the low guide record of the tap agrees with the FULL guide record of the pixel (normal, depth,
+ * albedo: the denoiser's terms), so that a silhouette of the full frame stays a silhouette.  A full pixel none of whose taps saw
+ * its surface — a thin sphere, a silhouette sliver — is an ORPHAN: it takes the plain bilinear mean and is counted; orphans are the
+ * known limit of the method, they are reported, not re-traced.  A contract of its own: exact integer geometry,
+ * + - x, correctly rounded division and compare-and-select in a fixed order, so that the device's result equals a serial CPU
+ * restatement bit for bit — it is NOT the reference's arithmetic (the reference has no upsampler), and a rebuilt frame is no path
+ * tracer's frame.  No speed and no quality is promised.
+ * Additions to ABI 6 (RT_HIP_ABI_VERSION stays 6): a caller that may meet an older library looks them up with dlsym.
+ */
+typedef struct rt_hip_upsample_params
+{
+	uint32_t normal_squarings; /* 0 .. 8: the normal term is max(0, n_p . n_q) squared this many times */
+	float sigma_albedo;		   /* > 0: width of the albedo term */
+	float sigma_depth;		   /* > 0: width of the depth term, relative to the deeper of the two hits */
+	float min_weight;		   /* (0, 1]: a pixel whose guided weights sum to less is an orphan */
+} rt_hip_upsample_params;
+
+/* the defaults a NULL `params` stands for (DESIGN.md §3.14 has the table min_weight was chosen from); pure host code */
+RT_HIP_API rt_hip_status rt_hip_upsample_default_params(rt_hip_upsample_params* out_params);
+
+/* the low frame rt_hip_render_upscaled traces for `factor` (1 .. 4): ceil(width / factor) x ceil(height / factor); pure host code */
+RT_HIP_API rt_hip_status rt_hip_upsample_low_size(uint32_t width, uint32_t height, uint32_t factor, uint32_t* out_low_width, uint32_t* out_low_height);
+
+/*
+ * The reconstruction, a pure image operation on DEVICE buffers: d_rgb_low (3 * low_width * low_height floats, a low frame's float
+ * mean), d_guide_low and d_guide_full (rt_hip_guide_device's records at the two sizes, 16-byte aligned) give d_rgb_out
+ * (3 * width * height floats, optional) and d_rgba8_out (width * height packed pixels: square root, clamp and pack as
+ * rt_hip_render finishes a pixel; optional) — not both NULL — and, optionally, the number of orphans (one word, overwritten).
+ * 1 <= low_width <= width <= 2^22, likewise the heights; the two sizes need not be in a whole ratio.  No output may overlap an
+ * input or another output.  params == NULL: the defaults.  It reads no scene: any buffers of the right shape will do.
+ * Asynchronous on `stream`; on a multi-GPU, rank or frame-group context the root member answers.
+ */
+RT_HIP_API rt_hip_status rt_hip_upsample_device(rt_hip_ctx* ctx,
+									uint32_t width,
+									uint32_t height,
+									uint32_t low_width,
+									uint32_t low_height,
+									const float* d_rgb_low,
+									const float* d_guide_low,
+									const float* d_guide_full,
+									const rt_hip_upsample_params* params, /* NULL = defaults */
+									float* d_rgb_out,					  /* nullable */
+									uint32_t* d_rgba8_out,				  /* nullable, not both NULL */
+									uint32_t* d_orphans,				  /* nullable */
+									void* stream);
+
+typedef struct rt_hip_upscale_info
+{
+	uint32_t low_width, low_height; /* the traced frame */
+	uint32_t orphans;				/* full pixels that fell back to the plain bilinear mean */
+	uint32_t pixels;				/* width x height */
+} rt_hip_upscale_info;
+
+/*
+ * Drop-in level: one call is one frame.  The scene is uploaded by fingerprint as in rt_hip_render; the one-shot frame is traced at
+ * ceil(width / factor) x ceil(height / factor) with the scene's own matrix, seed and samples into a device float mean, by the
+ * launch rt_hip_render_device makes; the guide is built at the low and at the full size; with `filter` the a-trous filter of
+ * rt_hip_denoise_device runs on the LOW mean with the low guide; the full frame is rebuilt, packed as rt_hip_render packs, and
+ * copied into the caller's plain HOST memory: pixels_rgba8888 (width * height) and, optionally, rgb_f32 (3 * width * height).
+ * The scratch (low mean, two guides, full outputs) belongs to the context, is grown on demand and freed with it.  It is state of
+ * its own: a progressive accumulation in flight, the temporal history and the denoiser's kept guide are left alone.
+ *   factor    2 .. 4
+ *   stats     optional: the traced LOW frame's (primary_samples = low_width x low_height x samples_per_pixel); render_ms
+ *             additionally holds guides, filter and upsampling.
+ * Flags: RT_HIP_FLAG_SM_MATERIALS, RT_HIP_FLAG_BVH, RT_HIP_FLAG_BVH_DEVICE_BUILD, RT_HIP_FLAG_TRACE_BOXES and RT_HIP_FLAG_STATS;
+ * every other flag is refused with RT_HIP_UNSUPPORTED and its name.  Contexts from rt_hip_create only.
+ */
+RT_HIP_API rt_hip_status rt_hip_render_upscaled(rt_hip_ctx* ctx,
+									const rt_hip_scene* scene,
+									uint32_t* pixels_rgba8888,
+									uint32_t width,
+									uint32_t height,
+									uint64_t seed,
+									uint32_t flags,
+									uint32_t factor,
+									const rt_hip_upsample_params* upsample, /* NULL = defaults */
+									const rt_hip_denoise_params* filter,	/* NULL = no filter on the low frame */
+									float* rgb_f32,							/* nullable */
+									rt_hip_stats* stats,
+									rt_hip_upscale_info* out_info);
+
 /* ---- adaptive sampling: passes that stop converged pixels ---------------------------------------------------------------- */
 /*
  * rt_hip_render_progressive gives every pixel the same number of samples.  An ADAPTIVE accumulation is a progressive accumulation

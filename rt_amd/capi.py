@@ -177,6 +177,24 @@ class RtHipTemporalInfo(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class RtHipUpsampleParams(C.Structure):
+    """``rt_hip_upsample_params`` (include/rt_hip.h): the widths of the guided upsampler's edge-stopping terms and its orphan threshold."""
+
+    _fields_ = [("normal_squarings", C.c_uint32), ("sigma_albedo", C.c_float), ("sigma_depth", C.c_float), ("min_weight", C.c_float)]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class RtHipUpscaleInfo(C.Structure):
+    """``rt_hip_upscale_info`` (include/rt_hip.h): the traced low frame and the orphans of a call of rt_hip_render_upscaled."""
+
+    _fields_ = [("low_width", C.c_uint32), ("low_height", C.c_uint32), ("orphans", C.c_uint32), ("pixels", C.c_uint32)]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class RtHipAdaptiveParams(C.Structure):
     """``rt_hip_adaptive_params`` (include/rt_hip.h): when a pixel of an adaptive accumulation has converged."""
 
@@ -253,6 +271,18 @@ RT_HIP_SYMBOLS = [
         "rt_hip_render_temporal",
         C.c_int,
         [C.c_void_p, C.POINTER(RtHipScene), C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(RtHipTemporalParams), C.POINTER(RtHipDenoiseParams), C.c_void_p, C.POINTER(RtHipStats), C.POINTER(RtHipTemporalInfo)],
+    ),
+    ("rt_hip_upsample_default_params", C.c_int, [C.POINTER(RtHipUpsampleParams)]),
+    ("rt_hip_upsample_low_size", C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, c_u32_p, c_u32_p]),
+    (
+        "rt_hip_upsample_device",
+        C.c_int,
+        [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RtHipUpsampleParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    ),
+    (
+        "rt_hip_render_upscaled",
+        C.c_int,
+        [C.c_void_p, C.POINTER(RtHipScene), C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(RtHipUpsampleParams), C.POINTER(RtHipDenoiseParams), C.c_void_p, C.POINTER(RtHipStats), C.POINTER(RtHipUpscaleInfo)],
     ),
     ("rt_hip_adaptive_default_params", C.c_int, [C.POINTER(RtHipAdaptiveParams)]),
     (

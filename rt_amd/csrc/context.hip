@@ -488,6 +488,7 @@ extern "C" void rt_hip_destroy(rt_hip_ctx* ctx)
 	ctx->denoise.release();
 	ctx->temporal.release();
 	ctx->adaptive.release();
+	ctx->upscale.release();
 	ctx->counters.release();
 	ctx->frame_rgb.release();
 	ctx->staging_rgb.release();

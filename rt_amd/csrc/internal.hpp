@@ -15,6 +15,8 @@
 //                 rt_hip_render_adaptive (parameters, sequencing: adaptive.cpp, host compiler; per-pixel rules: adaptive_rules.hpp)
 //   temporal.hip  temporal accumulation: reproject_frame, rt_hip_reproject_device and the drop-in rt_hip_render_temporal
 //                 (parameters, the forward matrix, same_history: temporal.cpp, host compiler; per-pixel rule: reproject_rules.hpp)
+//   upsample.hip  guided upsampling: upsample_frame, rt_hip_upsample_device and the drop-in rt_hip_render_upscaled
+//                 (parameters, sizes: upsample.cpp, host compiler; per-pixel rules: upsample_rules.hpp)
 //   multi.hip     rt_hip_render on several GPUs: stripes, one gather, assemble
 //   group.hip     rt_hip_render as one rank of a frame group (rank processes storing into one shared back buffer)
 //   kernels.hip   the gfx950 kernels (compiled twice: parity contract and RT_HIP_FLAG_FAST arithmetic)
@@ -213,6 +215,26 @@ namespace rt_hip
 		}
 	};
 
+	// what rt_hip_render_upscaled keeps on a context (upsample.hip): everything is grown on demand and freed with the context
+	struct upscale_state
+	{
+		device_buffer low_mean, low_packed, low_filtered; // the traced low frame: float mean, the packed pixels its launch writes, the filter's result
+		device_buffer guide_low, guide_full;			  // the guide at the two sizes
+		device_buffer rgb, packed;						  // the rebuilt frame: float mean (when asked for) and packed pixels
+		device_buffer orphans;							  // one word
+		pinned_buffer staging;							  // the results' landing place on the host
+		hipEvent_t end = nullptr;						  // behind guides + filter + upsampling (frames that keep stats)
+		void release()
+		{
+			for (device_buffer* b : { &low_mean, &low_packed, &low_filtered, &guide_low, &guide_full, &rgb, &packed, &orphans })
+				b->release();
+			staging.release();
+			if (end)
+				(void)hipEventDestroy(end);
+			end = nullptr;
+		}
+	};
+
 	// what adaptive sampling keeps on a context (adaptive.hip): everything is grown on demand and freed with the context
 	struct adaptive_accumulation
 	{
@@ -363,6 +385,7 @@ struct rt_hip_ctx
 	rt_hip::denoise_state denoise;			  // the denoiser's scratch images and the kept guide (denoise.hip)
 	rt_hip::temporal_state temporal;		  // the history of rt_hip_render_temporal (temporal.hip)
 	rt_hip::adaptive_accumulation adaptive;	  // the accumulation of rt_hip_render_adaptive (adaptive.hip)
+	rt_hip::upscale_state upscale;			  // the scratch of rt_hip_render_upscaled (upsample.hip)
 
 	// ---- the sky band (sky_band.hpp, render.hip) ----
 	bool sky_band_enabled = true;		 // RT_HIP_SKY_BAND=0 in the environment at creation: no frame of this context takes a band

@@ -12,7 +12,7 @@
 //   --progressive SAMPLES   the frame in passes of SAMPLES samples per pixel (exported to the renderer as RT_HIP_PROGRESSIVE):
 //                render() is called ceil(spp / SAMPLES) times — every call shows the frame as it stands — and the last frame,
 //                the same as without the option, is the one reported and written (hip renderers only; not together with --frames)
-//   --denoise               with --progressive (or --temporal, see there): every pass's frame goes through the guide-buffer denoiser (exported to the renderer as
+//   --denoise               with --progressive (or --temporal or --upscale, see there): every pass's frame goes through the guide-buffer denoiser (exported to the renderer as
 //                           RT_HIP_DENOISE=always: rt_hip_denoise_progressive after every pass, the last one included), so the frame
 //                           written is the denoised frame of the last pass
 //   --boxes                 the traced frame hits the scene's boxes too (exported to the renderer as RT_HIP_TRACE_BOXES=1: RT_HIP_FLAG_TRACE_BOXES);
@@ -28,6 +28,10 @@
 //                           16 samples — or of --progressive SAMPLES — over the pixels that have not converged yet; render() is called
 //                           until the accumulation is complete, the last frame is written, and the samples traced are printed against
 //                           pixels x spp.  Hip renderers only; not with --frames, --temporal, --boxes or --denoise
+//   --upscale FACTOR        2, 3 or 4: every frame is traced at ceil(size / FACTOR) and rebuilt at full size by the guided upsampler (exported
+//                           to the renderer as RT_HIP_UPSCALE=FACTOR: rt_hip_render_upscaled); with --denoise the traced low
+//                           frame goes through the a-trous filter first.  Hip renderers only; not with --progressive, --temporal,
+//                           --adaptive, --light or --box-bvh
 //   --light KEY=R,G,B       repeatable: the materials named KEY (or the material of that index) are LIGHTS of that emission; KEY=V is a grey
 //                           light (exported to the renderer as RT_HIP_LIGHTS, the items joined with ';': rt_hip_lights_from_spec,
 //                           rt_hip_set_emission, RT_HIP_FLAG_EMISSION).  Hip renderers only; not with --progressive, --adaptive,
@@ -153,6 +157,7 @@ int main(int argc, char** argv)
 	bool frames_given = false;
 	bool list = false;
 	bool boxes = false, box_bvh = false, denoise = false, temporal = false, dolly = false, adaptive = false;
+	unsigned upscale = 0;
 	float dolly_by[3] = { 0.0f, 0.0f, 0.0f };
 	// default renderer: the first whose name starts with "hip", else the first registered (reference: first "mg", :350)
 	for (auto& r : renderers::all())
@@ -228,6 +233,19 @@ int main(int argc, char** argv)
 			temporal = true;
 			::setenv("RT_HIP_TEMPORAL", "1", 1); // (read by the plug-in: every render() is one rt_hip_render_temporal frame)
 		}
+		else if (arg == "--upscale"sv)
+		{
+			const char* const factor = value();
+			char* end = nullptr;
+			const unsigned long parsed = std::strtoul(factor, &end, 10);
+			if (end == factor || *end || parsed < 2ul || parsed > 4ul)
+			{
+				error("--upscale expects the factor (2, 3 or 4)");
+				return 2;
+			}
+			upscale = static_cast<unsigned>(parsed);
+			::setenv("RT_HIP_UPSCALE", std::to_string(upscale).c_str(), 1); // (read by the plug-in: every render() is one rt_hip_render_upscaled frame)
+		}
 		else if (arg == "--adaptive"sv)
 		{
 			const char* const threshold = value();
@@ -269,7 +287,7 @@ int main(int argc, char** argv)
 			world = static_cast<unsigned>(std::strtoul(value(), nullptr, 10));
 		else if (arg == "--help"sv || arg == "-h"sv)
 		{
-			log("usage: rt_headless [--list] [--scene file.toml] [--renderer name] [--size WxH] [--spp N] [--bounces N] [--seed N] [--frames N] [--out file.ppm] [--progressive SAMPLES] [--denoise] [--boxes [--box-bvh]] [--temporal] [--adaptive THRESHOLD] [--light KEY=R,G,B]... [--direct-light] [--dolly DX,DY,DZ] [--shared-frame NAME --rank R --world N]");
+			log("usage: rt_headless [--list] [--scene file.toml] [--renderer name] [--size WxH] [--spp N] [--bounces N] [--seed N] [--frames N] [--out file.ppm] [--progressive SAMPLES] [--denoise] [--boxes [--box-bvh]] [--temporal] [--adaptive THRESHOLD] [--upscale FACTOR] [--light KEY=R,G,B]... [--direct-light] [--dolly DX,DY,DZ] [--shared-frame NAME --rank R --world N]");
 			return 0;
 		}
 		else
@@ -291,6 +309,15 @@ int main(int argc, char** argv)
 	{
 		error("no known renderer with name '", renderer_name, "'");
 		return 1;
+	}
+	if (upscale)
+	{
+		const char* const with = progressive ? "--progressive" : (temporal ? "--temporal" : (adaptive ? "--adaptive" : (!lights.empty() ? "--light" : (box_bvh ? "--box-bvh" : nullptr))));
+		if (with || std::string_view{ desc->name }.substr(0, 3) != "hip"sv)
+		{
+			error("--upscale traces one-shot frames of a hip renderer at 1 / FACTOR of the size and rebuilds them (not with --progressive, --temporal, --adaptive, --light or --box-bvh, not '", desc->name, "'): refused with ", with ? with : "this renderer");
+			return 2;
+		}
 	}
 	if (progressive && (frames_given || std::string_view{ desc->name }.substr(0, 3) != "hip"sv))
 	{
@@ -327,7 +354,7 @@ int main(int argc, char** argv)
 		error("--temporal blends whole frames of a hip renderer (not with --progressive, not '", desc->name, "')");
 		return 2;
 	}
-	if (denoise && !progressive && !temporal)
+	if (denoise && !progressive && !temporal && !upscale)
 	{
 		error("--denoise filters the passes of a progressive frame: it needs --progressive SAMPLES (or --temporal)");
 		return 2;

@@ -19,7 +19,7 @@ import ctypes as C
 import numpy as np
 
 from . import capi
-from .capi import RtHipAdaptiveInfo, RtHipAdaptiveParams, RtHipDenoiseParams, RtHipPartition, RtHipPhases, RtHipProgress, RtHipScene, RtHipStats, RtHipTemporalInfo, RtHipTemporalParams, check
+from .capi import RtHipAdaptiveInfo, RtHipAdaptiveParams, RtHipDenoiseParams, RtHipPartition, RtHipPhases, RtHipProgress, RtHipScene, RtHipStats, RtHipTemporalInfo, RtHipTemporalParams, RtHipUpsampleParams, RtHipUpscaleInfo, check
 
 
 def local_rows(height: int, rank: int, world: int, stripe_rows: int = capi.RT_HIP_DEFAULT_STRIPE_ROWS) -> int:
@@ -81,6 +81,20 @@ def box_bvh_build(scene: RtHipScene) -> dict:
     capi.check_kat(capi.kat_lib().rt_hip_kat_box_bvh_build(C.byref(scene), counts.ctypes.data, nodes.ctypes.data, order.ctypes.data, corners.ctypes.data, always.ctypes.data))
     n_nodes, n_tree, n_always, depth, root = (int(c) for c in counts)
     return {"nodes": nodes[:n_nodes], "order": order[:n_tree], "corners": corners[:n_tree], "always": always[:n_always], "depth": depth, "root": root}
+
+
+def upsample_default_params() -> RtHipUpsampleParams:
+    """rt_hip_upsample_default_params: what a NULL `params` stands for (pure host code)."""
+    params = RtHipUpsampleParams()
+    check(capi.hip_lib().rt_hip_upsample_default_params(C.byref(params)))
+    return params
+
+
+def upsample_low_size(width: int, height: int, factor: int) -> tuple:
+    """rt_hip_upsample_low_size: the (width, height) of the frame render_upscaled traces for `factor` (pure host code)."""
+    w, h = C.c_uint32(0), C.c_uint32(0)
+    check(capi.hip_lib().rt_hip_upsample_low_size(width, height, factor, C.byref(w), C.byref(h)))
+    return w.value, h.value
 
 
 def denoise_default_params() -> RtHipDenoiseParams:
@@ -300,6 +314,25 @@ class HipRayTracer:
         rgba = np.empty((height, width), dtype=np.uint32)
         rgb = np.empty((height, width, 3), dtype=np.float32) if want_rgb else None
         check(self._lib.rt_hip_render_temporal(self._ctx, C.byref(scene), rgba.ctypes.data, width, height, seed, flags, C.byref(temporal) if temporal is not None else None, C.byref(filter) if filter is not None else None,
+                                               rgb.ctypes.data if rgb is not None else None, C.byref(stats_pod) if stats else None, C.byref(info)))
+        return rgba, rgb, stats_pod.as_dict() if stats else {}, info.as_dict()
+
+    # ---- guided upsampling ------------------------------------------------------------------
+    def upsample_device(self, width: int, height: int, low_width: int, low_height: int, d_rgb_low: int, d_guide_low: int, d_guide_full: int, params: RtHipUpsampleParams | None = None, d_rgb_out: int | None = None,
+                        d_rgba8_out: int | None = None, d_orphans: int | None = None, stream: int | None = None) -> None:
+        """rt_hip_upsample_device: the full frame rebuilt from a low frame's mean and the guides of both sizes, on DEVICE buffers
+        (`params` None: the defaults).  Asynchronous on `stream`."""
+        check(self._lib.rt_hip_upsample_device(self._ctx, width, height, low_width, low_height, d_rgb_low, d_guide_low, d_guide_full, C.byref(params) if params is not None else None, d_rgb_out, d_rgba8_out, d_orphans, stream))
+
+    def render_upscaled(self, scene: RtHipScene, width: int, height: int, seed: int = 1, flags: int = 0, factor: int = 2, upsample: RtHipUpsampleParams | None = None, filter: RtHipDenoiseParams | None = None, want_rgb: bool = False,
+                        stats: bool = True):
+        """rt_hip_render_upscaled: one frame traced at ceil(size / factor) and rebuilt at full size — (rgba8 uint32[H, W], rgb
+        float32[H, W, 3] or None, stats dict of the traced low frame, info dict: low_width, low_height, orphans, pixels).  `filter`:
+        the a-trous filter's parameters for the LOW mean (None: no filter)."""
+        stats_pod, info = RtHipStats(), RtHipUpscaleInfo()
+        rgba = np.empty((height, width), dtype=np.uint32)
+        rgb = np.empty((height, width, 3), dtype=np.float32) if want_rgb else None
+        check(self._lib.rt_hip_render_upscaled(self._ctx, C.byref(scene), rgba.ctypes.data, width, height, seed, flags, factor, C.byref(upsample) if upsample is not None else None, C.byref(filter) if filter is not None else None,
                                                rgb.ctypes.data if rgb is not None else None, C.byref(stats_pod) if stats else None, C.byref(info)))
         return rgba, rgb, stats_pod.as_dict() if stats else {}, info.as_dict()
 

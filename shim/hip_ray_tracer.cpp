@@ -210,6 +210,30 @@ namespace
 		return threshold;
 	}
 
+	// RT_HIP_UPSCALE=K (2 .. 4; rt_headless --upscale K) makes render() ONE UPSCALED FRAME (rt_hip_render_upscaled): the frame is traced at
+	// ceil(size / K) and rebuilt at full size by the guided upsampler.  With RT_HIP_DENOISE=1 or always the traced low
+	// frame goes through the a-trous filter at its defaults first.  Where RT_HIP_ADAPTIVE, RT_HIP_TEMPORAL or RT_HIP_PROGRESSIVE is set, that
+	// one wins; with RT_HIP_LIGHTS, or on a renderer of several GPUs, the module refuses, which is said once, and the frames are
+	// rt_hip_render's.  Anything but 2, 3 or 4: off (an unreadable value is said).  (Not for the preview.)
+	uint32_t upscale_factor()
+	{
+		static const uint32_t factor = []() -> uint32_t
+		{
+			const char* upscale = std::getenv("RT_HIP_UPSCALE");
+			if (!upscale || !*upscale || std::strcmp(upscale, "0") == 0 || std::strcmp(upscale, "1") == 0)
+				return 0u;
+			char* end = nullptr;
+			const unsigned long value = std::strtoul(upscale, &end, 10);
+			if (end == upscale || *end || value < 2ul || value > 4ul)
+			{
+				std::cerr << "error: hip_ray_tracer: RT_HIP_UPSCALE='" << upscale << "' is not a factor of 2 .. 4: ignored\n";
+				return 0u;
+			}
+			return static_cast<uint32_t>(value);
+		}();
+		return factor;
+	}
+
 	// RT_HIP_LIGHTS="KEY=R,G,B;KEY=V;..." (rt_headless --light) makes materials LIGHTS (RT_HIP_FLAG_EMISSION): rt::materials has no emission
 	// column, so the table comes from this text and the scene's material names (rt_hip_lights_from_spec: a KEY is a material's name, or its
 	// index) and is handed to the context (rt_hip_set_emission) — again whenever the materials change.  Unset or empty: no lights.  One-shot
@@ -246,6 +270,7 @@ namespace
 		uint64_t frame_number = 0;
 		bool temporal_unsupported = false; // RT_HIP_TEMPORAL on a renderer of several GPUs: refused once, then whole frames as without it
 		bool adaptive_unsupported = false; // RT_HIP_ADAPTIVE on such a renderer: likewise
+		bool upscale_unsupported = false;  // RT_HIP_UPSCALE on such a renderer, or with lights: likewise
 		std::vector<std::string> light_names; // RT_HIP_LIGHTS: the material names the context's emission table was made from
 		bool lights_set = false;
 
@@ -400,6 +425,23 @@ namespace
 						if (rt_hip_denoise_progressive(ctx, nullptr, pixels.data(), nullptr, nullptr) != RT_HIP_OK) // (on failure the pass's own frame stays)
 							std::cerr << "error: hip_ray_tracer: " << rt_hip_last_error() << "\n";
 					return;
+				}
+			if constexpr (ModeFlags != RT_HIP_FLAG_PREVIEW)
+				if (const uint32_t factor = upscale_factor(); factor && !upscale_unsupported)
+				{
+					rt_hip_denoise_params filter{};
+					const bool filtered = denoise_mode() != 0u && rt_hip_denoise_default_params(&filter) == RT_HIP_OK;
+					const rt_hip_status st = rt_hip_render_upscaled(ctx, &s, pixels.data(), pixels.size().x, pixels.size().y, seed, accel_flags() | lights | ModeFlags, factor, nullptr, filtered ? &filter : nullptr, nullptr, nullptr, nullptr);
+					if (st == RT_HIP_OK)
+						return;
+					if (st != RT_HIP_UNSUPPORTED)
+					{
+						std::cerr << "error: hip_ray_tracer: " << rt_hip_last_error() << "\n";
+						return;
+					}
+					// a multi-GPU or frame-group renderer, or a flag upscaled frames do not take: said once, and from here on every frame is rt_hip_render's (below)
+					std::cerr << "error: hip_ray_tracer: " << rt_hip_last_error() << ": RT_HIP_UPSCALE is ignored for this renderer\n";
+					upscale_unsupported = true;
 				}
 			if (rt_hip_render(ctx, &s, pixels.data(), pixels.size().x, pixels.size().y, seed, frame_flags() | accel_flags() | lights | ModeFlags, nullptr, nullptr)
 				!= RT_HIP_OK)
