@@ -16,7 +16,7 @@ HIPFLAGS += -fvisibility=hidden
 # register pairs — moves, and a higher register count.  Measured on the contract-v4 kernels: headline 2.28 -> 2.14 ms,
 # basic + plane 2.74 -> 2.62, tilted camera 2.80 -> 2.62 (profiles/r05/codegen_ab.txt).
 HIPFLAGS += -fno-slp-vectorize
-API_UNITS := context scene frame render passes multi group denoise temporal adaptive upsample
+API_UNITS := context scene frame render frame_call passes multi group denoise temporal adaptive upsample
 HIP_HDR  := rt_amd/csrc/kernels.hpp rt_amd/csrc/launch_plan.hpp rt_amd/csrc/progressive.hpp rt_amd/csrc/denoise.hpp rt_amd/csrc/denoise_rules.hpp rt_amd/csrc/temporal.hpp rt_amd/csrc/reproject_rules.hpp rt_amd/csrc/adaptive.hpp rt_amd/csrc/adaptive_rules.hpp rt_amd/csrc/upsample.hpp rt_amd/csrc/upsample_rules.hpp rt_amd/csrc/lights.hpp rt_amd/csrc/sky_band.hpp rt_amd/csrc/centre_ray.hpp rt_amd/csrc/frame_setup.hpp rt_amd/csrc/contract.hpp rt_amd/csrc/scan.hpp rt_amd/csrc/bvh_scan.hpp rt_amd/csrc/bvh.hpp rt_amd/csrc/box_bvh.hpp rt_amd/csrc/box_bvh_scan.hpp rt_amd/csrc/scan_streamed.hpp rt_amd/csrc/handover.hpp rt_amd/csrc/pixel_output.hpp rt_amd/csrc/lane_state.hpp rt_amd/csrc/queue_build.hpp rt_amd/csrc/camera_forms.hpp rt_amd/csrc/bvh_build.hpp rt_amd/csrc/bvh_build_device.hpp rt_amd/csrc/frame_group.hpp rt_amd/csrc/delivery.hpp rt_amd/csrc/internal.hpp include/rt_hip.h
 HOST_SRC := rt_amd/host/host_capi.cpp rt_amd/host/scene.cpp rt_amd/host/toml_subset.cpp
 HOST_HDR := $(wildcard rt_amd/host/*.hpp) rt_amd/host/host_capi.h rt_amd/host/named_colours.inc include/rt_hip.h

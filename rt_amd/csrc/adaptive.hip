@@ -356,8 +356,8 @@ extern "C" rt_hip_status rt_hip_render_adaptive(rt_hip_ctx* ctx,
 		return fail(RT_HIP_INVALID_ARGUMENT, "rt_hip_render_adaptive: NULL argument");
 	if (!width || !height || width > max_frame_side || height > max_frame_side)
 		return fail(RT_HIP_INVALID_ARGUMENT, "rt_hip_render_adaptive: frame %ux%u (1 .. %u a side)", width, height, max_frame_side);
-	if (ctx->multi || ctx->group || ctx->world != 1u)
-		return fail(RT_HIP_UNSUPPORTED, "rt_hip_render_adaptive: contexts from rt_hip_create only (not a multi-GPU, rank or frame-group context)");
+	if (const rt_hip_status st = single_context_only("rt_hip_render_adaptive", ctx))
+		return st;
 	if (const char* const refused = refused_adaptive_flag(flags))
 		return fail(RT_HIP_UNSUPPORTED, "rt_hip_render_adaptive: %s is not available for adaptive passes (0x%x): they take RT_HIP_FLAG_SM_MATERIALS, RT_HIP_FLAG_BVH, RT_HIP_FLAG_BVH_DEVICE_BUILD and RT_HIP_FLAG_STATS", refused, flags);
 	if (!scene->samples_per_pixel || scene->samples_per_pixel > pass_max_samples_per_pixel)
@@ -365,29 +365,19 @@ extern "C" rt_hip_status rt_hip_render_adaptive(rt_hip_ctx* ctx,
 	if (pass_size > pass_max_samples_per_pixel)
 		return fail(RT_HIP_UNSUPPORTED, "rt_hip_render_adaptive: a pass of %u samples", pass_samples);
 	const size_t pixels = static_cast<size_t>(width) * height;
-	const size_t frame_bytes = pixels * sizeof(uint32_t), rgb_bytes = pixels * 3 * sizeof(float), block_bytes = pixels * block_words * sizeof(uint32_t);
+	const size_t frame_bytes = pixels * sizeof(uint32_t), block_bytes = pixels * block_words * sizeof(uint32_t);
 	const bool keep_stats = stats || (flags & RT_HIP_FLAG_STATS);
 	try
 	{
 		RT_HIP_TRY(hipSetDevice(ctx->device));
 		track_frame_buffer(ctx, pixels_rgba8888, frame_bytes, false); // (a page-lock an earlier rt_hip_render took on the caller's buffer is dropped)
 
-		const auto scene_t0 = std::chrono::steady_clock::now();
 		scene_request request;
-		if (const rt_hip_status st = open_request(request, scene))
+		if (const rt_hip_status st = resident_scene(ctx, scene, request))
 			return st;
-		ctx->phases = rt_hip_phases{};
-		if (const rt_hip_status st = make_resident(ctx, request))
-			return st;
-		ctx->stats.upload_ms = static_cast<float>(seconds_since(scene_t0) * 1e3);
 
 		adaptive_accumulation& a = ctx->adaptive;
-		frame_key frame{};
-		frame.scene_fingerprint = request.print;
-		frame.samples_per_pixel = scene->samples_per_pixel, frame.max_bounces = scene->max_bounces;
-		std::copy(scene->inverse_view_projection, scene->inverse_view_projection + 16, frame.inverse_view_projection);
-		frame.width = width, frame.height = height, frame.seed = seed, frame.flags = flags & pass_frame_flags;
-		const adaptive_key wanted = make_adaptive_key(frame, p, static_cast<uint32_t>(pass_size));
+		const adaptive_key wanted = make_adaptive_key(frame_key_of(request, scene, width, height, seed, flags & pass_frame_flags), p, static_cast<uint32_t>(pass_size));
 		const adaptive_step step = next_adaptive_pass(a.state, wanted);
 		if (step.restart)
 			a.state = adaptive_state{};
@@ -396,9 +386,9 @@ extern "C" rt_hip_status rt_hip_render_adaptive(rt_hip_ctx* ctx,
 		info.restarted = step.restart ? 1u : 0u;
 		info.pixels = static_cast<uint32_t>(pixels);
 
-		frame_delivery* const delivery = delivery_of(ctx);
-		if (!delivery)
-			return fail(RT_HIP_RUNTIME_ERROR, "rt_hip_render_adaptive: out of host memory");
+		carried_frame frame(ctx, pixels_rgba8888, rgb_f32, pixels);
+		if (const rt_hip_status st = frame.open("rt_hip_render_adaptive"))
+			return st;
 		const hipStream_t s = ctx->stream;
 		// what lands on the host: the active word and the state words behind a pass; accum and state for a call on a complete accumulation
 		const size_t landing_bytes = std::max(4u * pixels * sizeof(uint32_t), frame_bytes + sizeof(uint32_t));
@@ -410,7 +400,7 @@ extern "C" rt_hip_status rt_hip_render_adaptive(rt_hip_ctx* ctx,
 			// over its own sample count — pixel_mean's division, correctly rounded on either side of the bus.
 			if (a.frame.size() != pixels || a.block.bytes < block_bytes)
 				return fail(RT_HIP_RUNTIME_ERROR, "rt_hip_render_adaptive: the finished frame was not kept");
-			delivery->carrier.copy(pixels_rgba8888, a.frame.data(), frame_bytes);
+			frame.delivery->carrier.copy(pixels_rgba8888, a.frame.data(), frame_bytes);
 			if (rgb_f32 || sample_counts)
 			{
 				RT_HIP_TRY(hipMemcpyAsync(a.staging.ptr, a.block.ptr, 4u * pixels * sizeof(uint32_t), hipMemcpyDeviceToHost, s)); // accum, state
@@ -427,10 +417,7 @@ extern "C" rt_hip_status rt_hip_render_adaptive(rt_hip_ctx* ctx,
 							rgb_f32[i * 3 + c] = sums[i * 3 + c] / static_cast<float>(n);
 				}
 			}
-			ctx->render_recorded = false;
-			ctx->stats.kernel_variant = RT_HIP_KERNEL_NONE;
-			ctx->stats.primary_samples = ctx->stats.segments = ctx->stats.sphere_tests = ctx->stats.plane_tests = 0;
-			ctx->stats.render_ms = ctx->stats.readback_ms = 0.0f;
+			nothing_launched(ctx);
 			info.samples_done = a.state.samples_done, info.passes = a.state.passes, info.active_pixels = a.state.active_pixels;
 			info.samples_traced = a.state.samples_traced, info.complete = 1u;
 			remember(info);
@@ -446,66 +433,22 @@ extern "C" rt_hip_status rt_hip_render_adaptive(rt_hip_ctx* ctx,
 		if (!a.end)
 			RT_HIP_TRY(hipEventCreate(&a.end));
 
-		// the frame's way to the caller, as in rt_hip_render_progressive (render.hip has the why of each step)
-		struct abandon_unless_finished
-		{
-			frame_delivery* delivery;
-			~abandon_unless_finished()
-			{
-				if (delivery)
-					delivery->abandon();
-			}
-		} staged{ nullptr };
-		struct drain_before_abandoning // (declared after `staged`: runs first on every early exit)
-		{
-			hipStream_t stream;
-			bool armed;
-			~drain_before_abandoning()
-			{
-				if (armed && hipStreamSynchronize(stream) != hipSuccess)
-					(void)hipGetLastError();
-			}
-		} drain{ s, false };
-		uint32_t* d_frame = nullptr;
-		if (const rt_hip_status st = delivery->begin(pixels_rgba8888, pixels, &d_frame))
+		if (const rt_hip_status st = frame.begin())
 			return st;
-		staged.delivery = delivery;
-		if (rgb_f32)
-		{
-			RT_HIP_TRY(ctx->frame_rgb.reserve(rgb_bytes));
-			RT_HIP_TRY(ctx->staging_rgb.reserve(rgb_bytes));
-		}
 		// a pass that fails leaves the block in an unknown state: nothing is in flight from here until it has succeeded
 		const adaptive_state before = a.state;
 		a.state = adaptive_state{};
-		drain.armed = true;
-		if (const rt_hip_status st = adaptive_pass(ctx, width, height, seed, flags, step.first_sample, step.n_samples, step.whole_pass, p, a.block.as<float>(), d_frame, rgb_f32 ? ctx->frame_rgb.as<float>() : nullptr, a.active.as<uint32_t>(), s,
-												   keep_stats))
+		if (const rt_hip_status st = adaptive_pass(ctx, width, height, seed, flags, step.first_sample, step.n_samples, step.whole_pass, p, a.block.as<float>(), frame.d_frame, frame.d_rgb, a.active.as<uint32_t>(), s, keep_stats))
 			return st;
-		staged.delivery->launched();
+		frame.launched();
 		if (keep_stats)
 			RT_HIP_TRY(hipEventRecord(a.end, s));
 		unsigned char* const landing = a.staging.as<unsigned char>();
 		hipError_t e = hipMemcpyAsync(landing, a.active.ptr, sizeof(uint32_t), hipMemcpyDeviceToHost, s);
 		if (e == hipSuccess && sample_counts)
 			e = hipMemcpyAsync(landing + sizeof(uint32_t), view_of(a.block.as<float>(), pixels).state, frame_bytes, hipMemcpyDeviceToHost, s);
-		if (e == hipSuccess && rgb_f32)
-			e = hipMemcpyAsync(ctx->staging_rgb.ptr, ctx->frame_rgb.ptr, rgb_bytes, hipMemcpyDeviceToHost, s);
-		const auto issued = std::chrono::steady_clock::now();
-		if (e == hipSuccess && keep_stats)
-			e = hipEventSynchronize(a.end);
-		const auto t0 = std::chrono::steady_clock::now();
-		const hipError_t drained = hipStreamSynchronize(s);
-		drain.armed = drained != hipSuccess;
-		RT_HIP_TRY(e);
-		RT_HIP_TRY(drained);
-		staged.delivery->finish();
-		ctx->phases.carrier_bands = static_cast<uint32_t>(staged.delivery->carrier.bands());
-		ctx->phases.carrier_bands_early = static_cast<uint32_t>(staged.delivery->carrier.early_bands());
-		ctx->phases.carrier_helpers = staged.delivery->carrier.helpers();
-		staged.delivery = nullptr;
-		if (rgb_f32)
-			delivery->carrier.copy(rgb_f32, ctx->staging_rgb.ptr, rgb_bytes);
+		if (const rt_hip_status st = frame.deliver(keep_stats ? a.end : nullptr, e))
+			return st;
 		uint32_t active_after = 0;
 		std::memcpy(&active_after, landing, sizeof active_after);
 		if (sample_counts)
@@ -533,17 +476,10 @@ extern "C" rt_hip_status rt_hip_render_adaptive(rt_hip_ctx* ctx,
 			*out_info = info;
 
 		ctx->stats.primary_samples = traced_pixels * step.n_samples;
-		ctx->stats.readback_ms = keep_stats ? static_cast<float>(seconds_since(t0) * 1e3) : 0.0f;
-		ctx->phases.host_issue_ms = static_cast<float>(std::chrono::duration<double>(issued - entered).count() * 1e3);
-		ctx->phases.host_wait_ms = static_cast<float>(seconds_since(issued) * 1e3);
-		if (keep_stats)
-			ctx->phases.render_ms = elapsed_or_zero(ctx->render_begin, a.end);
+		if (const rt_hip_status st = frame.account(entered, stats))
+			return st;
 		if (stats)
-		{
-			if (const rt_hip_status st = rt_hip_stats_fetch(ctx, stats))
-				return st;
 			stats->render_ms = elapsed_or_zero(ctx->render_begin, a.end); // the traced pass and the update behind it
-		}
 		return ok();
 	}
 	catch (const std::exception& e) // nothing may propagate through the C boundary

@@ -296,9 +296,9 @@ extern "C" rt_hip_status rt_hip_guide_device(rt_hip_ctx* ctx, uint32_t width, ui
 		return fail(RT_HIP_UNSUPPORTED, "rt_hip_guide_device: %s is not available for the guide (0x%x): it takes RT_HIP_FLAG_TRACE_BOXES, and RT_HIP_FLAG_SM_MATERIALS, RT_HIP_FLAG_BVH, RT_HIP_FLAG_BVH_DEVICE_BUILD and RT_HIP_FLAG_STATS without effect", refused, flags);
 	if (!ctx->have_scene)
 		return fail(RT_HIP_NO_SCENE, "rt_hip_guide_device: no scene uploaded");
-	const bool trace_boxes = (flags & RT_HIP_FLAG_TRACE_BOXES) && ctx->scene.n_boxes;
-	if (trace_boxes && ctx->scene.n_boxes > box_max_count)
-		return fail(RT_HIP_UNSUPPORTED, "rt_hip_guide_device: RT_HIP_FLAG_TRACE_BOXES traces at most %u boxes, the scene has %u", box_max_count, ctx->scene.n_boxes);
+	bool trace_boxes = false;
+	if (const rt_hip_status st = guide_boxes("rt_hip_guide_device", ctx, flags, &trace_boxes))
+		return st;
 	try
 	{
 		RT_HIP_TRY(hipSetDevice(ctx->device)); // (a multi-GPU, rank or frame-group context: the root member, like the other device-level calls)
@@ -330,8 +330,8 @@ extern "C" rt_hip_status rt_hip_denoise_device(rt_hip_ctx* ctx,
 	if (reinterpret_cast<uintptr_t>(d_guide) % 16u)
 		return fail(RT_HIP_INVALID_ARGUMENT, "rt_hip_denoise_device: d_guide is not 16-byte aligned (two float4s per pixel)");
 	const size_t rgb_bytes = static_cast<size_t>(width) * height * 3u * sizeof(float);
-	if (d_rgb_out && buffers_overlap(d_rgb_in, rgb_bytes, d_rgb_out, rgb_bytes))
-		return fail(RT_HIP_INVALID_ARGUMENT, "rt_hip_denoise_device: d_rgb_out overlaps d_rgb_in (every pixel reads its neighbours' input)");
+	if (const rt_hip_status st = refuse_overlaps("rt_hip_denoise_device", { { d_rgb_out, rgb_bytes, "d_rgb_out" } }, { { d_rgb_in, rgb_bytes, "d_rgb_in" } }, "every pixel reads its neighbours' input"))
+		return st;
 	try
 	{
 		RT_HIP_TRY(hipSetDevice(ctx->device));
@@ -350,8 +350,8 @@ extern "C" rt_hip_status rt_hip_denoise_progressive(rt_hip_ctx* ctx, const rt_hi
 		return st;
 	if (!ctx || !pixels_rgba8888)
 		return fail(RT_HIP_INVALID_ARGUMENT, "rt_hip_denoise_progressive: NULL argument");
-	if (ctx->multi || ctx->group || ctx->world != 1u)
-		return fail(RT_HIP_UNSUPPORTED, "rt_hip_denoise_progressive: contexts from rt_hip_create only (not a multi-GPU, rank or frame-group context)");
+	if (const rt_hip_status st = single_context_only("rt_hip_denoise_progressive", ctx))
+		return st;
 	const pass_state& in_flight = ctx->progressive; // (a read-only look: the accumulation is not touched)
 	if (!in_flight.started || !in_flight.samples_done || !ctx->have_scene)
 		return fail(RT_HIP_INVALID_ARGUMENT, "rt_hip_denoise_progressive: no accumulation in flight (rt_hip_render_progressive has not delivered a pass on this context, or its last pass failed)");
@@ -375,7 +375,8 @@ extern "C" rt_hip_status rt_hip_denoise_progressive(rt_hip_ctx* ctx, const rt_hi
 		RT_HIP_TRY(d.packed.reserve(rgba_bytes));
 		if (rgb_f32)
 			RT_HIP_TRY(d.filtered.reserve(rgb_bytes));
-		RT_HIP_TRY(d.staging.reserve(rgba_bytes + (rgb_f32 ? rgb_bytes : 0u)));
+		staged_results results{ d.staging, rgba_bytes, rgb_f32 ? rgb_bytes : 0u, false };
+		RT_HIP_TRY(results.reserve());
 		// the guide belongs to the accumulation: built when the kept one is another frame's (its key differs), kept otherwise
 		const bool fresh_guide = !d.have_guide || !same_frame(d.guide_key, in_flight.key) || d.guide.bytes < pixels * denoise::guide_words * sizeof(float);
 		if (fresh_guide)
@@ -385,6 +386,7 @@ extern "C" rt_hip_status rt_hip_denoise_progressive(rt_hip_ctx* ctx, const rt_hi
 			d.have_guide = false;
 			RT_HIP_TRY(d.guide.reserve(pixels * denoise::guide_words * sizeof(float)));
 		}
+		frame_scope scope(s, true); // whatever was enqueued has finished before anything returns
 		RT_HIP_TRY(hipEventRecord(d.begin, s));
 		if (fresh_guide) // (the frame's flags: passes take no RT_HIP_FLAG_TRACE_BOXES, and the others do not change a first hit)
 			if (const rt_hip_status st = launch_guide(ctx, width, height, in_flight.key.inverse_view_projection, false, d.guide.as<float>(), s))
@@ -394,22 +396,13 @@ extern "C" rt_hip_status rt_hip_denoise_progressive(rt_hip_ctx* ctx, const rt_hi
 		if (const rt_hip_status st = launch_filter(ctx, width, height, d.mean.as<float>(), d.guide.as<float>(), p, rgb_f32 ? d.filtered.as<float>() : nullptr, d.packed.as<uint32_t>(), s))
 			return st;
 		RT_HIP_TRY(hipEventRecord(d.end, s));
-		// results to the module's page-locked staging, then into the caller's plain memory (the runtime never touches the caller's pages)
-		unsigned char* const landing = d.staging.as<unsigned char>();
-		hipError_t e = hipMemcpyAsync(landing, d.packed.ptr, rgba_bytes, hipMemcpyDeviceToHost, s);
-		if (e == hipSuccess && rgb_f32)
-			e = hipMemcpyAsync(landing + rgba_bytes, d.filtered.ptr, rgb_bytes, hipMemcpyDeviceToHost, s);
-		const hipError_t drained = hipStreamSynchronize(s); // (whatever was enqueued has finished before anything returns)
-		RT_HIP_TRY(e);
-		RT_HIP_TRY(drained);
+		if (const rt_hip_status st = results.deliver(scope, d.packed.ptr, d.filtered.ptr, nullptr, pixels_rgba8888, rgb_f32, nullptr))
+			return st;
 		if (fresh_guide)
 		{
 			d.guide_key = in_flight.key;
 			d.have_guide = true;
 		}
-		std::memcpy(pixels_rgba8888, landing, rgba_bytes);
-		if (rgb_f32)
-			std::memcpy(rgb_f32, landing + rgba_bytes, rgb_bytes);
 		if (render_ms)
 			*render_ms = elapsed_or_zero(d.begin, d.end);
 		return ok();

@@ -6,6 +6,8 @@
 //   frame.hip     the caller's frame buffer: the module-owned page-locked frame and its delivery threads (the default),
 //                 the opt-in page-lock of the caller's own buffer, NUMA placement
 //   render.hip    one launch (rt_hip_render_device), the work counters, the single-GPU drop-in rt_hip_render
+//   frame_call.hip   the steps the single-context drop-in calls share: the scene prologue, the frame key, the drain-then-abandon
+//                 scope, and the two ways a finished frame reaches the caller's plain memory, carried and staged
 //   frame_setup.cpp, launch_plan.cpp   (host compiler, no HIP) what a launch is refused for, its per-frame constants, its plan
 //   passes.hip    a frame in resumable passes: rt_hip_render_progressive (sequencing: progressive.cpp, host compiler; one pass at the
 //                 device level, rt_hip_render_pass_device, is render.hip's)
@@ -45,6 +47,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -557,6 +560,109 @@ namespace rt_hip
 	};
 	// the context's delivery, made on first use (NULL: out of memory)
 	frame_delivery* delivery_of(rt_hip_ctx* ctx);
+
+	// ---- frame_call.hip: the steps the single-context drop-in calls share ----
+	// `who` is the entry point's name, the prefix of every message.
+	// "contexts from rt_hip_create only": the refusal of a multi-GPU, rank or frame-group context
+	rt_hip_status single_context_only(const char* who, const rt_hip_ctx* ctx);
+	// the caller's scene checked, fingerprinted and resident on `ctx`; starts the call's phases and sets its upload_ms (the whole scene
+	// check, fingerprint pass included)
+	rt_hip_status resident_scene(rt_hip_ctx* ctx, const rt_hip_scene* scene, scene_request& request);
+	// everything the frame's pixels depend on; `flags` masked by the caller (pass_frame_flags, history_frame_flags)
+	frame_key frame_key_of(const scene_request& request, const rt_hip_scene* scene, uint32_t width, uint32_t height, uint64_t seed, uint32_t flags);
+	// RT_HIP_FLAG_TRACE_BOXES for the guide kernel: does it trace the resident scene's boxes?  Refused beyond box_max_count
+	rt_hip_status guide_boxes(const char* who, const rt_hip_ctx* ctx, uint32_t flags, bool* trace_boxes);
+	// a call on a finished accumulation has launched nothing: its stats say so
+	void nothing_launched(rt_hip_ctx* ctx);
+	// Device buffers by the names the caller knows them under (NULL: not given).  An output that overlaps an input is refused as
+	// "<out> overlaps <in> (<why>)"; two outputs that overlap as `among_outputs`, or by their names where that is NULL.
+	struct named_buffer
+	{
+		const void* ptr;
+		size_t bytes;
+		const char* name;
+	};
+	rt_hip_status refuse_overlaps(const char* who, std::initializer_list<named_buffer> outputs, std::initializer_list<named_buffer> inputs, const char* why, const char* among_outputs = nullptr);
+
+	// What one drop-in call has put on its stream, and the module-owned frame it has begun.  On EVERY exit that has not drained
+	// and finished, the destructor first waits for the stream and only then abandons the frame — in that order by construction:
+	// whatever the call enqueued has drained before the staging frame is abandoned (wiped, or on growth unmapped, by the next
+	// begin()).  A launch can fail AFTER its kernel is enqueued (hipGetLastError, the timing events, the counters' copy): without
+	// the wait the device would go on storing pixels into a frame the zero-means-pending protocol has already handed to the next
+	// call — or into unmapped memory — and results would still be landing in a staging buffer the next call re-uses.  (ADVICE r4;
+	// settle_members below is the same rule for several devices.)
+	struct frame_scope
+	{
+		hipStream_t stream;
+		bool armed = false;				   // the device may be storing into host memory: no return before the stream has drained
+		frame_delivery* carried = nullptr; // begun and not finished: no thread keeps copying, the staging frame is wiped before its next use
+		explicit frame_scope(hipStream_t s, bool arm = false) : stream(s), armed(arm) {}
+		frame_scope(const frame_scope&) = delete;
+		frame_scope& operator=(const frame_scope&) = delete;
+		~frame_scope()
+		{
+			if (armed && hipStreamSynchronize(stream) != hipSuccess)
+				(void)hipGetLastError();
+			if (carried)
+				carried->abandon();
+		}
+		hipError_t drain() // the success path's wait (a failed one is tried once more on the way out)
+		{
+			const hipError_t drained = hipStreamSynchronize(stream);
+			armed = drained != hipSuccess;
+			return drained;
+		}
+	};
+
+	// The carried shape (rt_hip_render, rt_hip_render_progressive, rt_hip_render_adaptive): the kernels store finished pixels into the
+	// module-owned page-locked frame, the carrier's threads take them on into the caller's buffer (frame.hip), and the float mean
+	// lands in the module's own page-locked buffer and is copied on from there.
+	//   open      the context's delivery (a finished accumulation uses its carrier alone)
+	//   begin     the frame in place, the float buffers reserved, the scope armed; `direct`: the caller's own page-locked frame as
+	//             the device sees it — nothing is staged (RT_HIP_FLAG_PERSISTENT_FRAME)
+	//   ... the launch into d_frame / d_rgb ...
+	//   launched  directly behind the launch: the carrier's threads wake beside the kernel
+	//   ... whatever else the call enqueues ...
+	//   deliver   the float copy, the wait on `end` (the event behind the call's device work; NULL: no stats kept) and on the stream,
+	//             the rest of the frame and the float mean in the caller's memory; `e`: what the caller's own enqueues returned
+	//   account   behind the caller's own bookkeeping: readback_ms, the host phases, render_ms from render_begin to `end`, the stats
+	struct carried_frame
+	{
+		rt_hip_ctx* ctx;
+		uint32_t* pixels_rgba8888;
+		float* rgb_f32;
+		size_t pixels;
+		frame_scope scope;
+		frame_delivery* delivery = nullptr;
+		uint32_t* d_frame = nullptr; // where the launch stores packed pixels ...
+		float* d_rgb = nullptr;		 // ... and the float mean (NULL: not asked for)
+		hipEvent_t end = nullptr;
+		std::chrono::steady_clock::time_point issued{}, waited_from{};
+		carried_frame(rt_hip_ctx* c, uint32_t* caller_pixels, float* caller_rgb, size_t n) : ctx(c), pixels_rgba8888(caller_pixels), rgb_f32(caller_rgb), pixels(n), scope(c->stream) {}
+		rt_hip_status open(const char* who);
+		rt_hip_status begin(uint32_t* direct = nullptr);
+		void launched()
+		{
+			if (scope.carried)
+				scope.carried->launched();
+		}
+		rt_hip_status deliver(hipEvent_t end_event, hipError_t e = hipSuccess);
+		rt_hip_status account(std::chrono::steady_clock::time_point entered, rt_hip_stats* stats);
+	};
+
+	// The staged shape (rt_hip_render_temporal, rt_hip_render_upscaled, rt_hip_denoise_progressive): the results lie in device buffers;
+	// packed pixels, an optional float image and an optional count word go to the feature's page-locked landing, then by memcpy into
+	// the caller's plain memory (the runtime never touches the caller's pages).
+	struct staged_results
+	{
+		pinned_buffer& staging;
+		size_t rgba_bytes, rgb_bytes; // rgb_bytes 0: no float image
+		bool word;
+		std::chrono::steady_clock::time_point waited_from{}; // where readback_ms starts
+		hipError_t reserve() { return staging.reserve(rgba_bytes + rgb_bytes + (word ? sizeof(uint32_t) : 0u)); }
+		// enqueues the copies on the scope's stream, drains it, fills the caller's pointers; *out_word (may be NULL) is the word
+		rt_hip_status deliver(frame_scope& scope, const void* d_packed, const void* d_rgb, const void* d_word, uint32_t* pixels_rgba8888, float* rgb_f32, uint32_t* out_word);
+	};
 
 	// After the first launch of a multi-GPU frame nothing may return before every member's stream has drained: a member
 	// that is still storing into the frame (or into stripe buffers a later call would re-use) must not outlive the call

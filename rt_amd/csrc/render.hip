@@ -462,99 +462,32 @@ extern "C" rt_hip_status rt_hip_render(rt_hip_ctx* ctx,
 		if (ctx->multi)
 			return render_multi(ctx, scene, pixels_rgba8888, width, height, seed, flags, rgb_f32, stats, entered);
 
-		const auto scene_t0 = std::chrono::steady_clock::now();
 		scene_request request;
-		if (const rt_hip_status st = open_request(request, scene))
+		if (const rt_hip_status st = resident_scene(ctx, scene, request))
 			return st;
-		ctx->phases = rt_hip_phases{};
-		if (const rt_hip_status st = make_resident(ctx, request))
-			return st;
-		ctx->stats.upload_ms = static_cast<float>(seconds_since(scene_t0) * 1e3); // the frame's whole scene check, fingerprint pass included
 		// Where the kernel stores its finished pixels (4 bytes per pixel over PCIe while the rest of the frame is still being
 		// traced): the caller's own buffer if it is page-locked and mapped (RT_HIP_FLAG_PERSISTENT_FRAME), else the module's
 		// own page-locked frame, from which the carrier's threads take them on into the caller's buffer (frame.hip).
-		uint32_t* d_frame = nullptr;
+		uint32_t* direct = nullptr;
 		if (ctx->pinned_frame)
 		{
 			void* device_view = nullptr;
 			if (hipHostGetDevicePointer(&device_view, pixels_rgba8888, 0) == hipSuccess && device_view)
-				d_frame = static_cast<uint32_t*>(device_view);
+				direct = static_cast<uint32_t*>(device_view);
 			else
 				(void)hipGetLastError();
 		}
-		frame_delivery* const delivery = delivery_of(ctx);
-		if (!delivery)
-			return fail(RT_HIP_RUNTIME_ERROR, "rt_hip_render: out of host memory");
-		struct abandon_unless_finished // any early exit below: no thread keeps copying, the staging frame is wiped before its next use
-		{
-			frame_delivery* delivery;
-			~abandon_unless_finished()
-			{
-				if (delivery)
-					delivery->abandon();
-			}
-		} staged{ nullptr };
-		// Declared AFTER `staged`, so that it runs FIRST on every early exit: whatever this call has put on the stream has
-		// drained before the staging frame is abandoned (wiped, or on growth unmapped, by the next begin()).  render_device can
-		// fail AFTER its kernel is enqueued (hipGetLastError, the timing events, the counters' copy): without this the device
-		// would go on storing pixels into a frame the zero-means-pending protocol has already handed to the next call — or
-		// into unmapped memory.  (multi.hip's settle_members is the same rule for several devices.)
-		struct drain_before_abandoning
-		{
-			hipStream_t stream;
-			bool armed;
-			~drain_before_abandoning()
-			{
-				if (armed && hipStreamSynchronize(stream) != hipSuccess)
-					(void)hipGetLastError();
-			}
-		} drain{ ctx->stream, false };
-		if (!d_frame)
-		{
-			if (const rt_hip_status st = delivery->begin(pixels_rgba8888, pixels, &d_frame))
-				return st;
-			staged.delivery = delivery;
-		}
-		const size_t rgb_bytes = pixels * 3 * sizeof(float);
-		if (rgb_f32)
-		{
-			RT_HIP_TRY(ctx->frame_rgb.reserve(rgb_bytes));
-			RT_HIP_TRY(ctx->staging_rgb.reserve(rgb_bytes));
-		}
-		drain.armed = true; // from here on the device may be storing into host memory: no return before the stream has drained
-		if (const rt_hip_status st = render_device(ctx, width, height, seed, flags & render_flag_mask, nullptr, d_frame, rgb_f32 ? ctx->frame_rgb.as<float>() : nullptr, ctx->stream, false, keep_stats, true, nullptr, true))
+		carried_frame frame(ctx, pixels_rgba8888, rgb_f32, pixels);
+		if (const rt_hip_status st = frame.open("rt_hip_render"))
 			return st;
-		if (staged.delivery)
-			staged.delivery->launched();
-		hipError_t e = hipSuccess;
-		if (rgb_f32) // the float mean lands in the module's own page-locked buffer and is copied on from there
-			e = hipMemcpyAsync(ctx->staging_rgb.ptr, ctx->frame_rgb.ptr, rgb_bytes, hipMemcpyDeviceToHost, ctx->stream);
-		const auto issued = std::chrono::steady_clock::now();
-		if (e == hipSuccess && keep_stats)
-			e = hipEventSynchronize(ctx->render_end);
-		const auto t0 = std::chrono::steady_clock::now();
-		const hipError_t drained = hipStreamSynchronize(ctx->stream);
-		drain.armed = drained != hipSuccess; // (a failed wait is tried once more on the way out)
-		RT_HIP_TRY(e);
-		RT_HIP_TRY(drained);
-		if (staged.delivery)
-		{
-			staged.delivery->finish(); // the last tiles' pixels; returns with the whole frame in the caller's buffer
-			ctx->phases.carrier_bands = static_cast<uint32_t>(staged.delivery->carrier.bands());
-			ctx->phases.carrier_bands_early = static_cast<uint32_t>(staged.delivery->carrier.early_bands());
-			ctx->phases.carrier_helpers = staged.delivery->carrier.helpers();
-			staged.delivery = nullptr;
-		}
-		if (rgb_f32)
-			delivery->carrier.copy(rgb_f32, ctx->staging_rgb.ptr, rgb_bytes);
-		ctx->stats.readback_ms = keep_stats ? static_cast<float>(seconds_since(t0) * 1e3) : 0.0f;
-		ctx->phases.host_issue_ms = static_cast<float>(std::chrono::duration<double>(issued - entered).count() * 1e3);
-		ctx->phases.host_wait_ms = static_cast<float>(seconds_since(issued) * 1e3);
-		if (keep_stats)
-			ctx->phases.render_ms = elapsed_or_zero(ctx->render_begin, ctx->render_end);
-		if (stats)
-			return rt_hip_stats_fetch(ctx, stats);
-		return ok();
+		if (const rt_hip_status st = frame.begin(direct))
+			return st;
+		if (const rt_hip_status st = render_device(ctx, width, height, seed, flags & render_flag_mask, nullptr, frame.d_frame, frame.d_rgb, ctx->stream, false, keep_stats, true, nullptr, true))
+			return st;
+		frame.launched();
+		if (const rt_hip_status st = frame.deliver(keep_stats ? ctx->render_end : nullptr))
+			return st;
+		return frame.account(entered, stats);
 	}
 	catch (const std::exception& e) // nothing may propagate through the C boundary
 	{

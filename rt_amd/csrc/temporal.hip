@@ -152,19 +152,10 @@ extern "C" rt_hip_status rt_hip_reproject_device(rt_hip_ctx* ctx,
 		return fail(RT_HIP_INVALID_ARGUMENT, "rt_hip_reproject_device: d_guide, d_prev_record or d_record_out is not 16-byte aligned (two float4s per pixel)");
 	const size_t pixels = static_cast<size_t>(width) * height;
 	const size_t rgb_bytes = pixels * 3u * sizeof(float), record_bytes = pixels * reproject::record_words * sizeof(float);
-	const struct
-	{
-		const void* ptr;
-		size_t bytes;
-		const char* name;
-	} inputs[] = { { d_guide, record_bytes, "d_guide" }, { d_rgb_in, rgb_bytes, "d_rgb_in" }, { d_prev_rgb, rgb_bytes, "d_prev_rgb" }, { d_prev_record, record_bytes, "d_prev_record" } },
-	  outputs[] = { { d_rgb_out, rgb_bytes, "d_rgb_out" }, { d_record_out, record_bytes, "d_record_out" }, { d_pixels_with_history, sizeof(uint32_t), "d_pixels_with_history" } };
-	for (const auto& out : outputs)
-		for (const auto& in : inputs)
-			if (out.ptr && in.ptr && buffers_overlap(out.ptr, out.bytes, in.ptr, in.bytes))
-				return fail(RT_HIP_INVALID_ARGUMENT, "rt_hip_reproject_device: %s overlaps %s (a pixel reads other pixels' history)", out.name, in.name);
-	if (buffers_overlap(d_rgb_out, rgb_bytes, d_record_out, record_bytes) || (d_pixels_with_history && (buffers_overlap(d_pixels_with_history, 4u, d_rgb_out, rgb_bytes) || buffers_overlap(d_pixels_with_history, 4u, d_record_out, record_bytes))))
-		return fail(RT_HIP_INVALID_ARGUMENT, "rt_hip_reproject_device: the outputs overlap one another");
+	if (const rt_hip_status st = refuse_overlaps("rt_hip_reproject_device", { { d_rgb_out, rgb_bytes, "d_rgb_out" }, { d_record_out, record_bytes, "d_record_out" }, { d_pixels_with_history, sizeof(uint32_t), "d_pixels_with_history" } },
+												 { { d_guide, record_bytes, "d_guide" }, { d_rgb_in, rgb_bytes, "d_rgb_in" }, { d_prev_rgb, rgb_bytes, "d_prev_rgb" }, { d_prev_record, record_bytes, "d_prev_record" } },
+												 "a pixel reads other pixels' history", "the outputs overlap one another"))
+		return st;
 	float forward[16] = {};
 	if (d_prev_rgb)
 	{
@@ -214,8 +205,8 @@ extern "C" rt_hip_status rt_hip_render_temporal(rt_hip_ctx* ctx,
 		return fail(RT_HIP_INVALID_ARGUMENT, "rt_hip_render_temporal: NULL argument");
 	if (!width || !height || width > max_frame_side || height > max_frame_side)
 		return fail(RT_HIP_INVALID_ARGUMENT, "rt_hip_render_temporal: frame %ux%u (1 .. %u a side)", width, height, max_frame_side);
-	if (ctx->multi || ctx->group || ctx->world != 1u)
-		return fail(RT_HIP_UNSUPPORTED, "rt_hip_render_temporal: contexts from rt_hip_create only (not a multi-GPU, rank or frame-group context)");
+	if (const rt_hip_status st = single_context_only("rt_hip_render_temporal", ctx))
+		return st;
 	if (const char* const refused = refused_guide_flag(flags))
 		return fail(RT_HIP_UNSUPPORTED, "rt_hip_render_temporal: %s is not available for temporal frames (0x%x): they take RT_HIP_FLAG_SM_MATERIALS, RT_HIP_FLAG_BVH, RT_HIP_FLAG_BVH_DEVICE_BUILD, RT_HIP_FLAG_TRACE_BOXES and RT_HIP_FLAG_STATS", refused, flags);
 	if (!scene->samples_per_pixel || scene->samples_per_pixel > reproject::max_samples_in)
@@ -226,25 +217,16 @@ extern "C" rt_hip_status rt_hip_render_temporal(rt_hip_ctx* ctx,
 	try
 	{
 		RT_HIP_TRY(hipSetDevice(ctx->device));
-		const auto scene_t0 = std::chrono::steady_clock::now();
 		scene_request request;
-		if (const rt_hip_status st = open_request(request, scene))
+		if (const rt_hip_status st = resident_scene(ctx, scene, request))
 			return st;
-		ctx->phases = rt_hip_phases{};
-		if (const rt_hip_status st = make_resident(ctx, request))
+		bool trace_boxes = false;
+		if (const rt_hip_status st = guide_boxes("rt_hip_render_temporal", ctx, flags, &trace_boxes))
 			return st;
-		ctx->stats.upload_ms = static_cast<float>(seconds_since(scene_t0) * 1e3);
-		const bool trace_boxes = (flags & RT_HIP_FLAG_TRACE_BOXES) && ctx->scene.n_boxes;
-		if (trace_boxes && ctx->scene.n_boxes > box_max_count)
-			return fail(RT_HIP_UNSUPPORTED, "rt_hip_render_temporal: RT_HIP_FLAG_TRACE_BOXES traces at most %u boxes, the scene has %u", box_max_count, ctx->scene.n_boxes);
 
 		// is the context's history this frame's?
 		temporal_state& t = ctx->temporal;
-		frame_key key{};
-		key.scene_fingerprint = request.print;
-		key.samples_per_pixel = scene->samples_per_pixel, key.max_bounces = scene->max_bounces;
-		std::copy(scene->inverse_view_projection, scene->inverse_view_projection + 16, key.inverse_view_projection);
-		key.width = width, key.height = height, key.seed = seed, key.flags = flags & history_frame_flags;
+		const frame_key key = frame_key_of(request, scene, width, height, seed, flags & history_frame_flags);
 		float forward[16] = {};
 		bool carried = t.have_history && same_history(t.key, key) && t.rgb[t.current].bytes >= rgb_bytes && t.record[t.current].bytes >= record_bytes;
 		if (carried && forward_view_projection(t.key.inverse_view_projection, forward).status) // (a matrix no frame could have been traced under)
@@ -269,19 +251,10 @@ extern "C" rt_hip_status rt_hip_render_temporal(rt_hip_ctx* ctx,
 		RT_HIP_TRY(t.found.reserve(sizeof(uint32_t)));
 		if (rgb_f32 && spatial.iterations)
 			RT_HIP_TRY(t.filtered.reserve(rgb_bytes));
-		const size_t found_at = rgba_bytes + (rgb_f32 ? rgb_bytes : 0u);
-		RT_HIP_TRY(t.staging.reserve(found_at + sizeof(uint32_t)));
+		staged_results results{ t.staging, rgba_bytes, rgb_f32 ? rgb_bytes : 0u, true };
+		RT_HIP_TRY(results.reserve());
 
-		struct drain_on_exit // whatever was enqueued has finished before anything returns
-		{
-			hipStream_t stream;
-			bool armed;
-			~drain_on_exit()
-			{
-				if (armed && hipStreamSynchronize(stream) != hipSuccess)
-					(void)hipGetLastError();
-			}
-		} drain{ s, true };
+		frame_scope scope(s, true); // whatever was enqueued has finished before anything returns
 		// 1. the one-shot frame, by the launch rt_hip_render_device makes (its packed pixels land in `packed` and are overwritten below)
 		if (const rt_hip_status st = render_device(ctx, width, height, seed, flags & render_flag_mask, nullptr, t.packed.as<uint32_t>(), t.traced.as<float>(), s, false, keep_stats, false))
 			return st;
@@ -298,32 +271,16 @@ extern "C" rt_hip_status rt_hip_render_temporal(rt_hip_ctx* ctx,
 			delivered = t.filtered.as<float>();
 		if (keep_stats)
 			RT_HIP_TRY(hipEventRecord(t.end, s));
-		// results to the module's page-locked staging, then into the caller's plain memory (the runtime never touches the caller's pages)
-		unsigned char* const landing = t.staging.as<unsigned char>();
-		hipError_t e = hipMemcpyAsync(landing, t.packed.ptr, rgba_bytes, hipMemcpyDeviceToHost, s);
-		if (e == hipSuccess && rgb_f32)
-			e = hipMemcpyAsync(landing + rgba_bytes, delivered, rgb_bytes, hipMemcpyDeviceToHost, s);
-		if (e == hipSuccess)
-			e = hipMemcpyAsync(landing + found_at, t.found.ptr, sizeof(uint32_t), hipMemcpyDeviceToHost, s);
-		const auto t0 = std::chrono::steady_clock::now();
-		const hipError_t drained = hipStreamSynchronize(s);
-		drain.armed = drained != hipSuccess;
-		RT_HIP_TRY(e);
-		RT_HIP_TRY(drained);
+		uint32_t found = 0;
+		if (const rt_hip_status st = results.deliver(scope, t.packed.ptr, delivered, t.found.ptr, pixels_rgba8888, rgb_f32, &found))
+			return st;
 		t.current = to;
 		t.key = key;
 		t.have_history = true;
 		t.frames++;
-		std::memcpy(pixels_rgba8888, landing, rgba_bytes);
-		if (rgb_f32)
-			std::memcpy(rgb_f32, landing + rgba_bytes, rgb_bytes);
 		if (out_info)
-		{
-			uint32_t found = 0;
-			std::memcpy(&found, landing + found_at, sizeof found);
 			*out_info = { t.frames, carried ? 0u : 1u, found, static_cast<uint32_t>(pixels) };
-		}
-		ctx->stats.readback_ms = keep_stats ? static_cast<float>(seconds_since(t0) * 1e3) : 0.0f;
+		ctx->stats.readback_ms = keep_stats ? static_cast<float>(seconds_since(results.waited_from) * 1e3) : 0.0f;
 		if (stats)
 		{
 			if (const rt_hip_status st = rt_hip_stats_fetch(ctx, stats))

@@ -173,21 +173,10 @@ extern "C" rt_hip_status rt_hip_upsample_device(rt_hip_ctx* ctx,
 	if (reinterpret_cast<uintptr_t>(d_guide_low) % 16u || reinterpret_cast<uintptr_t>(d_guide_full) % 16u)
 		return fail(RT_HIP_INVALID_ARGUMENT, "rt_hip_upsample_device: d_guide_low or d_guide_full is not 16-byte aligned (two float4s per pixel)");
 	const size_t pixels = static_cast<size_t>(width) * height, low_pixels = static_cast<size_t>(low_width) * low_height;
-	const struct
-	{
-		const void* ptr;
-		size_t bytes;
-		const char* name;
-	} inputs[] = { { d_rgb_low, low_pixels * 3u * sizeof(float), "d_rgb_low" }, { d_guide_low, low_pixels * denoise::guide_words * sizeof(float), "d_guide_low" }, { d_guide_full, pixels * denoise::guide_words * sizeof(float), "d_guide_full" } },
-	  outputs[] = { { d_rgb_out, pixels * 3u * sizeof(float), "d_rgb_out" }, { d_rgba8_out, pixels * sizeof(uint32_t), "d_rgba8_out" }, { d_orphans, sizeof(uint32_t), "d_orphans" } };
-	for (const auto& out : outputs)
-		for (const auto& in : inputs)
-			if (out.ptr && buffers_overlap(out.ptr, out.bytes, in.ptr, in.bytes))
-				return fail(RT_HIP_INVALID_ARGUMENT, "rt_hip_upsample_device: %s overlaps %s (a pixel reads other pixels' taps)", out.name, in.name);
-	for (size_t i = 0; i < 3u; i++)
-		for (size_t j = i + 1u; j < 3u; j++)
-			if (outputs[i].ptr && outputs[j].ptr && buffers_overlap(outputs[i].ptr, outputs[i].bytes, outputs[j].ptr, outputs[j].bytes))
-				return fail(RT_HIP_INVALID_ARGUMENT, "rt_hip_upsample_device: %s overlaps %s", outputs[i].name, outputs[j].name);
+	if (const rt_hip_status st = refuse_overlaps("rt_hip_upsample_device", { { d_rgb_out, pixels * 3u * sizeof(float), "d_rgb_out" }, { d_rgba8_out, pixels * sizeof(uint32_t), "d_rgba8_out" }, { d_orphans, sizeof(uint32_t), "d_orphans" } },
+												 { { d_rgb_low, low_pixels * 3u * sizeof(float), "d_rgb_low" }, { d_guide_low, low_pixels * denoise::guide_words * sizeof(float), "d_guide_low" }, { d_guide_full, pixels * denoise::guide_words * sizeof(float), "d_guide_full" } },
+												 "a pixel reads other pixels' taps"))
+		return st;
 	try
 	{
 		RT_HIP_TRY(hipSetDevice(ctx->device)); // (a multi-GPU, rank or frame-group context: the root member, like the other device-level calls)
@@ -228,8 +217,8 @@ extern "C" rt_hip_status rt_hip_render_upscaled(rt_hip_ctx* ctx,
 		return fail(RT_HIP_INVALID_ARGUMENT, "rt_hip_render_upscaled: frame %ux%u (1 .. %u a side)", width, height, max_frame_side);
 	if (factor < 2u || factor > upsample::max_factor)
 		return fail(RT_HIP_INVALID_ARGUMENT, "rt_hip_render_upscaled: factor = %u (2 .. %u)", factor, upsample::max_factor);
-	if (ctx->multi || ctx->group || ctx->world != 1u)
-		return fail(RT_HIP_UNSUPPORTED, "rt_hip_render_upscaled: contexts from rt_hip_create only (not a multi-GPU, rank or frame-group context)");
+	if (const rt_hip_status st = single_context_only("rt_hip_render_upscaled", ctx))
+		return st;
 	if (const char* const refused = refused_guide_flag(flags))
 		return fail(RT_HIP_UNSUPPORTED, "rt_hip_render_upscaled: %s is not available for upscaled frames (0x%x): they take RT_HIP_FLAG_SM_MATERIALS, RT_HIP_FLAG_BVH, RT_HIP_FLAG_BVH_DEVICE_BUILD, RT_HIP_FLAG_TRACE_BOXES and RT_HIP_FLAG_STATS", refused, flags);
 	uint32_t w = 0, h = 0;
@@ -242,17 +231,12 @@ extern "C" rt_hip_status rt_hip_render_upscaled(rt_hip_ctx* ctx,
 	try
 	{
 		RT_HIP_TRY(hipSetDevice(ctx->device));
-		const auto scene_t0 = std::chrono::steady_clock::now();
 		scene_request request;
-		if (const rt_hip_status st = open_request(request, scene))
+		if (const rt_hip_status st = resident_scene(ctx, scene, request))
 			return st;
-		ctx->phases = rt_hip_phases{};
-		if (const rt_hip_status st = make_resident(ctx, request))
+		bool trace_boxes = false;
+		if (const rt_hip_status st = guide_boxes("rt_hip_render_upscaled", ctx, flags, &trace_boxes))
 			return st;
-		ctx->stats.upload_ms = static_cast<float>(seconds_since(scene_t0) * 1e3);
-		const bool trace_boxes = (flags & RT_HIP_FLAG_TRACE_BOXES) && ctx->scene.n_boxes;
-		if (trace_boxes && ctx->scene.n_boxes > box_max_count)
-			return fail(RT_HIP_UNSUPPORTED, "rt_hip_render_upscaled: RT_HIP_FLAG_TRACE_BOXES traces at most %u boxes, the scene has %u", box_max_count, ctx->scene.n_boxes);
 
 		upscale_state& u = ctx->upscale;
 		const hipStream_t s = ctx->stream;
@@ -268,19 +252,10 @@ extern "C" rt_hip_status rt_hip_render_upscaled(rt_hip_ctx* ctx,
 			RT_HIP_TRY(u.rgb.reserve(rgb_bytes));
 		RT_HIP_TRY(u.packed.reserve(rgba_bytes));
 		RT_HIP_TRY(u.orphans.reserve(sizeof(uint32_t)));
-		const size_t orphans_at = rgba_bytes + (rgb_f32 ? rgb_bytes : 0u);
-		RT_HIP_TRY(u.staging.reserve(orphans_at + sizeof(uint32_t)));
+		staged_results results{ u.staging, rgba_bytes, rgb_f32 ? rgb_bytes : 0u, true };
+		RT_HIP_TRY(results.reserve());
 
-		struct drain_on_exit // whatever was enqueued has finished before anything returns
-		{
-			hipStream_t stream;
-			bool armed;
-			~drain_on_exit()
-			{
-				if (armed && hipStreamSynchronize(stream) != hipSuccess)
-					(void)hipGetLastError();
-			}
-		} drain{ s, true };
+		frame_scope scope(s, true); // whatever was enqueued has finished before anything returns
 		// 1. the one-shot LOW frame, by the launch rt_hip_render_device makes (its packed pixels are not used)
 		if (const rt_hip_status st = render_device(ctx, w, h, seed, flags & render_flag_mask, nullptr, u.low_packed.as<uint32_t>(), u.low_mean.as<float>(), s, false, keep_stats, false))
 			return st;
@@ -300,28 +275,12 @@ extern "C" rt_hip_status rt_hip_render_upscaled(rt_hip_ctx* ctx,
 			return st;
 		if (keep_stats)
 			RT_HIP_TRY(hipEventRecord(u.end, s));
-		// results to the module's page-locked staging, then into the caller's plain memory (the runtime never touches the caller's pages)
-		unsigned char* const landing = u.staging.as<unsigned char>();
-		hipError_t e = hipMemcpyAsync(landing, u.packed.ptr, rgba_bytes, hipMemcpyDeviceToHost, s);
-		if (e == hipSuccess && rgb_f32)
-			e = hipMemcpyAsync(landing + rgba_bytes, u.rgb.ptr, rgb_bytes, hipMemcpyDeviceToHost, s);
-		if (e == hipSuccess)
-			e = hipMemcpyAsync(landing + orphans_at, u.orphans.ptr, sizeof(uint32_t), hipMemcpyDeviceToHost, s);
-		const auto t0 = std::chrono::steady_clock::now();
-		const hipError_t drained = hipStreamSynchronize(s);
-		drain.armed = drained != hipSuccess;
-		RT_HIP_TRY(e);
-		RT_HIP_TRY(drained);
-		std::memcpy(pixels_rgba8888, landing, rgba_bytes);
-		if (rgb_f32)
-			std::memcpy(rgb_f32, landing + rgba_bytes, rgb_bytes);
+		uint32_t orphans = 0;
+		if (const rt_hip_status st = results.deliver(scope, u.packed.ptr, u.rgb.ptr, u.orphans.ptr, pixels_rgba8888, rgb_f32, &orphans))
+			return st;
 		if (out_info)
-		{
-			uint32_t orphans = 0;
-			std::memcpy(&orphans, landing + orphans_at, sizeof orphans);
 			*out_info = { w, h, orphans, static_cast<uint32_t>(pixels) };
-		}
-		ctx->stats.readback_ms = keep_stats ? static_cast<float>(seconds_since(t0) * 1e3) : 0.0f;
+		ctx->stats.readback_ms = keep_stats ? static_cast<float>(seconds_since(results.waited_from) * 1e3) : 0.0f;
 		if (stats)
 		{
 			if (const rt_hip_status st = rt_hip_stats_fetch(ctx, stats))
