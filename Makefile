@@ -129,10 +129,22 @@ variant: $(HIP_OBJS) $(OBJDIR)/kat.o
 	$(HIPCC) --offload-arch=gfx950 -fPIC -shared -o $(LIBDIR)/librt_hip_$(NAME).so $(HIP_OBJS) $(OBJDIR)/kat.o -L/opt/rocm/lib -lrccl -lpthread
 
 # windowless driver: the registry, the hip_ray_tracer plug-in and the scene loader, linked against the C ABI only
+# (the plug-in's body is shim/rt_hip_plugin.hpp, which finds <rt_hip.h> on the include path as it does inside rt: -Iinclude)
 HEADLESS_SRC := rt_amd/host/main.cpp rt_amd/host/hip_ray_tracer.cpp rt_amd/host/scene.cpp rt_amd/host/toml_subset.cpp
-rt_amd/bin/rt_headless: $(HEADLESS_SRC) $(HOST_HDR) $(LIBDIR)/librt_hip.so
+rt_amd/bin/rt_headless: $(HEADLESS_SRC) $(HOST_HDR) shim/rt_hip_plugin.hpp $(LIBDIR)/librt_hip.so
 	@mkdir -p rt_amd/bin
-	$(CXX) $(HOSTFLAGS) -o $@ $(HEADLESS_SRC) -L$(LIBDIR) -lrt_hip -Wl,-rpath,'$$ORIGIN/../lib'
+	$(CXX) $(HOSTFLAGS) -Iinclude -o $@ $(HEADLESS_SRC) -L$(LIBDIR) -lrt_hip -Wl,-rpath,'$$ORIGIN/../lib'
+
+# `make sanitize-plugin`: the plug-in behind the main() of tests/native/plugin_calls.cpp — a recording fake of the C entry points it links,
+# no GPU — under AddressSanitizer and UndefinedBehaviorSanitizer, run over the RT_HIP_GROUP, RT_HIP_DEVICES and RT_HIP_LIGHTS rows of
+# tests/test_plugin_calls.py's matrix (the parsers with buffers of their own, the emission table's upkeep) and held to
+# tests/golden/plugin_calls.txt.  CPU only, nothing is loaded into python (it starts the program, one process per row); the binary
+# goes to build/ and is run at once
+PLUGIN_CALLS_SRC := tests/native/plugin_calls.cpp rt_amd/host/hip_ray_tracer.cpp rt_amd/host/scene.cpp rt_amd/host/toml_subset.cpp
+sanitize-plugin: $(PLUGIN_CALLS_SRC) $(HOST_HDR) shim/rt_hip_plugin.hpp
+	@mkdir -p build
+	$(CXX) -O1 -g -std=c++20 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -Iinclude -Irt_amd/host $(PLUGIN_CALLS_SRC) -o build/plugin_calls_sanitize
+	python3 -m tests.test_plugin_calls check build/plugin_calls_sanitize RT_HIP_GROUP RT_HIP_DEVICES RT_HIP_LIGHTS
 
 # the device builder of the sphere hierarchy restated serially over its own per-element header, g++ alone (tests/test_bvh_lbvh_reference.py
 # builds its own copy; this one is for the command line)
@@ -249,4 +261,4 @@ clean:
 	rm -f $(LIBDIR)/*.so rt_amd/bin/rt_headless tests/native/lbvh_reference tests/native/libbox_reference.so tests/native/libdenoise_reference.so tests/native/libreproject_reference.so tests/native/libadaptive_reference.so tests/native/liblight_reference.so tests/native/libdirect_reference.so tests/native/libupsample_reference.so
 	$(MAKE) -C oracle clean
 
-.PHONY: all oracle clean variant sanitize-temporal sanitize-box-bvh sanitize-adaptive sanitize-lights sanitize-sky-band sanitize-upsample
+.PHONY: all oracle clean variant sanitize-temporal sanitize-box-bvh sanitize-adaptive sanitize-lights sanitize-sky-band sanitize-upsample sanitize-plugin

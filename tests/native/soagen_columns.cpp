@@ -174,7 +174,7 @@ int main(int argc, char** argv)
 
 	const uint32_t width = 96, height = 54;
 	rt_hip_scene s{};
-	// what shim/hip_ray_tracer.cpp does with scene.spheres.center_x() ... (the named accessors are column<N>())
+	// what gather_scene() of shim/rt_hip_plugin.hpp does with scene.spheres.center_x() ... (the named accessors are column<N>())
 	s.n_spheres = static_cast<uint32_t>(spheres.size());
 	s.sphere_material = spheres.column<1>();
 	s.sphere_center_x = spheres.column<2>();
