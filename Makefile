@@ -114,9 +114,14 @@ $(LIBDIR)/librt_hip.so: $(HIP_OBJS)
 
 # test-only: the known-answer entry points of include/rt_hip_kat.h (never shipped; loads next to librt_hip.so)
 # (with its own copies of both builders of the sphere hierarchy: librt_hip.so exports neither)
-$(LIBDIR)/librt_hip_kat.so: $(OBJDIR)/kat.o $(OBJDIR)/bvh.o $(OBJDIR)/box_bvh.o $(OBJDIR)/bvh_build.o $(LIBDIR)/librt_hip.so
-	$(HIPCC) --offload-arch=gfx950 -fPIC -shared -o $@ $(OBJDIR)/kat.o $(OBJDIR)/bvh.o $(OBJDIR)/box_bvh.o $(OBJDIR)/bvh_build.o -L$(LIBDIR) -lrt_hip -Wl,-rpath,'$$ORIGIN' -L/opt/rocm/lib -lrccl
+# (kat_fast.o: contract.hpp's fast leaf functions as RT_HIP_FLAG_FAST's build of the kernels compiles them, for rt_hip_kat_fast_math — FASTFLAGS,
+# this library only: nothing of it is linked into librt_hip.so)
+$(LIBDIR)/librt_hip_kat.so: $(OBJDIR)/kat.o $(OBJDIR)/kat_fast.o $(OBJDIR)/bvh.o $(OBJDIR)/box_bvh.o $(OBJDIR)/bvh_build.o $(LIBDIR)/librt_hip.so
+	$(HIPCC) --offload-arch=gfx950 -fPIC -shared -o $@ $(OBJDIR)/kat.o $(OBJDIR)/kat_fast.o $(OBJDIR)/bvh.o $(OBJDIR)/box_bvh.o $(OBJDIR)/bvh_build.o -L$(LIBDIR) -lrt_hip -Wl,-rpath,'$$ORIGIN' -L/opt/rocm/lib -lrccl
 $(OBJDIR)/kat.o: include/rt_hip_kat.h
+$(OBJDIR)/kat_fast.o: rt_amd/csrc/kat_fast.hip rt_amd/csrc/contract.hpp rt_amd/csrc/frame_setup.hpp
+	@mkdir -p $(OBJDIR)
+	$(HIPCC) $(FASTFLAGS) $(DEFS) -c $< -o $@
 
 $(LIBDIR)/librt_host.so: $(HOST_SRC) $(HOST_HDR)
 	@mkdir -p $(LIBDIR)
@@ -124,9 +129,9 @@ $(LIBDIR)/librt_host.so: $(HOST_SRC) $(HOST_HDR)
 
 # experiment builds for tools/gpu_ab.py: make variant NAME=x DEFS="-DRT_HIP_SOMETHING=1" -> rt_amd/lib/librt_hip_x.so
 # (objects under build/obj<NAME>; an experiment library carries the known-answer and debug entry points itself)
-variant: $(HIP_OBJS) $(OBJDIR)/kat.o
+variant: $(HIP_OBJS) $(OBJDIR)/kat.o $(OBJDIR)/kat_fast.o
 	@mkdir -p $(LIBDIR)
-	$(HIPCC) --offload-arch=gfx950 -fPIC -shared -o $(LIBDIR)/librt_hip_$(NAME).so $(HIP_OBJS) $(OBJDIR)/kat.o -L/opt/rocm/lib -lrccl -lpthread
+	$(HIPCC) --offload-arch=gfx950 -fPIC -shared -o $(LIBDIR)/librt_hip_$(NAME).so $(HIP_OBJS) $(OBJDIR)/kat.o $(OBJDIR)/kat_fast.o -L/opt/rocm/lib -lrccl -lpthread
 
 # windowless driver: the registry, the hip_ray_tracer plug-in and the scene loader, linked against the C ABI only
 # (the plug-in's body is shim/rt_hip_plugin.hpp, which finds <rt_hip.h> on the include path as it does inside rt: -Iinclude)

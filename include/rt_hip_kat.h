@@ -127,6 +127,11 @@ RT_HIP_API rt_hip_status rt_hip_kat_sqrt_div(rt_hip_ctx* ctx, uint32_t n, const 
  * k = 0 sqrt, 1 reciprocal, 2 reciprocal of sqrt.  All three counts must be 0. */
 RT_HIP_API rt_hip_status rt_hip_kat_exhaustive_math(rt_hip_ctx* ctx, uint64_t out_mismatches[3], uint32_t out_first[3]);
 
+/* RT_HIP_FLAG_FAST's leaf functions (the fast half of rt_amd/csrc/contract.hpp, compiled as the fast build of the kernels is:
+ * rt_amd/csrc/kat_fast.hip) per element: out_sqrt[i] = sqrt_rn(x[i]), out_rcp[i] = rcp_rn(x[i]), out_rsq[i] = inv_sqrt_rn(x[i]),
+ * out_div[i] = divide(x[i], y[i]).  The hardware's approximations as they are: tests MEASURE their error against binary64. */
+RT_HIP_API rt_hip_status rt_hip_kat_fast_math(rt_hip_ctx* ctx, uint32_t n, const float* x, const float* y, float* out_sqrt, float* out_rcp, float* out_rsq, float* out_div);
+
 /* RT_HIP_FLAG_DIRECT_LIGHT's rules (rt_amd/csrc/direct_light_rules.hpp) as the device computes them; both must equal
  * the same header compiled with g++ (tests/native/direct_reference.cpp) bit for bit.
  * The octahedral map: out[4 i ..] = (p.x, p.y, p.z, dot(p, p)) of the numerators (ka[i], kb[i]), each below 2^24. */

@@ -322,6 +322,7 @@ RT_HIP_KAT_SYMBOLS = [
     ("rt_hip_kat_box_bvh_builds", C.c_int, [C.c_void_p, C.c_void_p]),
     ("rt_hip_kat_sqrt_div", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rt_hip_kat_exhaustive_math", C.c_int, [C.c_void_p, C.POINTER(C.c_uint64 * 3), C.POINTER(C.c_uint32 * 3)]),
+    ("rt_hip_kat_fast_math", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rt_hip_kat_direct_octahedral", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rt_hip_kat_direct_aim", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
 ]

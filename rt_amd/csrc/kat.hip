@@ -756,6 +756,35 @@ extern "C" rt_hip_status rt_hip_kat_sqrt_div(rt_hip_ctx* ctx, uint32_t n, const 
 	return RT_HIP_OK;
 }
 
+// kat_fast.hip: this library's one unit built with the Makefile's FASTFLAGS — contract.hpp's fast leaf functions, one thread per element
+namespace rt_hip
+{
+	void launch_kat_fast_math(uint32_t n, const float* d_x, const float* d_y, float* d_sqrt, float* d_rcp, float* d_rsq, float* d_div, hipStream_t stream);
+}
+
+extern "C" rt_hip_status rt_hip_kat_fast_math(rt_hip_ctx* ctx, uint32_t n, const float* x, const float* y, float* out_sqrt, float* out_rcp, float* out_rsq, float* out_div)
+{
+	if (!ctx || !n || !x || !y || !out_sqrt || !out_rcp || !out_rsq || !out_div)
+		return kat_fail(RT_HIP_INVALID_ARGUMENT, "rt_hip_kat_fast_math: invalid argument");
+	RT_HIP_KAT_TRY(hipSetDevice(ctx->device));
+	const size_t bytes = static_cast<size_t>(n) * sizeof(float);
+	scratch in, out;
+	RT_HIP_KAT_TRY(in.reserve(2 * bytes));
+	RT_HIP_KAT_TRY(out.reserve(4 * bytes));
+	std::memcpy(in.host.as<unsigned char>(), x, bytes);
+	std::memcpy(in.host.as<unsigned char>() + bytes, y, bytes);
+	RT_HIP_KAT_TRY(hipMemcpy(in.device.ptr, in.host.ptr, 2 * bytes, hipMemcpyHostToDevice));
+	const float* const d_in = in.device.as<float>();
+	float* const d_out = out.device.as<float>();
+	launch_kat_fast_math(n, d_in, d_in + n, d_out, d_out + n, d_out + 2 * static_cast<size_t>(n), d_out + 3 * static_cast<size_t>(n), nullptr);
+	RT_HIP_KAT_TRY(hipGetLastError());
+	RT_HIP_KAT_TRY(hipMemcpy(out.host.ptr, out.device.ptr, 4 * bytes, hipMemcpyDeviceToHost));
+	float* const results[4] = { out_sqrt, out_rcp, out_rsq, out_div };
+	for (size_t k = 0; k < 4; k++)
+		std::memcpy(results[k], out.host.as<unsigned char>() + k * bytes, bytes);
+	return RT_HIP_OK;
+}
+
 // both entries of RT_HIP_FLAG_DIRECT_LIGHT's rules: in = NULL is the octahedral map (4 floats out per item), else the aim (5 floats out)
 static rt_hip_status kat_direct(const char* name, rt_hip_ctx* ctx, uint32_t n, const uint32_t* ka, const uint32_t* kb, const float* in, const float* radius, uint32_t n_lights, float* out)
 {

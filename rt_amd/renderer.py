@@ -490,6 +490,15 @@ class HipRayTracer:
         capi.check_kat(capi.kat_lib().rt_hip_kat_sqrt_div(self._ctx, a.size, a.ctypes.data, b.ctypes.data, s.ctypes.data, q.ctypes.data))
         return s, q
 
+    def kat_fast_math(self, x: np.ndarray, y: np.ndarray):
+        """RT_HIP_FLAG_FAST's leaf functions on the device, per element: (sqrt_rn(x), rcp_rn(x), inv_sqrt_rn(x), divide(x, y))."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        y = np.ascontiguousarray(y, dtype=np.float32)
+        assert x.shape == y.shape
+        out = [np.empty_like(x) for _ in range(4)]
+        capi.check_kat(capi.kat_lib().rt_hip_kat_fast_math(self._ctx, x.size, x.ctypes.data, y.ctypes.data, *(o.ctypes.data for o in out)))
+        return tuple(out)
+
     def kat_direct_octahedral(self, ka: np.ndarray, kb: np.ndarray) -> np.ndarray:
         """rt_amd/csrc/direct_light_rules.hpp's octahedral_point on the device: float32[n, 4] = (p.xyz, dot(p, p))."""
         ka = np.ascontiguousarray(ka, dtype=np.uint32)
