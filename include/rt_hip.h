@@ -1022,6 +1022,100 @@ RT_HIP_API rt_hip_status rt_hip_set_emission(rt_hip_ctx* ctx, const float* emiss
  */
 RT_HIP_API rt_hip_status rt_hip_lights_from_spec(const char* spec, const char* const* material_names, uint32_t n_materials, float* out_emission_rgb);
 
+/* ---- tone mapping for HDR frames: device auto-exposure, three curves --------------------------------------- */
+/*
+ * With RT_HIP_FLAG_EMISSION the float mean of a frame lies far above 1, and the only way from a float mean to pixels above is the
+ * renderer's own finish: square root, clamp to [0, 1], pack.  These entry points put an EXPOSURE and a TONE CURVE in front of that
+ * finish, on the device: the exposure is metered from an integer histogram of the frame's log2 luminance (8 bins per octave from
+ * 2^-16 to 2^16, a trimmed mean of the bins in exact integer arithmetic), optionally eased toward from the exposure of the frame
+ * before, and never leaves the device on its way to the pixels.  A contract of its own: + - x, correctly rounded division and
+ * square root, compare-and-select in one stated order, no log, exp or pow anywhere, so that the device's result equals a serial CPU
+ * restatement bit for bit — it is NOT the reference's arithmetic (the reference has no tone mapping).  No speed is promised.
+ * Additions to ABI 6 (RT_HIP_ABI_VERSION stays 6): a caller that may meet an older library looks them up with dlsym.
+ */
+#define RT_HIP_TONEMAP_NONE 0u	   /* o = v */
+#define RT_HIP_TONEMAP_REINHARD 1u /* extended Reinhard on luminance, hue kept: o = v (1 + Yv / white^2) / (1 + Yv) */
+#define RT_HIP_TONEMAP_ACES 2u	   /* the Narkowicz rational fit, per channel */
+
+typedef struct rt_hip_tonemap_params
+{
+	uint32_t curve;			/* RT_HIP_TONEMAP_NONE, _REINHARD or _ACES; default ACES */
+	uint32_t low_permille;	/* the darkest pixels the meter drops, in thousandths of the metered ones; default 50 */
+	uint32_t high_permille; /* ... and the brightest; low_permille + high_permille < 1000; default 20 */
+	float exposure;			/* 0 = auto (metered); finite and > 0 = manual: nothing is metered; default 0 */
+	float key;				/* finite, > 0: the luminance the metered one is mapped to; default 0.18 */
+	float white;			/* 2^-20 .. 2^20: REINHARD's white point, the luminance that maps to 1; default 4 */
+	float min_exposure;		/* finite, > 0: the metered exposure is clamped to [min_exposure, max_exposure]; default 2^-10 */
+	float max_exposure;		/* finite, >= min_exposure; default 2^10 */
+	float adaptation;		/* (0, 1]: 1 = the metered target at once; less: prev + adaptation x (target - prev); default 1 */
+} rt_hip_tonemap_params;
+
+typedef struct rt_hip_tonemap_info
+{
+	float exposure;	   /* the exposure applied */
+	float target;	   /* the metered target (manual exposure: the exposure) */
+	uint32_t counted;  /* pixels that were metered; 0 under a manual exposure, like the three below */
+	uint32_t skipped;  /* pixels whose luminance is NaN, not positive or infinite: not metered */
+	uint32_t kept;	   /* metered pixels inside the rank window */
+	uint32_t mean_q8;  /* the trimmed mean bin, in 1/256 of a bin */
+} rt_hip_tonemap_info;
+
+/* the defaults a NULL `params` stands for; pure host code */
+RT_HIP_API rt_hip_status rt_hip_tonemap_default_params(rt_hip_tonemap_params* out_params);
+
+/*
+ * Parameters from a text, CURVE[:EXPOSURE]: CURVE is none, reinhard or aces; EXPOSURE is auto (the default) or a positive finite
+ * number.  Everything else keeps its default.  Host-only; touches no device.  RT_HIP_INVALID_ARGUMENT, with a message that quotes
+ * the text, for anything else; out_params is untouched then.
+ */
+RT_HIP_API rt_hip_status rt_hip_tonemap_from_spec(const char* spec, rt_hip_tonemap_params* out_params);
+
+/*
+ * Tone mapping as a pure image operation on DEVICE buffers of a whole width x height frame: d_rgb_in (3 * width * height floats, a
+ * frame's float mean in linear light, 16-byte aligned) gives d_rgb_out (3 * width * height floats: the mapped frame, linear light,
+ * neither clamped nor gamma-encoded; optional) and d_rgba8_out (width * height packed pixels: square root, clamp and pack as
+ * rt_hip_render finishes a pixel; optional) — not both NULL.  d_rgb_out == d_rgb_in exactly is allowed (in place); every other
+ * overlap between the buffers is refused.
+ *   d_state   the caller's 8-word DEVICE record, written by every call: exposure (float bits), target (float bits), counted,
+ *             skipped, kept, mean_q8, and two reserved words (0).  With params->adaptation < 1 word 0 is also READ, as the exposure
+ *             of the frame before (a word that is not a finite positive float — a zeroed record — starts over at the target).
+ * Three launches on `stream` (histogram, exposure, pixels; one under a manual exposure) and no readback: asynchronous.  The
+ * histogram's 257 words belong to the context: the tone-mapping calls of one context must be ordered on ONE stream (or by the
+ * caller).  It reads no scene.  On a multi-GPU, rank or frame-group context the root member answers.
+ */
+RT_HIP_API rt_hip_status rt_hip_tonemap_device(rt_hip_ctx* ctx,
+									uint32_t width,
+									uint32_t height,
+									const float* d_rgb_in,
+									const rt_hip_tonemap_params* params, /* NULL = defaults */
+									uint32_t* d_state,
+									float* d_rgb_out,	   /* nullable; may be d_rgb_in */
+									uint32_t* d_rgba8_out, /* nullable, not both NULL */
+									void* stream);
+
+/*
+ * Drop-in level: one call is one tone-mapped frame.  The scene is uploaded by fingerprint as in rt_hip_render; the one-shot frame
+ * is traced into a device float mean by the launch rt_hip_render_device makes, mapped by the three launches above and copied into
+ * the caller's plain HOST memory: pixels_rgba8888 (width * height) and, optionally, rgb_f32 (3 * width * height: the MAPPED frame
+ * in linear light).  The context keeps the state record from call to call (what params->adaptation < 1 eases from) and zeroes it
+ * when the frame's size changes.
+ *   stats     optional: the traced frame's; render_ms runs through the last of the three launches.
+ * Flags: every flag of a one-shot frame (RT_HIP_FLAG_EMISSION and RT_HIP_FLAG_DIRECT_LIGHT among them) and RT_HIP_FLAG_STATS;
+ * RT_HIP_FLAG_PREVIEW and RT_HIP_FLAG_PERSISTENT_FRAME are refused with RT_HIP_UNSUPPORTED and their names.  Contexts from
+ * rt_hip_create only.
+ */
+RT_HIP_API rt_hip_status rt_hip_render_tonemapped(rt_hip_ctx* ctx,
+									const rt_hip_scene* scene,
+									uint32_t* pixels_rgba8888,
+									uint32_t width,
+									uint32_t height,
+									uint64_t seed,
+									uint32_t flags,
+									const rt_hip_tonemap_params* params, /* NULL = defaults */
+									float* rgb_f32,						 /* nullable */
+									rt_hip_stats* stats,
+									rt_hip_tonemap_info* out_info);		 /* nullable */
+
 /* Drop the page-lock taken under RT_HIP_FLAG_PERSISTENT_FRAME (see there).  Waits for the context's stream first. */
 RT_HIP_API void rt_hip_forget_frame(rt_hip_ctx* ctx);
 

@@ -34,6 +34,7 @@ RT_HIP_FLAG_TRACE_BOXES = 1 << 13  # the traced frame hits the scene's boxes too
 RT_HIP_FLAG_BOX_BVH = 1 << 14  # with RT_HIP_FLAG_TRACE_BOXES: the boxes through a hierarchy of their own, no 256-box cap, same frame
 RT_HIP_FLAG_EMISSION = 1 << 16  # materials with a row > 0 in the context's emission table are lights; bit 15 is unassigned
 RT_HIP_FLAG_DIRECT_LIGHT = 1 << 17  # with RT_HIP_FLAG_EMISSION: lambert vertices sample the sphere lights directly
+RT_HIP_TONEMAP_NONE, RT_HIP_TONEMAP_REINHARD, RT_HIP_TONEMAP_ACES = 0, 1, 2  # rt_hip_tonemap_params.curve
 RT_HIP_MULTI_PEER_COPY = 1 << 0
 RT_HIP_MULTI_DIRECT_FRAME = 1 << 1
 RT_HIP_TRANSPORT_NONE, RT_HIP_TRANSPORT_RCCL_GATHER, RT_HIP_TRANSPORT_PEER_COPY, RT_HIP_TRANSPORT_DIRECT_FRAME = 0, 1, 2, 3
@@ -195,6 +196,25 @@ class RtHipUpscaleInfo(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class RtHipTonemapParams(C.Structure):
+    """``rt_hip_tonemap_params`` (include/rt_hip.h): the curve, the meter's rank window, manual or metered exposure and its limits."""
+
+    _fields_ = [("curve", C.c_uint32), ("low_permille", C.c_uint32), ("high_permille", C.c_uint32), ("exposure", C.c_float), ("key", C.c_float), ("white", C.c_float), ("min_exposure", C.c_float),
+                ("max_exposure", C.c_float), ("adaptation", C.c_float)]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class RtHipTonemapInfo(C.Structure):
+    """``rt_hip_tonemap_info`` (include/rt_hip.h): the exposure a call of rt_hip_render_tonemapped applied and what its meter saw."""
+
+    _fields_ = [("exposure", C.c_float), ("target", C.c_float), ("counted", C.c_uint32), ("skipped", C.c_uint32), ("kept", C.c_uint32), ("mean_q8", C.c_uint32)]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class RtHipAdaptiveParams(C.Structure):
     """``rt_hip_adaptive_params`` (include/rt_hip.h): when a pixel of an adaptive accumulation has converged."""
 
@@ -303,6 +323,14 @@ RT_HIP_SYMBOLS = [
     ("rt_hip_adaptive_last_info", C.c_int, [C.POINTER(RtHipAdaptiveInfo)]),
     ("rt_hip_set_emission", C.c_int, [C.c_void_p, c_float_p, C.c_uint32]),
     ("rt_hip_lights_from_spec", C.c_int, [C.c_char_p, C.POINTER(C.c_char_p), C.c_uint32, c_float_p]),
+    ("rt_hip_tonemap_default_params", C.c_int, [C.POINTER(RtHipTonemapParams)]),
+    ("rt_hip_tonemap_from_spec", C.c_int, [C.c_char_p, C.POINTER(RtHipTonemapParams)]),
+    ("rt_hip_tonemap_device", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(RtHipTonemapParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    (
+        "rt_hip_render_tonemapped",
+        C.c_int,
+        [C.c_void_p, C.POINTER(RtHipScene), C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(RtHipTonemapParams), C.c_void_p, C.POINTER(RtHipStats), C.POINTER(RtHipTonemapInfo)],
+    ),
     ("rt_hip_forget_frame", None, [C.c_void_p]),
     ("rt_hip_live_frame_locks", C.c_uint32, []),
 ]

@@ -489,6 +489,7 @@ extern "C" void rt_hip_destroy(rt_hip_ctx* ctx)
 	ctx->temporal.release();
 	ctx->adaptive.release();
 	ctx->upscale.release();
+	ctx->tonemap.release();
 	ctx->counters.release();
 	ctx->frame_rgb.release();
 	ctx->staging_rgb.release();

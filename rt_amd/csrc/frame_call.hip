@@ -141,7 +141,7 @@ rt_hip_status staged_results::deliver(frame_scope& scope, const void* d_packed, 
 	if (e == hipSuccess && rgb_bytes)
 		e = hipMemcpyAsync(landing + rgba_bytes, d_rgb, rgb_bytes, hipMemcpyDeviceToHost, scope.stream);
 	if (e == hipSuccess && word)
-		e = hipMemcpyAsync(landing + word_at, d_word, sizeof(uint32_t), hipMemcpyDeviceToHost, scope.stream);
+		e = hipMemcpyAsync(landing + word_at, d_word, words * sizeof(uint32_t), hipMemcpyDeviceToHost, scope.stream);
 	waited_from = std::chrono::steady_clock::now();
 	const hipError_t drained = scope.drain();
 	RT_HIP_TRY(e);
@@ -150,7 +150,7 @@ rt_hip_status staged_results::deliver(frame_scope& scope, const void* d_packed, 
 	if (rgb_bytes)
 		std::memcpy(rgb_f32, landing + rgba_bytes, rgb_bytes);
 	if (word && out_word)
-		std::memcpy(out_word, landing + word_at, sizeof(uint32_t));
+		std::memcpy(out_word, landing + word_at, words * sizeof(uint32_t));
 	return ok();
 }
 }

@@ -19,6 +19,8 @@
 //                 (parameters, the forward matrix, same_history: temporal.cpp, host compiler; per-pixel rule: reproject_rules.hpp)
 //   upsample.hip  guided upsampling: upsample_frame, rt_hip_upsample_device and the drop-in rt_hip_render_upscaled
 //                 (parameters, sizes: upsample.cpp, host compiler; per-pixel rules: upsample_rules.hpp)
+//   tonemap.hip   tone mapping: luminance_histogram, exposure_from_histogram, tonemap_frame, rt_hip_tonemap_device and the
+//                 drop-in rt_hip_render_tonemapped (parameters, the spec parser: tonemap.cpp, host compiler; per-element rules: tonemap_rules.hpp)
 //   multi.hip     rt_hip_render on several GPUs: stripes, one gather, assemble
 //   group.hip     rt_hip_render as one rank of a frame group (rank processes storing into one shared back buffer)
 //   kernels.hip   the gfx950 kernels (compiled twice: parity contract and RT_HIP_FLAG_FAST arithmetic)
@@ -238,6 +240,28 @@ namespace rt_hip
 		}
 	};
 
+	// what tone mapping keeps on a context (tonemap.hip): everything is grown on demand and freed with the context
+	struct tonemap_state
+	{
+		device_buffer histogram;   // the meter's 256 bins and the skipped count (rt_hip_tonemap_device's too)
+		device_buffer traced;	   // rt_hip_render_tonemapped: the traced float mean, mapped in place
+		device_buffer packed;	   // ... the packed pixels (the traced frame's own, then the mapped ones)
+		device_buffer record;	   // ... the 8-word state record, kept from call to call
+		uint32_t width = 0, height = 0; // ... the frame the record was kept for (0: none)
+		pinned_buffer staging;	   // the results' landing place on the host
+		hipEvent_t end = nullptr;  // behind the three launches (frames that keep stats)
+		void release()
+		{
+			for (device_buffer* b : { &histogram, &traced, &packed, &record })
+				b->release();
+			staging.release();
+			if (end)
+				(void)hipEventDestroy(end);
+			end = nullptr;
+			width = height = 0;
+		}
+	};
+
 	// what adaptive sampling keeps on a context (adaptive.hip): everything is grown on demand and freed with the context
 	struct adaptive_accumulation
 	{
@@ -404,6 +428,9 @@ struct rt_hip_ctx
 		rt_hip::frame_params frame{};
 		uint32_t rows = 0;
 	} sky_band_asked;
+
+	// ---- tone mapping (tonemap.hip) ----
+	rt_hip::tonemap_state tonemap; // the meter's histogram and the scratch of rt_hip_render_tonemapped
 
 	rt_hip_ctx() = default;
 	rt_hip_ctx(const rt_hip_ctx&) = delete;
@@ -659,7 +686,8 @@ namespace rt_hip
 		size_t rgba_bytes, rgb_bytes; // rgb_bytes 0: no float image
 		bool word;
 		std::chrono::steady_clock::time_point waited_from{}; // where readback_ms starts
-		hipError_t reserve() { return staging.reserve(rgba_bytes + rgb_bytes + (word ? sizeof(uint32_t) : 0u)); }
+		uint32_t words = 1;									 // how many words `word` is (rt_hip_render_tonemapped: its state record)
+		hipError_t reserve() { return staging.reserve(rgba_bytes + rgb_bytes + (word ? words * sizeof(uint32_t) : 0u)); }
 		// enqueues the copies on the scope's stream, drains it, fills the caller's pointers; *out_word (may be NULL) is the word
 		rt_hip_status deliver(frame_scope& scope, const void* d_packed, const void* d_rgb, const void* d_word, uint32_t* pixels_rgba8888, float* rgb_f32, uint32_t* out_word);
 	};

@@ -38,6 +38,10 @@
 //                           --temporal, --denoise or --boxes
 //   --direct-light          with --light: lambert surfaces sample the sphere lights directly (exported as RT_HIP_DIRECT_LIGHT=1:
 //                           RT_HIP_FLAG_DIRECT_LIGHT).  Not without --light, and not where --light is refused
+//   --tonemap CURVE[:EXPOSURE]   every frame is exposed and tone-mapped on the device before it is packed (exported to the renderer as
+//                           RT_HIP_TONEMAP: rt_hip_render_tonemapped): CURVE is none, reinhard or aces, EXPOSURE auto (metered
+//                           from the frame, the default) or a positive number.  What --light makes bright is the point.  Hip tracers only,
+//                           one-shot frames only: not with --progressive, --temporal, --adaptive or --upscale
 //   --dolly DX,DY,DZ        the camera moves by that much in world space before every frame after the first (camera::pose)
 //   --shared-frame NAME --rank R --world N   this process is rank R of N rt_headless processes that render ONE frame
 //                together (one per GPU: RT_HIP_DEVICE picks this one's): the back buffer is every process's mapping of the
@@ -46,7 +50,7 @@
 // It renders through renderer_interface::render exactly as window::loop does (src/window.cpp:213-217 via
 // src/main.cpp:315-321): clear to opaque black, then render(scene, pixels, threads).
 #include "renderer.hpp"
-#include "../../include/rt_hip.h" // (rt_hip_adaptive_last_info, rt_hip_live_frame_locks: what --adaptive asks the module itself)
+#include "../../include/rt_hip.h" // (rt_hip_adaptive_last_info, rt_hip_live_frame_locks: what --adaptive asks the module itself; rt_hip_tonemap_from_spec)
 
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -151,7 +155,7 @@ namespace
 
 int main(int argc, char** argv)
 {
-	std::string scene_path, renderer_name, out_path, shared_name, lights;
+	std::string scene_path, renderer_name, out_path, shared_name, lights, tonemap;
 	bool direct_light = false;
 	unsigned width = 800, height = 600, spp = 0, bounces = 0, frames = 1, rank = 0, world = 1, progressive = 0;
 	bool frames_given = false;
@@ -269,6 +273,17 @@ int main(int argc, char** argv)
 			direct_light = true;
 			::setenv("RT_HIP_DIRECT_LIGHT", "1", 1); // (read by the plug-in: RT_HIP_FLAG_DIRECT_LIGHT next to RT_HIP_FLAG_EMISSION)
 		}
+		else if (arg == "--tonemap"sv)
+		{
+			tonemap = value();
+			rt_hip_tonemap_params parsed{};
+			if (rt_hip_tonemap_from_spec(tonemap.c_str(), &parsed) != RT_HIP_OK)
+			{
+				error("--tonemap expects CURVE[:EXPOSURE], none, reinhard or aces and auto or a positive number (", rt_hip_last_error(), ")");
+				return 2;
+			}
+			::setenv("RT_HIP_TONEMAP", tonemap.c_str(), 1); // (read by the plug-in: every one-shot render() is one rt_hip_render_tonemapped frame)
+		}
 		else if (arg == "--dolly"sv)
 		{
 			char trailing = 0;
@@ -287,7 +302,7 @@ int main(int argc, char** argv)
 			world = static_cast<unsigned>(std::strtoul(value(), nullptr, 10));
 		else if (arg == "--help"sv || arg == "-h"sv)
 		{
-			log("usage: rt_headless [--list] [--scene file.toml] [--renderer name] [--size WxH] [--spp N] [--bounces N] [--seed N] [--frames N] [--out file.ppm] [--progressive SAMPLES] [--denoise] [--boxes [--box-bvh]] [--temporal] [--adaptive THRESHOLD] [--upscale FACTOR] [--light KEY=R,G,B]... [--direct-light] [--dolly DX,DY,DZ] [--shared-frame NAME --rank R --world N]");
+			log("usage: rt_headless [--list] [--scene file.toml] [--renderer name] [--size WxH] [--spp N] [--bounces N] [--seed N] [--frames N] [--out file.ppm] [--progressive SAMPLES] [--denoise] [--boxes [--box-bvh]] [--temporal] [--adaptive THRESHOLD] [--upscale FACTOR] [--light KEY=R,G,B]... [--direct-light] [--tonemap CURVE[:EXPOSURE]] [--dolly DX,DY,DZ] [--shared-frame NAME --rank R --world N]");
 			return 0;
 		}
 		else
@@ -316,6 +331,16 @@ int main(int argc, char** argv)
 		if (with || std::string_view{ desc->name }.substr(0, 3) != "hip"sv)
 		{
 			error("--upscale traces one-shot frames of a hip renderer at 1 / FACTOR of the size and rebuilds them (not with --progressive, --temporal, --adaptive, --light or --box-bvh, not '", desc->name, "'): refused with ", with ? with : "this renderer");
+			return 2;
+		}
+	}
+	if (!tonemap.empty())
+	{
+		const char* const with = progressive ? "--progressive" : (temporal ? "--temporal" : (adaptive ? "--adaptive" : (upscale ? "--upscale" : nullptr)));
+		const std::string_view name{ desc->name };
+		if (with || name.substr(0, 3) != "hip"sv || name == "hip_rasterizer"sv)
+		{
+			error("--tonemap maps one-shot frames of a hip tracer (not with --progressive, --temporal, --adaptive or --upscale, not '", desc->name, "'): refused with ", with ? with : "this renderer");
 			return 2;
 		}
 	}

@@ -19,7 +19,7 @@ import ctypes as C
 import numpy as np
 
 from . import capi
-from .capi import RtHipAdaptiveInfo, RtHipAdaptiveParams, RtHipDenoiseParams, RtHipPartition, RtHipPhases, RtHipProgress, RtHipScene, RtHipStats, RtHipTemporalInfo, RtHipTemporalParams, RtHipUpsampleParams, RtHipUpscaleInfo, check
+from .capi import RtHipAdaptiveInfo, RtHipAdaptiveParams, RtHipDenoiseParams, RtHipPartition, RtHipPhases, RtHipProgress, RtHipScene, RtHipStats, RtHipTemporalInfo, RtHipTemporalParams, RtHipTonemapInfo, RtHipTonemapParams, RtHipUpsampleParams, RtHipUpscaleInfo, check
 
 
 def local_rows(height: int, rank: int, world: int, stripe_rows: int = capi.RT_HIP_DEFAULT_STRIPE_ROWS) -> int:
@@ -95,6 +95,21 @@ def upsample_low_size(width: int, height: int, factor: int) -> tuple:
     w, h = C.c_uint32(0), C.c_uint32(0)
     check(capi.hip_lib().rt_hip_upsample_low_size(width, height, factor, C.byref(w), C.byref(h)))
     return w.value, h.value
+
+
+def tonemap_default_params() -> RtHipTonemapParams:
+    """rt_hip_tonemap_default_params: what a NULL `params` of the tone-mapping entry points stands for (pure host code)."""
+    params = RtHipTonemapParams()
+    check(capi.hip_lib().rt_hip_tonemap_default_params(C.byref(params)))
+    return params
+
+
+def tonemap_from_spec(spec: str) -> RtHipTonemapParams:
+    """rt_hip_tonemap_from_spec: the defaults with the curve and the exposure of ``CURVE[:EXPOSURE]`` (none, reinhard or aces; auto or
+    a positive number; pure host code).  Raises RtHipError with the text in the message for anything else."""
+    params = RtHipTonemapParams()
+    check(capi.hip_lib().rt_hip_tonemap_from_spec(spec.encode(), C.byref(params)))
+    return params
 
 
 def denoise_default_params() -> RtHipDenoiseParams:
@@ -334,6 +349,22 @@ class HipRayTracer:
         rgb = np.empty((height, width, 3), dtype=np.float32) if want_rgb else None
         check(self._lib.rt_hip_render_upscaled(self._ctx, C.byref(scene), rgba.ctypes.data, width, height, seed, flags, factor, C.byref(upsample) if upsample is not None else None, C.byref(filter) if filter is not None else None,
                                                rgb.ctypes.data if rgb is not None else None, C.byref(stats_pod) if stats else None, C.byref(info)))
+        return rgba, rgb, stats_pod.as_dict() if stats else {}, info.as_dict()
+
+    # ---- tone mapping ------------------------------------------------------------------------
+    def tonemap_device(self, width: int, height: int, d_rgb_in: int, d_state: int, params: RtHipTonemapParams | None = None, d_rgb_out: int | None = None, d_rgba8_out: int | None = None, stream: int | None = None) -> None:
+        """rt_hip_tonemap_device: a float frame on the DEVICE metered, exposed and mapped (`params` None: the defaults) into
+        `d_rgb_out` (may be `d_rgb_in`) and / or `d_rgba8_out`; `d_state`: the caller's 8-word device record.  Asynchronous on `stream`."""
+        check(self._lib.rt_hip_tonemap_device(self._ctx, width, height, d_rgb_in, C.byref(params) if params is not None else None, d_state, d_rgb_out, d_rgba8_out, stream))
+
+    def render_tonemapped(self, scene: RtHipScene, width: int, height: int, seed: int = 1, flags: int = 0, params: RtHipTonemapParams | None = None, want_rgb: bool = False, stats: bool = True):
+        """rt_hip_render_tonemapped: one frame traced, metered and tone-mapped on the device — (rgba8 uint32[H, W], the MAPPED rgb
+        float32[H, W, 3] or None, stats dict of the traced frame, info dict: exposure, target, counted, skipped, kept, mean_q8)."""
+        stats_pod, info = RtHipStats(), RtHipTonemapInfo()
+        rgba = np.empty((height, width), dtype=np.uint32)
+        rgb = np.empty((height, width, 3), dtype=np.float32) if want_rgb else None
+        check(self._lib.rt_hip_render_tonemapped(self._ctx, C.byref(scene), rgba.ctypes.data, width, height, seed, flags, C.byref(params) if params is not None else None, rgb.ctypes.data if rgb is not None else None,
+                                                 C.byref(stats_pod) if stats else None, C.byref(info)))
         return rgba, rgb, stats_pod.as_dict() if stats else {}, info.as_dict()
 
     # ---- adaptive sampling (DESIGN.md §3.11) -----------------------------------------------------------------

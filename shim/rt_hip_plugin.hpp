@@ -12,10 +12,21 @@
 //   - the rt_hip context is created lazily on the first render() and destroyed with the renderer object;
 //   - render() is noexcept and returns void: on any failure it prints `error: ...` to stderr (the reference's
 //     style, src/main.cpp:43-47) and leaves the caller's pre-cleared frame (src/main.cpp:318) untouched;
-//   - the call blocks until the frame is in `pixels`.
+//   - the call blocks until the frame is in `pixels`;
+//   - entry points added to the C ABI after this text's other calls are declared weak and tested for null: a caller may meet an
+//     older library.
 #pragma once
 
 #include <rt_hip.h>
+
+// Additions to ABI 6 that came after this plug-in's other calls: declared WEAK here, so that a plug-in built from this text still loads
+// against a librt_hip.so that lacks them, and tested for null before use (tonemap_wanted below).
+extern "C"
+{
+	__attribute__((weak)) rt_hip_status rt_hip_render_tonemapped(rt_hip_ctx* ctx, const rt_hip_scene* scene, uint32_t* pixels_rgba8888, uint32_t width, uint32_t height, uint64_t seed, uint32_t flags, const rt_hip_tonemap_params* params,
+																 float* rgb_f32, rt_hip_stats* stats, rt_hip_tonemap_info* out_info);
+	__attribute__((weak)) rt_hip_status rt_hip_tonemap_from_spec(const char* spec, rt_hip_tonemap_params* out_params);
+}
 
 #include <algorithm>
 #include <cstdint>
@@ -260,6 +271,21 @@ namespace rt_hip_plugin
 		return spec;
 	}
 
+	// RT_HIP_TONEMAP=CURVE[:EXPOSURE] (none, reinhard or aces; auto or a positive number; rt_headless --tonemap) makes a one-shot render() of
+	// the two tracers ONE TONE-MAPPED FRAME (rt_hip_render_tonemapped): traced as without the variable — lights and all —
+	// then exposed and mapped on the device.  It is IGNORED, which is said once, where a frame mode (RT_HIP_ADAPTIVE, RT_HIP_TEMPORAL,
+	// RT_HIP_PROGRESSIVE, RT_HIP_UPSCALE) is set, for the preview, where the library lacks the call, where the text cannot be read and where
+	// the module refuses (a renderer of several GPUs): the frames are rt_hip_render's then.  Unset or empty: off, and nothing is said.
+	inline const char* tonemap_spec()
+	{
+		static const char* const spec = []
+		{
+			const char* tonemap = std::getenv("RT_HIP_TONEMAP");
+			return (tonemap && *tonemap) ? tonemap : nullptr;
+		}();
+		return spec;
+	}
+
 	// The struct-of-arrays columns (soagen column accessors, src/soa.hpp), the two sampling scalars and the camera matrix as the POD
 	// the C ABI takes: pointers are borrowed for the call.  The matrix goes element-wise through m(r, c): independent of muu's storage
 	// order (accessor form: src/scene.cpp:179).  `view` is scene.camera.viewport(size of the frame) (mg_ray_tracer.cpp:180).
@@ -314,6 +340,8 @@ namespace rt_hip_plugin
 		bool temporal_unsupported = false; // RT_HIP_TEMPORAL on a renderer of several GPUs: refused once, then whole frames as without it
 		bool adaptive_unsupported = false; // RT_HIP_ADAPTIVE on such a renderer: likewise
 		bool upscale_unsupported = false;  // RT_HIP_UPSCALE on such a renderer, or with lights: likewise
+		bool tonemap_decided = false, tonemap_on = false; // RT_HIP_TONEMAP: looked at once; on: one-shot frames are rt_hip_render_tonemapped's
+		rt_hip_tonemap_params tonemap_params{};			  // ... with these, as rt_hip_tonemap_from_spec read them
 		std::vector<std::string> light_names; // RT_HIP_LIGHTS: the material names the context's emission table was made from
 		bool lights_set = false;
 
@@ -349,6 +377,31 @@ namespace rt_hip_plugin
 			return true;
 		}
 
+		// RT_HIP_TONEMAP, looked at once per renderer: true where its one-shot frames are to be tone-mapped; every reason why not is said here
+		bool tonemap_wanted(uint32_t mode)
+		{
+			const char* const spec = tonemap_spec();
+			if (!spec)
+				return false;
+			const char* const frame_mode = mode == RT_HIP_FLAG_PREVIEW	  ? nullptr
+										   : adaptive_threshold() >= 0.0f ? "RT_HIP_ADAPTIVE"
+										   : temporal_frames()			  ? "RT_HIP_TEMPORAL"
+										   : progressive_pass_samples()	  ? "RT_HIP_PROGRESSIVE"
+										   : upscale_factor()			  ? "RT_HIP_UPSCALE"
+																		  : nullptr;
+			if (mode == RT_HIP_FLAG_PREVIEW)
+				std::cerr << "error: hip_ray_tracer: RT_HIP_TONEMAP is ignored: the preview has no float frame to map\n";
+			else if (frame_mode)
+				std::cerr << "error: hip_ray_tracer: RT_HIP_TONEMAP is ignored: " << frame_mode << " is set, and only one-shot frames are tone-mapped\n";
+			else if (!rt_hip_render_tonemapped || !rt_hip_tonemap_from_spec)
+				std::cerr << "error: hip_ray_tracer: RT_HIP_TONEMAP is ignored: this librt_hip.so has no rt_hip_render_tonemapped\n";
+			else if (rt_hip_tonemap_from_spec(spec, &tonemap_params) != RT_HIP_OK)
+				std::cerr << "error: hip_ray_tracer: " << rt_hip_last_error() << ": RT_HIP_TONEMAP is ignored\n";
+			else
+				return true;
+			return false;
+		}
+
 		// one frame of `s` into `pixels` (width x height, never null); `names`: the scene's n_materials material names
 		void render(uint32_t mode, const rt_hip_scene& s, const std::string* names, size_t n_names, uint32_t* pixels, uint32_t width, uint32_t height) noexcept
 		{
@@ -366,6 +419,12 @@ namespace rt_hip_plugin
 			// frame keeps that behaviour; RT_HIP_SEED pins it for reproducible output.
 			const char* fixed = std::getenv("RT_HIP_SEED");
 			const uint64_t seed = fixed ? std::strtoull(fixed, nullptr, 0) : ++frame_number;
+
+			if (!tonemap_decided)
+			{
+				tonemap_decided = true;
+				tonemap_on = tonemap_wanted(mode);
+			}
 
 			uint32_t lights = RT_HIP_FLAG_NONE; // (RT_HIP_LIGHTS: RT_HIP_FLAG_EMISSION, the table in place)
 			if (!light_flags(mode, names, n_names, lights))
@@ -447,6 +506,20 @@ namespace rt_hip_plugin
 					std::cerr << "error: hip_ray_tracer: " << rt_hip_last_error() << ": RT_HIP_UPSCALE is ignored for this renderer\n";
 					upscale_unsupported = true;
 				}
+			if (tonemap_on) // (one-shot frames of the two tracers only: tonemap_wanted; no frame flag: the pixels come from a device buffer)
+			{
+				const rt_hip_status st = rt_hip_render_tonemapped(ctx, &s, pixels, width, height, seed, accel_flags() | lights | mode, &tonemap_params, nullptr, nullptr, nullptr);
+				if (st == RT_HIP_OK)
+					return;
+				if (st != RT_HIP_UNSUPPORTED)
+				{
+					std::cerr << "error: hip_ray_tracer: " << rt_hip_last_error() << "\n";
+					return;
+				}
+				// a multi-GPU or frame-group renderer: said once, and from here on every frame is rt_hip_render's (below)
+				std::cerr << "error: hip_ray_tracer: " << rt_hip_last_error() << ": RT_HIP_TONEMAP is ignored for this renderer\n";
+				tonemap_on = false;
+			}
 			if (rt_hip_render(ctx, &s, pixels, width, height, seed, frame_flags() | accel_flags() | lights | mode, nullptr, nullptr) != RT_HIP_OK)
 				std::cerr << "error: hip_ray_tracer: " << rt_hip_last_error() << "\n";
 		}

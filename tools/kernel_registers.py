@@ -14,8 +14,8 @@ it never touches — that costs nothing; spills in the loop are what to look for
 Given a listing of rt_amd/csrc/bvh_build.hip instead, it lists the device builder's kernels (build_*, sort_*) in a second table:
 they are expected to reserve no scratch at all.  A listing of rt_amd/csrc/denoise.hip lists the denoiser's kernels (guide_frame,
 atrous_pass<1 | 2 | 0>, finish_frame, mean_frame) in the same second table, under the same expectation; a listing of
-rt_amd/csrc/temporal.hip lists reproject_frame there, one of rt_amd/csrc/sky_band.hip the sky band's kernel, and one of rt_amd/csrc/upsample.hip the guided
-upsampler's upsample_frame."""
+rt_amd/csrc/temporal.hip lists reproject_frame there, one of rt_amd/csrc/sky_band.hip the sky band's kernel, one of rt_amd/csrc/upsample.hip the guided
+upsampler's upsample_frame, and one of rt_amd/csrc/tonemap.hip tone mapping's luminance_histogram, exposure_from_histogram and tonemap_frame."""
 import re
 import sys
 
@@ -36,7 +36,7 @@ for line in open(path):
         name = (m.group(1),)
         cur = {}
         continue
-    m = re.match(r"^_ZN6rt_hip12_GLOBAL__N_1\d+(guide_frame|finish_frame|mean_frame|atrous_pass|reproject_frame|sky_band_rows_kernel|upsample_frame)(?:ILi(\d)E)?E\w*:", line)
+    m = re.match(r"^_ZN6rt_hip12_GLOBAL__N_1\d+(guide_frame|finish_frame|mean_frame|atrous_pass|reproject_frame|sky_band_rows_kernel|upsample_frame|luminance_histogram|exposure_from_histogram|tonemap_frame)(?:ILi(\d)E)?E\w*:", line)
     if m:
         name = (m.group(1) + (f"<{m.group(2)}>" if m.group(2) else ""),)
         cur = {}
