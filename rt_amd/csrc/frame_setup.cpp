@@ -88,7 +88,10 @@ namespace rt_hip
 		check.bvh_device_build = (flags & RT_HIP_FLAG_BVH_DEVICE_BUILD) != 0u;
 		flags &= ~static_cast<uint32_t>(RT_HIP_FLAG_BVH_DEVICE_BUILD); // (the builder's business: the launch is RT_HIP_FLAG_BVH's either way)
 		check.flags = flags;
-		if (height > 65535u * 2u) // the launch grid's y dimension counts pixel tiles at least two rows high
+		// The launch grid's y dimension counts rows of pixel tiles and holds 65535 of them.  A tile may be ONE row high (a page-locked frame's,
+		// from 64 samples a pixel: choose_queue), but it holds at least four pixels, and where one-row tiles would be more than 65535 rows of
+		// them the plan takes the next taller shape (launch_plan.cpp, cut_tiles): two rows a tile is what every frame up to here can have.
+		if (height > 65535u * 2u)
 			return refuse(check, RT_HIP_INVALID_ARGUMENT, "rt_hip_render_device: frame height %u exceeds the supported 131070 rows", height);
 		const rt_hip_partition whole = { 0, 1, RT_HIP_DEFAULT_STRIPE_ROWS };
 		const rt_hip_partition p = part ? *part : whole;

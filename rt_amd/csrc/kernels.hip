@@ -1374,19 +1374,22 @@ namespace rt_hip
 																		  uint32_t* __restrict__ frame)
 		{
 			const uint32_t x = blockIdx.x * block_threads + threadIdx.x;
-			const uint32_t y = blockIdx.y;
-			if (x >= width || y >= height)
+			if (x >= width)
 				return;
-			const uint32_t stripe = y / stripe_rows;
-			const uint32_t rank = stripe % world;
-			if (rank < first_rank) // (block-uniform: a block lies within one row)
-				return;
-			const uint32_t local_row = (stripe / world) * stripe_rows + (y % stripe_rows);
-			const uint32_t word = gathered[(static_cast<size_t>(rank) * padded_local_rows + local_row) * width + x];
-			if (TO_HOST)
-				__hip_atomic_store(&frame[static_cast<size_t>(y) * width + x], word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-			else
-				frame[static_cast<size_t>(y) * width + x] = word;
+			// a workgroup takes rows blockIdx.y, blockIdx.y + gridDim.y, ...: one each up to assemble_max_grid_y rows (launch_assemble)
+			for (uint32_t y = blockIdx.y; y < height; y += gridDim.y)
+			{
+				const uint32_t stripe = y / stripe_rows;
+				const uint32_t rank = stripe % world;
+				if (rank < first_rank) // (block-uniform: a block lies within one row at a time)
+					continue;
+				const uint32_t local_row = (stripe / world) * stripe_rows + (y % stripe_rows);
+				const uint32_t word = gathered[(static_cast<size_t>(rank) * padded_local_rows + local_row) * width + x];
+				if (TO_HOST)
+					__hip_atomic_store(&frame[static_cast<size_t>(y) * width + x], word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+				else
+					frame[static_cast<size_t>(y) * width + x] = word;
+			}
 		}
 
 #endif // !RT_HIP_FAST_BUILD
@@ -1595,7 +1598,10 @@ namespace rt_hip
 						 bool frame_is_host_memory,
 						 hipStream_t stream)
 	{
-		const dim3 grid((width + block_threads - 1) / block_threads, height);
+		// one workgroup per 256 words of a row; in y one per row while the grid holds them, beyond that a workgroup strides over rows
+		// (the multi-GPU frame's height is the render's, up to 131070 rows, and rt_hip_assemble_device puts no cap on it)
+		constexpr uint32_t assemble_max_grid_y = 65535u;
+		const dim3 grid((width + block_threads - 1) / block_threads, std::min(height, assemble_max_grid_y));
 		if (frame_is_host_memory)
 			hipLaunchKernelGGL(assemble_stripes<true>, grid, dim3(block_threads), 0, stream, width, height, world, stripe_rows, padded_local_rows, first_rank, d_gathered, d_frame);
 		else

@@ -38,6 +38,28 @@ namespace rt_hip
 		return RT_HIP_KERNEL_STREAMED;
 	}
 
+	namespace
+	{
+		// The frame as tiles of queue.pixels_log2 pixels, queue.tile_w_log2 of them in a row.  tiles_y is the launch grid's y dimension
+		// (plan_launch), which holds at most max_grid_y workgroups: where the shape asked for would give more tile rows — a page-locked
+		// frame's one-row tiles in a frame of more than 65535 rows — the next taller shape of the same pixel count is taken.  A tile holds
+		// at least four pixels and a frame at most 2 x max_grid_y rows (check_render_request), so one step suffices; the loop says the rule,
+		// not the count.  (The rolling kernels' 1 x 1 "tiles" are not launched as a grid: nothing to lower, grid_y is 1.)
+		void cut_tiles(queue_params& q, uint32_t width, uint32_t local_rows)
+		{
+			constexpr uint32_t max_grid_y = 65535u;
+			for (;;)
+			{
+				const uint32_t tile_w = 1u << q.tile_w_log2, tile_h = (1u << q.pixels_log2) >> q.tile_w_log2;
+				q.tiles_x = (width + tile_w - 1u) / tile_w;
+				q.tiles_y = (local_rows + tile_h - 1u) / tile_h;
+				if (q.tiles_y <= max_grid_y || q.tile_w_log2 == 0u)
+					return;
+				q.tile_w_log2--;
+			}
+		}
+	}
+
 	queue_params choose_queue(uint32_t samples_per_pixel, uint32_t width, uint32_t local_rows, bool big_scene, bool host_frame, int half_chunks, uint32_t primitives, bool sparse_launch)
 	{
 		queue_params q{};
@@ -173,9 +195,7 @@ namespace rt_hip
 				q.tile_w_log2 = std::min<uint32_t>(static_cast<uint32_t>(std::atoi(knob)), pixels_log2);
 		}
 #endif
-		const uint32_t tile_w = 1u << q.tile_w_log2, tile_h = (1u << pixels_log2) >> q.tile_w_log2;
-		q.tiles_x = (width + tile_w - 1u) / tile_w;
-		q.tiles_y = (local_rows + tile_h - 1u) / tile_h;
+		cut_tiles(q, width, local_rows);
 		return q;
 	}
 
@@ -231,9 +251,7 @@ namespace rt_hip
 			queue.tile_w_log2 = std::min(queue.tile_w_log2, 4u); // (64 pixels: 8 x 8, or 16 x 4 for a page-locked frame)
 			if (!request.host_frame)
 				queue.tile_w_log2 = 3u;
-			const uint32_t tile_w = 1u << queue.tile_w_log2, tile_h = (1u << queue.pixels_log2) >> queue.tile_w_log2;
-			queue.tiles_x = (request.width + tile_w - 1u) / tile_w;
-			queue.tiles_y = (request.local_rows + tile_h - 1u) / tile_h;
+			cut_tiles(queue, request.width, request.local_rows);
 		}
 		plan.queue = queue;
 		plan.build.pass = pass;

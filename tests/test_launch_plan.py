@@ -116,39 +116,44 @@ def test_plans_are_the_recorded_ones(dump):
         pytest.fail(f"{sum(a != b for a, b in zip(g, w)) + abs(len(g) - len(w))} of {len(w)} rows differ; first at line {first + 1}:\n got  {g[first] if first < len(g) else None}\n want {w[first] if first < len(w) else None}")
 
 
+def row_invariants(r):
+    """What the kernels rely on in one row of the dump (tests/test_plan_frame_extremes.py holds its frames to the same)."""
+    where = str(r)
+    rolling = r["variant"] in (KERNEL["tiled"], KERNEL["streamed"])
+    assert rolling == bool(r["big_scene"]) == (r["scan"] in (-1, -2, -3)) == (r["persistent_slot"] >= 0), where
+    # tiles cover the rows, and are no wider than they are large
+    tile_w_log2, tile_h_log2 = r["tile_w_log2"], r["pixels_log2"] - r["tile_w_log2"]
+    assert r["tile_w_log2"] <= r["pixels_log2"], where
+    assert (r["tiles_x"] << tile_w_log2) >= r["width"] and (r["tiles_y"] << tile_h_log2) >= r["local_rows"], where
+    if rolling:
+        assert 1 <= r["lane_cap"] <= 64, where
+        assert 1 <= r["block_items"] <= max(r["lane_cap"], 8), where
+        assert r["item_samples"] & (r["item_samples"] - 1) == 0 and 1 <= r["item_samples"] <= r["sample_chunk"], where
+    else:  # (fields of the rolling kernels: not set, not read)
+        assert r["lane_cap"] == r["block_items"] == r["item_samples"] == r["sparse_rays"] == 0, where
+    if r["sm_table"] or r["flags"] & capi.RT_HIP_FLAG_FORCE_WHOLE_CHUNKS:
+        assert r["halves"] == 0, where
+    assert r["sub_chunk_items"] == r["halves"], where
+    one_whole_chunk = r["chunks"] <= 1 and not r["halves"]
+    assert (r["item_sums_bytes"] == 0) == (not rolling or one_whole_chunk), where
+    assert (r["pixel_done_bytes"] == 0) == (r["item_sums_bytes"] == 0), where
+    assert r["lds_bytes"] == r["table_bytes"] + r["slot_bytes"], where
+    if not rolling:
+        assert r["slot_bytes"] == r["four_tile_slot_bytes"] and r["lds_bytes"] == r["table_bytes"] + r["four_tile_slot_bytes"], where
+        assert (r["grid_x"], r["grid_y"]) == ((r["tiles_x"] + 3) // 4, r["tiles_y"]), where
+    else:
+        assert r["slot_bytes"] == 0 and r["grid_y"] == 1 and 1 <= r["grid_x"] <= r["total_items"], where
+        assert 0 <= r["persistent_slot"] < 18 and r["per_cu_cap"] == (6 if r["scan"] == -3 else 5), where
+    if r["scan"] > 0:  # the scalar-register kernels: the builds that exist
+        assert r["variant"] == KERNEL["small"] and (r["scan"], r["planes"]) == (r["n_spheres"], r["n_planes"]) and r["scan"] + r["planes"] <= 8 and r["planes"] <= 3, where
+
+
 def test_invariants_the_kernels_rely_on(dump):
     rows = parse(dump(grid()))
     assert len(rows) == len(grid())
     seen = set()
     for r in rows:
-        where = str(r)
-        rolling = r["variant"] in (KERNEL["tiled"], KERNEL["streamed"])
-        assert rolling == bool(r["big_scene"]) == (r["scan"] in (-1, -2, -3)) == (r["persistent_slot"] >= 0), where
-        # tiles cover the rows, and are no wider than they are large
-        tile_w_log2, tile_h_log2 = r["tile_w_log2"], r["pixels_log2"] - r["tile_w_log2"]
-        assert r["tile_w_log2"] <= r["pixels_log2"], where
-        assert (r["tiles_x"] << tile_w_log2) >= r["width"] and (r["tiles_y"] << tile_h_log2) >= r["local_rows"], where
-        if rolling:
-            assert 1 <= r["lane_cap"] <= 64, where
-            assert 1 <= r["block_items"] <= max(r["lane_cap"], 8), where
-            assert r["item_samples"] & (r["item_samples"] - 1) == 0 and 1 <= r["item_samples"] <= r["sample_chunk"], where
-        else:  # (fields of the rolling kernels: not set, not read)
-            assert r["lane_cap"] == r["block_items"] == r["item_samples"] == r["sparse_rays"] == 0, where
-        if r["sm_table"] or r["flags"] & capi.RT_HIP_FLAG_FORCE_WHOLE_CHUNKS:
-            assert r["halves"] == 0, where
-        assert r["sub_chunk_items"] == r["halves"], where
-        one_whole_chunk = r["chunks"] <= 1 and not r["halves"]
-        assert (r["item_sums_bytes"] == 0) == (not rolling or one_whole_chunk), where
-        assert (r["pixel_done_bytes"] == 0) == (r["item_sums_bytes"] == 0), where
-        assert r["lds_bytes"] == r["table_bytes"] + r["slot_bytes"], where
-        if not rolling:
-            assert r["slot_bytes"] == r["four_tile_slot_bytes"] and r["lds_bytes"] == r["table_bytes"] + r["four_tile_slot_bytes"], where
-            assert (r["grid_x"], r["grid_y"]) == ((r["tiles_x"] + 3) // 4, r["tiles_y"]), where
-        else:
-            assert r["slot_bytes"] == 0 and r["grid_y"] == 1 and 1 <= r["grid_x"] <= r["total_items"], where
-            assert 0 <= r["persistent_slot"] < 18 and r["per_cu_cap"] == (6 if r["scan"] == -3 else 5), where
-        if r["scan"] > 0:  # the scalar-register kernels: the builds that exist
-            assert r["variant"] == KERNEL["small"] and (r["scan"], r["planes"]) == (r["n_spheres"], r["n_planes"]) and r["scan"] + r["planes"] <= 8 and r["planes"] <= 3, where
+        row_invariants(r)
         seen.add((r["variant"], r["scan"], r["planes"] if r["scan"] <= 0 else 0, r["general_camera"], r["halves"]))
     # the grid reaches every kernel, every scan mode and both item sizes
     assert {v for v, *_ in seen} == {KERNEL["resident"], KERNEL["tiled"], KERNEL["small"], KERNEL["streamed"], KERNEL["bvh"]}
