@@ -16,18 +16,18 @@ HIPFLAGS += -fvisibility=hidden
 # register pairs — moves, and a higher register count.  Measured on the contract-v4 kernels: headline 2.28 -> 2.14 ms,
 # basic + plane 2.74 -> 2.62, tilted camera 2.80 -> 2.62 (profiles/r05/codegen_ab.txt).
 HIPFLAGS += -fno-slp-vectorize
-API_UNITS := context scene frame render frame_call passes multi group denoise temporal adaptive upsample tonemap
-HIP_HDR  := rt_amd/csrc/kernels.hpp rt_amd/csrc/launch_plan.hpp rt_amd/csrc/progressive.hpp rt_amd/csrc/denoise.hpp rt_amd/csrc/denoise_rules.hpp rt_amd/csrc/temporal.hpp rt_amd/csrc/reproject_rules.hpp rt_amd/csrc/adaptive.hpp rt_amd/csrc/adaptive_rules.hpp rt_amd/csrc/upsample.hpp rt_amd/csrc/upsample_rules.hpp rt_amd/csrc/tonemap.hpp rt_amd/csrc/tonemap_rules.hpp rt_amd/csrc/lights.hpp rt_amd/csrc/sky_band.hpp rt_amd/csrc/centre_ray.hpp rt_amd/csrc/frame_setup.hpp rt_amd/csrc/contract.hpp rt_amd/csrc/scan.hpp rt_amd/csrc/bvh_scan.hpp rt_amd/csrc/bvh.hpp rt_amd/csrc/box_bvh.hpp rt_amd/csrc/box_bvh_scan.hpp rt_amd/csrc/scan_streamed.hpp rt_amd/csrc/handover.hpp rt_amd/csrc/pixel_output.hpp rt_amd/csrc/lane_state.hpp rt_amd/csrc/queue_build.hpp rt_amd/csrc/camera_forms.hpp rt_amd/csrc/bvh_build.hpp rt_amd/csrc/bvh_build_device.hpp rt_amd/csrc/frame_group.hpp rt_amd/csrc/delivery.hpp rt_amd/csrc/internal.hpp include/rt_hip.h
+API_UNITS := context scene frame render frame_call passes multi group denoise temporal adaptive upsample tonemap bloom
+HIP_HDR  := rt_amd/csrc/kernels.hpp rt_amd/csrc/launch_plan.hpp rt_amd/csrc/progressive.hpp rt_amd/csrc/denoise.hpp rt_amd/csrc/denoise_rules.hpp rt_amd/csrc/temporal.hpp rt_amd/csrc/reproject_rules.hpp rt_amd/csrc/adaptive.hpp rt_amd/csrc/adaptive_rules.hpp rt_amd/csrc/upsample.hpp rt_amd/csrc/upsample_rules.hpp rt_amd/csrc/tonemap.hpp rt_amd/csrc/tonemap_rules.hpp rt_amd/csrc/bloom.hpp rt_amd/csrc/bloom_rules.hpp rt_amd/csrc/lights.hpp rt_amd/csrc/sky_band.hpp rt_amd/csrc/centre_ray.hpp rt_amd/csrc/frame_setup.hpp rt_amd/csrc/contract.hpp rt_amd/csrc/scan.hpp rt_amd/csrc/bvh_scan.hpp rt_amd/csrc/bvh.hpp rt_amd/csrc/box_bvh.hpp rt_amd/csrc/box_bvh_scan.hpp rt_amd/csrc/scan_streamed.hpp rt_amd/csrc/handover.hpp rt_amd/csrc/pixel_output.hpp rt_amd/csrc/lane_state.hpp rt_amd/csrc/queue_build.hpp rt_amd/csrc/camera_forms.hpp rt_amd/csrc/bvh_build.hpp rt_amd/csrc/bvh_build_device.hpp rt_amd/csrc/frame_group.hpp rt_amd/csrc/delivery.hpp rt_amd/csrc/internal.hpp include/rt_hip.h
 HOST_SRC := rt_amd/host/host_capi.cpp rt_amd/host/scene.cpp rt_amd/host/toml_subset.cpp
 HOST_HDR := $(wildcard rt_amd/host/*.hpp) rt_amd/host/host_capi.h rt_amd/host/named_colours.inc include/rt_hip.h
 
-all: $(LIBDIR)/librt_hip.so $(LIBDIR)/librt_hip_kat.so $(LIBDIR)/librt_host.so rt_amd/bin/rt_headless tests/native/lbvh_reference tests/native/libbox_reference.so tests/native/libdenoise_reference.so tests/native/libreproject_reference.so tests/native/libadaptive_reference.so tests/native/liblight_reference.so tests/native/libdirect_reference.so tests/native/libupsample_reference.so tests/native/libtonemap_reference.so oracle
+all: $(LIBDIR)/librt_hip.so $(LIBDIR)/librt_hip_kat.so $(LIBDIR)/librt_host.so rt_amd/bin/rt_headless tests/native/lbvh_reference tests/native/libbox_reference.so tests/native/libdenoise_reference.so tests/native/libreproject_reference.so tests/native/libadaptive_reference.so tests/native/liblight_reference.so tests/native/libdirect_reference.so tests/native/libupsample_reference.so tests/native/libtonemap_reference.so tests/native/libbloom_reference.so oracle
 
 # kernels.hip is compiled twice: the parity contract (contraction off), and RT_HIP_FLAG_FAST's arithmetic
 # (-DRT_HIP_FAST_BUILD -ffp-contract=fast: only launch_render_fast comes out of that one)
 FASTFLAGS := $(filter-out -ffp-contract=off,$(HIPFLAGS)) -ffp-contract=fast -DRT_HIP_FAST_BUILD
 OBJDIR   := build/obj$(NAME)
-HIP_OBJS := $(OBJDIR)/kernels.o $(OBJDIR)/kernels_fast.o $(API_UNITS:%=$(OBJDIR)/%.o) $(OBJDIR)/delivery.o $(OBJDIR)/bvh.o $(OBJDIR)/box_bvh.o $(OBJDIR)/bvh_build.o $(OBJDIR)/launch_plan.o $(OBJDIR)/frame_setup.o $(OBJDIR)/progressive.o $(OBJDIR)/denoise_params.o $(OBJDIR)/temporal_params.o $(OBJDIR)/adaptive_params.o $(OBJDIR)/upsample_params.o $(OBJDIR)/tonemap_params.o $(OBJDIR)/lights.o $(OBJDIR)/sky_band.o $(OBJDIR)/sky_band_rule.o
+HIP_OBJS := $(OBJDIR)/kernels.o $(OBJDIR)/kernels_fast.o $(API_UNITS:%=$(OBJDIR)/%.o) $(OBJDIR)/delivery.o $(OBJDIR)/bvh.o $(OBJDIR)/box_bvh.o $(OBJDIR)/bvh_build.o $(OBJDIR)/launch_plan.o $(OBJDIR)/frame_setup.o $(OBJDIR)/progressive.o $(OBJDIR)/denoise_params.o $(OBJDIR)/temporal_params.o $(OBJDIR)/adaptive_params.o $(OBJDIR)/upsample_params.o $(OBJDIR)/tonemap_params.o $(OBJDIR)/bloom_params.o $(OBJDIR)/lights.o $(OBJDIR)/sky_band.o $(OBJDIR)/sky_band_rule.o
 
 $(OBJDIR)/kernels.o: rt_amd/csrc/kernels.hip $(HIP_HDR)
 	@mkdir -p $(OBJDIR)
@@ -91,6 +91,13 @@ $(OBJDIR)/upsample_params.o: rt_amd/csrc/upsample.cpp rt_amd/csrc/upsample.hpp i
 $(OBJDIR)/tonemap_params.o: rt_amd/csrc/tonemap.cpp rt_amd/csrc/tonemap.hpp include/rt_hip.h
 	@mkdir -p $(OBJDIR)
 	$(CXX) -std=c++17 -O2 -fPIC -fvisibility=hidden -Wall -Wextra $(DEFS) -c $< -o $@
+
+# bloom's host-only rules (parameters, the level plan, the key=value parser): plain C++17 too, and the same source is built into
+# tests/native/libbloom_reference.so and the program of `make sanitize-bloom` on the CPU.  Contraction off, spelled out: norm and gain
+# are defined by their order of operations
+$(OBJDIR)/bloom_params.o: rt_amd/csrc/bloom.cpp rt_amd/csrc/bloom.hpp rt_amd/csrc/bloom_rules.hpp include/rt_hip.h
+	@mkdir -p $(OBJDIR)
+	$(CXX) -std=c++17 -O2 -fPIC -fvisibility=hidden -ffp-contract=off -Wall -Wextra $(DEFS) -c $< -o $@
 
 # emissive materials' host-only rules (the emission table's checks, rt_hip_lights_from_spec): plain C++17 too, and the same source is
 # built into tests/native/light_plan_dump and the program of `make sanitize-lights` on the CPU
@@ -270,6 +277,21 @@ sanitize-tonemap: tests/native/tonemap_sanitize.cpp $(TONEMAP_REF_SRC)
 	$(CXX) -O1 -g -std=c++17 -ffp-contract=off -fno-fast-math -fno-math-errno -mfma -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer $< tests/native/tonemap_reference.cpp rt_amd/csrc/tonemap.cpp -o build/tonemap_sanitize -lpthread
 	build/tonemap_sanitize
 
+# the CPU restatement of bloom: the serial loops over rt_amd/csrc/bloom_rules.hpp — the kernels' own text — and
+# bloom.cpp as it is; g++ alone, the oracle's strict flags; tests/bloom_reference.py binds it
+BLOOM_REF_SRC := tests/native/bloom_reference.cpp rt_amd/csrc/bloom_rules.hpp rt_amd/csrc/bloom.cpp rt_amd/csrc/bloom.hpp include/rt_hip.h
+tests/native/libbloom_reference.so: $(BLOOM_REF_SRC)
+	$(CXX) -O2 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -fno-math-errno -mfma -Wall -Wextra -shared $< rt_amd/csrc/bloom.cpp -o $@
+
+# `make sanitize-bloom`: the host-only unit and the serial restatement behind a main() of their own (ragged sizes from 1 x 1, frames of
+# NaN, infinities, negatives and denormals, every level count, in place, every parameter refusal, the parser on well-formed, malformed,
+# truncated and oversized texts) under AddressSanitizer and UndefinedBehaviorSanitizer.  CPU only, nothing is loaded into python; the
+# binary goes to build/ and is run at once
+sanitize-bloom: tests/native/bloom_sanitize.cpp $(BLOOM_REF_SRC)
+	@mkdir -p build
+	$(CXX) -O1 -g -std=c++17 -ffp-contract=off -fno-fast-math -fno-math-errno -mfma -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer $< tests/native/bloom_reference.cpp rt_amd/csrc/bloom.cpp -o build/bloom_sanitize
+	build/bloom_sanitize
+
 oracle:
 	$(MAKE) -C oracle
 
@@ -285,7 +307,7 @@ oracle/_ref/soagen_columns: tests/native/soagen_columns.cpp $(LIBDIR)/librt_hip.
 endif
 
 clean:
-	rm -f $(LIBDIR)/*.so rt_amd/bin/rt_headless tests/native/lbvh_reference tests/native/libbox_reference.so tests/native/libdenoise_reference.so tests/native/libreproject_reference.so tests/native/libadaptive_reference.so tests/native/liblight_reference.so tests/native/libdirect_reference.so tests/native/libupsample_reference.so tests/native/libtonemap_reference.so
+	rm -f $(LIBDIR)/*.so rt_amd/bin/rt_headless tests/native/lbvh_reference tests/native/libbox_reference.so tests/native/libdenoise_reference.so tests/native/libreproject_reference.so tests/native/libadaptive_reference.so tests/native/liblight_reference.so tests/native/libdirect_reference.so tests/native/libupsample_reference.so tests/native/libtonemap_reference.so tests/native/libbloom_reference.so
 	$(MAKE) -C oracle clean
 
-.PHONY: all oracle clean variant sanitize-temporal sanitize-box-bvh sanitize-adaptive sanitize-lights sanitize-sky-band sanitize-upsample sanitize-tonemap sanitize-plugin
+.PHONY: all oracle clean variant sanitize-temporal sanitize-box-bvh sanitize-adaptive sanitize-lights sanitize-sky-band sanitize-upsample sanitize-tonemap sanitize-bloom sanitize-plugin

@@ -1116,6 +1116,96 @@ RT_HIP_API rt_hip_status rt_hip_render_tonemapped(rt_hip_ctx* ctx,
 									rt_hip_stats* stats,
 									rt_hip_tonemap_info* out_info);		 /* nullable */
 
+/* ---- bloom for HDR frames: a device pyramid in front of the tone curve -------------------------------------- */
+/*
+ * Tone mapping is a global operator: a lamp comes out as a hard-edged disc, and a lamp of 4 looks like a lamp of 400.  What tells a
+ * viewer that something is brighter than the display is the glow around it.  These entry points add that glow to a float frame, on
+ * the device, BEFORE the exposure and the curve: what of every pixel lies above a threshold (through a quadratic knee) is averaged
+ * 2 x 2 into a half-size level, filtered down a pyramid of up to 8 levels with a separable 5-tap binomial, summed back up with a
+ * tent, each coarser level weighted by `scatter`, and added to the frame times intensity / (1 + scatter + scatter^2 + ...).
+ * A contract of its own: + - x, correctly rounded division and compare-and-select in one stated order, no log, exp or pow anywhere,
+ * so that the device's result equals a serial CPU restatement bit for bit — it is NOT the reference's arithmetic (the reference has
+ * no bloom).  No speed is promised.  Additions to ABI 6 (RT_HIP_ABI_VERSION stays 6): a caller that may meet an older library
+ * looks them up with dlsym.
+ */
+typedef struct rt_hip_bloom_params
+{
+	float threshold; /* 0 .. 2^20: the largest channel above which a pixel glows; default 1 */
+	float knee;		 /* 0, or 2^-20 .. threshold: the half-width of the quadratic knee below and above the threshold; default 0.5 */
+	float intensity; /* 0 .. 2^10: how much of the glow layer is added (the layer is normalised by the levels' weights); default 0.1 */
+	float scatter;	 /* 0 .. 1: the weight of every coarser level relative to the one before: 0 = a tight glow, 1 = a wide one; default 0.7 */
+	uint32_t levels; /* 1 .. 8: the pyramid's levels, fewer where the frame reaches 1 x 1 before; default 6 */
+} rt_hip_bloom_params;
+
+typedef struct rt_hip_bloom_info
+{
+	uint32_t levels;		/* the levels a frame of this size gets: min(params->levels, the count at which a level first is 1 x 1) */
+	uint32_t last_width;	/* the coarsest level's size */
+	uint32_t last_height;
+	uint64_t scratch_bytes; /* what the pyramid takes of device memory: 12 bytes a texel, all levels */
+} rt_hip_bloom_info;
+
+/* the defaults a NULL `params` stands for; pure host code */
+RT_HIP_API rt_hip_status rt_hip_bloom_default_params(rt_hip_bloom_params* out_params);
+
+/*
+ * Parameters from a text: `default`, or items KEY=VALUE separated by ',' with the keys intensity, threshold, knee, scatter and
+ * levels, each at most once; a value is a plain decimal number (levels: a whole one).  Everything else keeps its default.
+ * Host-only; touches no device.  RT_HIP_INVALID_ARGUMENT, with a message that quotes the text, for anything else and for values
+ * the parameter check refuses (that message names the field too); out_params is untouched then.
+ */
+RT_HIP_API rt_hip_status rt_hip_bloom_from_spec(const char* spec, rt_hip_bloom_params* out_params);
+
+/*
+ * The pyramid a width x height frame (1 .. 32768 a side) gets under `params` (NULL = defaults).  Level 0 is ceil(width / 2) x
+ * ceil(height / 2), every next level halves the one before with ceil.  Host-only; touches no device.
+ */
+RT_HIP_API rt_hip_status rt_hip_bloom_plan(uint32_t width, uint32_t height, const rt_hip_bloom_params* params, rt_hip_bloom_info* out_info);
+
+/*
+ * Bloom as a pure image operation on DEVICE buffers of a whole width x height frame: d_rgb_in (3 * width * height floats, a frame's
+ * float mean in linear light) gives d_rgb_out (3 * width * height floats: d_rgb_in + gain x layer, per channel; optional) and
+ * d_layer_out (3 * width * height floats: the glow layer alone, before the gain; optional) — not both NULL.  d_rgb_out == d_rgb_in
+ * exactly is allowed (in place); every other overlap between the buffers is refused.  NaN, negative and infinite channels enter the
+ * pyramid as 0, 0 and 2^20: a bad pixel does not spread, and d_rgb_out keeps it as it was (NaN + anything is that NaN).
+ * 2 x levels launches on `stream` (prefilter, levels - 1 down, levels - 1 up, composite: at most 16) and no readback:
+ * asynchronous.  The pyramid's scratch belongs to the context and grows on demand: the bloom calls of one context must be ordered
+ * on ONE stream (or by the caller), and a call that grows the scratch frees the block the call before used — with calls in flight
+ * on another stream that is the caller's to order.  It reads no scene.  On a multi-GPU, rank or frame-group context the root
+ * member answers.
+ */
+RT_HIP_API rt_hip_status rt_hip_bloom_device(rt_hip_ctx* ctx,
+									uint32_t width,
+									uint32_t height,
+									const float* d_rgb_in,
+									const rt_hip_bloom_params* params, /* NULL = defaults */
+									float* d_rgb_out,				   /* nullable; may be d_rgb_in */
+									float* d_layer_out,				   /* nullable, not both NULL */
+									void* stream);
+
+/*
+ * Drop-in level: one call is one bloomed, tone-mapped frame.  As rt_hip_render_tonemapped, with the bloom launches between the
+ * traced frame and the meter: the one-shot frame is traced into a device float mean, bloomed in place, metered, exposed and mapped,
+ * and copied into the caller's plain HOST memory (pixels_rgba8888 and, optionally, rgb_f32: the MAPPED frame in linear light).  The
+ * meter sees the bloomed frame.  The context keeps a state record for these calls, separate from rt_hip_render_tonemapped's, and
+ * zeroes it when the frame's size changes.
+ *   stats     optional: the traced frame's; render_ms runs through the last launch.
+ * Flags, refusals (RT_HIP_FLAG_PREVIEW and RT_HIP_FLAG_PERSISTENT_FRAME by name, unknown bits) and the contexts taken (those from
+ * rt_hip_create only) are rt_hip_render_tonemapped's.
+ */
+RT_HIP_API rt_hip_status rt_hip_render_bloomed(rt_hip_ctx* ctx,
+									const rt_hip_scene* scene,
+									uint32_t* pixels_rgba8888,
+									uint32_t width,
+									uint32_t height,
+									uint64_t seed,
+									uint32_t flags,
+									const rt_hip_bloom_params* bloom_params,	 /* NULL = defaults */
+									const rt_hip_tonemap_params* tonemap_params, /* NULL = defaults */
+									float* rgb_f32,								 /* nullable */
+									rt_hip_stats* stats,
+									rt_hip_tonemap_info* out_tonemap_info);		 /* nullable */
+
 /* Drop the page-lock taken under RT_HIP_FLAG_PERSISTENT_FRAME (see there).  Waits for the context's stream first. */
 RT_HIP_API void rt_hip_forget_frame(rt_hip_ctx* ctx);
 

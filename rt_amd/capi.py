@@ -206,6 +206,24 @@ class RtHipTonemapParams(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class RtHipBloomParams(C.Structure):
+    """``rt_hip_bloom_params`` (include/rt_hip.h): the threshold and its knee, how much glow is added, how wide it spreads, the levels."""
+
+    _fields_ = [("threshold", C.c_float), ("knee", C.c_float), ("intensity", C.c_float), ("scatter", C.c_float), ("levels", C.c_uint32)]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class RtHipBloomInfo(C.Structure):
+    """``rt_hip_bloom_info`` (include/rt_hip.h): the pyramid a frame of some size gets (rt_hip_bloom_plan)."""
+
+    _fields_ = [("levels", C.c_uint32), ("last_width", C.c_uint32), ("last_height", C.c_uint32), ("scratch_bytes", C.c_uint64)]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class RtHipTonemapInfo(C.Structure):
     """``rt_hip_tonemap_info`` (include/rt_hip.h): the exposure a call of rt_hip_render_tonemapped applied and what its meter saw."""
 
@@ -330,6 +348,15 @@ RT_HIP_SYMBOLS = [
         "rt_hip_render_tonemapped",
         C.c_int,
         [C.c_void_p, C.POINTER(RtHipScene), C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(RtHipTonemapParams), C.c_void_p, C.POINTER(RtHipStats), C.POINTER(RtHipTonemapInfo)],
+    ),
+    ("rt_hip_bloom_default_params", C.c_int, [C.POINTER(RtHipBloomParams)]),
+    ("rt_hip_bloom_from_spec", C.c_int, [C.c_char_p, C.POINTER(RtHipBloomParams)]),
+    ("rt_hip_bloom_plan", C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(RtHipBloomParams), C.POINTER(RtHipBloomInfo)]),
+    ("rt_hip_bloom_device", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(RtHipBloomParams), C.c_void_p, C.c_void_p, C.c_void_p]),
+    (
+        "rt_hip_render_bloomed",
+        C.c_int,
+        [C.c_void_p, C.POINTER(RtHipScene), C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(RtHipBloomParams), C.POINTER(RtHipTonemapParams), C.c_void_p, C.POINTER(RtHipStats), C.POINTER(RtHipTonemapInfo)],
     ),
     ("rt_hip_forget_frame", None, [C.c_void_p]),
     ("rt_hip_live_frame_locks", C.c_uint32, []),

@@ -490,6 +490,7 @@ extern "C" void rt_hip_destroy(rt_hip_ctx* ctx)
 	ctx->adaptive.release();
 	ctx->upscale.release();
 	ctx->tonemap.release();
+	ctx->bloom.release();
 	ctx->counters.release();
 	ctx->frame_rgb.release();
 	ctx->staging_rgb.release();

@@ -21,6 +21,8 @@
 //                 (parameters, sizes: upsample.cpp, host compiler; per-pixel rules: upsample_rules.hpp)
 //   tonemap.hip   tone mapping: luminance_histogram, exposure_from_histogram, tonemap_frame, rt_hip_tonemap_device and the
 //                 drop-in rt_hip_render_tonemapped (parameters, the spec parser: tonemap.cpp, host compiler; per-element rules: tonemap_rules.hpp)
+//   bloom.hip     bloom: bloom_prefilter, bloom_down, bloom_up, bloom_composite, rt_hip_bloom_device and the drop-in
+//                 rt_hip_render_bloomed (parameters, the level plan, the spec parser: bloom.cpp, host compiler; per-element rules: bloom_rules.hpp)
 //   multi.hip     rt_hip_render on several GPUs: stripes, one gather, assemble
 //   group.hip     rt_hip_render as one rank of a frame group (rank processes storing into one shared back buffer)
 //   kernels.hip   the gfx950 kernels (compiled twice: parity contract and RT_HIP_FLAG_FAST arithmetic)
@@ -262,6 +264,28 @@ namespace rt_hip
 		}
 	};
 
+	// what bloom keeps on a context (bloom.hip): everything is grown on demand and freed with the context
+	struct bloom_state
+	{
+		device_buffer pyramid;	   // every level back to back, 12 bytes a texel (rt_hip_bloom_device's too)
+		device_buffer traced;	   // rt_hip_render_bloomed: the traced float mean, bloomed and mapped in place
+		device_buffer packed;	   // ... the packed pixels (the traced frame's own, then the mapped ones)
+		device_buffer record;	   // ... tone mapping's 8-word state record, kept from call to call: NOT rt_hip_render_tonemapped's
+		uint32_t width = 0, height = 0; // ... the frame the record was kept for (0: none)
+		pinned_buffer staging;	   // the results' landing place on the host
+		hipEvent_t end = nullptr;  // behind the last launch (frames that keep stats)
+		void release()
+		{
+			for (device_buffer* b : { &pyramid, &traced, &packed, &record })
+				b->release();
+			staging.release();
+			if (end)
+				(void)hipEventDestroy(end);
+			end = nullptr;
+			width = height = 0;
+		}
+	};
+
 	// what adaptive sampling keeps on a context (adaptive.hip): everything is grown on demand and freed with the context
 	struct adaptive_accumulation
 	{
@@ -431,6 +455,7 @@ struct rt_hip_ctx
 
 	// ---- tone mapping (tonemap.hip) ----
 	rt_hip::tonemap_state tonemap; // the meter's histogram and the scratch of rt_hip_render_tonemapped
+	rt_hip::bloom_state bloom;	   // the pyramid and the scratch of rt_hip_render_bloomed
 
 	rt_hip_ctx() = default;
 	rt_hip_ctx(const rt_hip_ctx&) = delete;
@@ -512,6 +537,12 @@ namespace rt_hip
 	// ctx->device current
 	rt_hip_status launch_guide(rt_hip_ctx* ctx, uint32_t width, uint32_t height, const float* matrix, bool trace_boxes, float* d_guide, hipStream_t stream);
 	rt_hip_status launch_filter(rt_hip_ctx* ctx, uint32_t width, uint32_t height, const float* d_in, const float* d_guide, const rt_hip_denoise_params& params, float* d_out, uint32_t* d_rgba, hipStream_t stream);
+
+	// ---- tonemap.hip (what bloom.hip uses of it) ----
+	// `params`, or the defaults; refused with the field's name behind `who`
+	rt_hip_status resolve_tonemap(const char* who, const rt_hip_tonemap_params* params, rt_hip_tonemap_params& out);
+	// the tone-mapping launches on device buffers (everything checked by the caller; ctx->device current)
+	rt_hip_status launch_tonemap(rt_hip_ctx* ctx, uint32_t width, uint32_t height, const float* d_in, const rt_hip_tonemap_params& p, uint32_t* d_state, float* d_out, uint32_t* d_rgba, hipStream_t stream);
 
 	// ---- multi.hip / group.hip ----
 	rt_hip_status render_multi(rt_hip_ctx* root, const rt_hip_scene* scene, uint32_t* pixels_rgba8888, uint32_t width, uint32_t height, uint64_t seed, uint32_t flags, float* rgb_f32, rt_hip_stats* stats, std::chrono::steady_clock::time_point entered);

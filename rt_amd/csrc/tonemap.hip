@@ -125,6 +125,9 @@ namespace
 			rgba[pixel] = tonemap::finish(o);
 	}
 
+}
+
+	// (the two below are bloom.hip's too: declared in internal.hpp)
 	// `params`, or the defaults; refused with the field's name
 	rt_hip_status resolve_tonemap(const char* who, const rt_hip_tonemap_params* params, rt_hip_tonemap_params& out)
 	{
@@ -161,7 +164,6 @@ namespace
 		RT_HIP_TRY(hipGetLastError());
 		return ok();
 	}
-}
 }
 
 using namespace rt_hip;

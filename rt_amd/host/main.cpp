@@ -42,6 +42,10 @@
 //                           RT_HIP_TONEMAP: rt_hip_render_tonemapped): CURVE is none, reinhard or aces, EXPOSURE auto (metered
 //                           from the frame, the default) or a positive number.  What --light makes bright is the point.  Hip tracers only,
 //                           one-shot frames only: not with --progressive, --temporal, --adaptive or --upscale
+//   --bloom SPEC            every frame gets the glow of what is brighter than the display, on the device, in front of the tone curve (exported to
+//                           the renderer as RT_HIP_BLOOM: rt_hip_render_bloomed): SPEC is default, or KEY=VALUE items separated
+//                           by ',' with the keys intensity, threshold, knee, scatter and levels.  With --tonemap that curve follows; alone the
+//                           finish is none:1, the plain square root.  Refused where --tonemap is
 //   --dolly DX,DY,DZ        the camera moves by that much in world space before every frame after the first (camera::pose)
 //   --shared-frame NAME --rank R --world N   this process is rank R of N rt_headless processes that render ONE frame
 //                together (one per GPU: RT_HIP_DEVICE picks this one's): the back buffer is every process's mapping of the
@@ -50,7 +54,7 @@
 // It renders through renderer_interface::render exactly as window::loop does (src/window.cpp:213-217 via
 // src/main.cpp:315-321): clear to opaque black, then render(scene, pixels, threads).
 #include "renderer.hpp"
-#include "../../include/rt_hip.h" // (rt_hip_adaptive_last_info, rt_hip_live_frame_locks: what --adaptive asks the module itself; rt_hip_tonemap_from_spec)
+#include "../../include/rt_hip.h" // (rt_hip_adaptive_last_info, rt_hip_live_frame_locks: what --adaptive asks the module itself; rt_hip_tonemap_from_spec, rt_hip_bloom_from_spec)
 
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -155,7 +159,7 @@ namespace
 
 int main(int argc, char** argv)
 {
-	std::string scene_path, renderer_name, out_path, shared_name, lights, tonemap;
+	std::string scene_path, renderer_name, out_path, shared_name, lights, tonemap, bloom;
 	bool direct_light = false;
 	unsigned width = 800, height = 600, spp = 0, bounces = 0, frames = 1, rank = 0, world = 1, progressive = 0;
 	bool frames_given = false;
@@ -284,6 +288,17 @@ int main(int argc, char** argv)
 			}
 			::setenv("RT_HIP_TONEMAP", tonemap.c_str(), 1); // (read by the plug-in: every one-shot render() is one rt_hip_render_tonemapped frame)
 		}
+		else if (arg == "--bloom"sv)
+		{
+			bloom = value();
+			rt_hip_bloom_params parsed{};
+			if (rt_hip_bloom_from_spec(bloom.c_str(), &parsed) != RT_HIP_OK)
+			{
+				error("--bloom expects default or KEY=VALUE items separated by ',' with the keys intensity, threshold, knee, scatter and levels (", rt_hip_last_error(), ")");
+				return 2;
+			}
+			::setenv("RT_HIP_BLOOM", bloom.c_str(), 1); // (read by the plug-in: every one-shot render() is one rt_hip_render_bloomed frame)
+		}
 		else if (arg == "--dolly"sv)
 		{
 			char trailing = 0;
@@ -302,7 +317,7 @@ int main(int argc, char** argv)
 			world = static_cast<unsigned>(std::strtoul(value(), nullptr, 10));
 		else if (arg == "--help"sv || arg == "-h"sv)
 		{
-			log("usage: rt_headless [--list] [--scene file.toml] [--renderer name] [--size WxH] [--spp N] [--bounces N] [--seed N] [--frames N] [--out file.ppm] [--progressive SAMPLES] [--denoise] [--boxes [--box-bvh]] [--temporal] [--adaptive THRESHOLD] [--upscale FACTOR] [--light KEY=R,G,B]... [--direct-light] [--tonemap CURVE[:EXPOSURE]] [--dolly DX,DY,DZ] [--shared-frame NAME --rank R --world N]");
+			log("usage: rt_headless [--list] [--scene file.toml] [--renderer name] [--size WxH] [--spp N] [--bounces N] [--seed N] [--frames N] [--out file.ppm] [--progressive SAMPLES] [--denoise] [--boxes [--box-bvh]] [--temporal] [--adaptive THRESHOLD] [--upscale FACTOR] [--light KEY=R,G,B]... [--direct-light] [--tonemap CURVE[:EXPOSURE]] [--bloom SPEC] [--dolly DX,DY,DZ] [--shared-frame NAME --rank R --world N]");
 			return 0;
 		}
 		else
@@ -341,6 +356,16 @@ int main(int argc, char** argv)
 		if (with || name.substr(0, 3) != "hip"sv || name == "hip_rasterizer"sv)
 		{
 			error("--tonemap maps one-shot frames of a hip tracer (not with --progressive, --temporal, --adaptive or --upscale, not '", desc->name, "'): refused with ", with ? with : "this renderer");
+			return 2;
+		}
+	}
+	if (!bloom.empty())
+	{
+		const char* const with = progressive ? "--progressive" : (temporal ? "--temporal" : (adaptive ? "--adaptive" : (upscale ? "--upscale" : nullptr)));
+		const std::string_view name{ desc->name };
+		if (with || name.substr(0, 3) != "hip"sv || name == "hip_rasterizer"sv)
+		{
+			error("--bloom blooms one-shot frames of a hip tracer (not with --progressive, --temporal, --adaptive or --upscale, not '", desc->name, "'): refused with ", with ? with : "this renderer");
 			return 2;
 		}
 	}

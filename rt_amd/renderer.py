@@ -19,7 +19,7 @@ import ctypes as C
 import numpy as np
 
 from . import capi
-from .capi import RtHipAdaptiveInfo, RtHipAdaptiveParams, RtHipDenoiseParams, RtHipPartition, RtHipPhases, RtHipProgress, RtHipScene, RtHipStats, RtHipTemporalInfo, RtHipTemporalParams, RtHipTonemapInfo, RtHipTonemapParams, RtHipUpsampleParams, RtHipUpscaleInfo, check
+from .capi import RtHipAdaptiveInfo, RtHipAdaptiveParams, RtHipBloomInfo, RtHipBloomParams, RtHipDenoiseParams, RtHipPartition, RtHipPhases, RtHipProgress, RtHipScene, RtHipStats, RtHipTemporalInfo, RtHipTemporalParams, RtHipTonemapInfo, RtHipTonemapParams, RtHipUpsampleParams, RtHipUpscaleInfo, check
 
 
 def local_rows(height: int, rank: int, world: int, stripe_rows: int = capi.RT_HIP_DEFAULT_STRIPE_ROWS) -> int:
@@ -102,6 +102,28 @@ def tonemap_default_params() -> RtHipTonemapParams:
     params = RtHipTonemapParams()
     check(capi.hip_lib().rt_hip_tonemap_default_params(C.byref(params)))
     return params
+
+
+def bloom_default_params() -> RtHipBloomParams:
+    """rt_hip_bloom_default_params: what a NULL `params` of the bloom entry points stands for (pure host code)."""
+    params = RtHipBloomParams()
+    check(capi.hip_lib().rt_hip_bloom_default_params(C.byref(params)))
+    return params
+
+
+def bloom_from_spec(spec: str) -> RtHipBloomParams:
+    """rt_hip_bloom_from_spec: ``default``, or the defaults with the ``KEY=VALUE`` items of the text (intensity, threshold, knee, scatter,
+    levels; separated by ','; pure host code).  Raises RtHipError with the text in the message for anything else."""
+    params = RtHipBloomParams()
+    check(capi.hip_lib().rt_hip_bloom_from_spec(spec.encode(), C.byref(params)))
+    return params
+
+
+def bloom_plan(width: int, height: int, params: RtHipBloomParams | None = None) -> dict:
+    """rt_hip_bloom_plan: the pyramid a width x height frame gets — levels, last_width, last_height, scratch_bytes (pure host code)."""
+    info = RtHipBloomInfo()
+    check(capi.hip_lib().rt_hip_bloom_plan(width, height, C.byref(params) if params is not None else None, C.byref(info)))
+    return info.as_dict()
 
 
 def tonemap_from_spec(spec: str) -> RtHipTonemapParams:
@@ -356,6 +378,23 @@ class HipRayTracer:
         """rt_hip_tonemap_device: a float frame on the DEVICE metered, exposed and mapped (`params` None: the defaults) into
         `d_rgb_out` (may be `d_rgb_in`) and / or `d_rgba8_out`; `d_state`: the caller's 8-word device record.  Asynchronous on `stream`."""
         check(self._lib.rt_hip_tonemap_device(self._ctx, width, height, d_rgb_in, C.byref(params) if params is not None else None, d_state, d_rgb_out, d_rgba8_out, stream))
+
+    # ---- bloom (DESIGN.md §3.16) -------------------------------------------------------------------------------
+    def bloom_device(self, width: int, height: int, d_rgb_in: int, params: RtHipBloomParams | None = None, d_rgb_out: int | None = None, d_layer_out: int | None = None, stream: int | None = None) -> None:
+        """rt_hip_bloom_device: a float frame on the DEVICE plus its glow (`params` None: the defaults) into `d_rgb_out` (may be
+        `d_rgb_in`) and / or the glow layer alone into `d_layer_out`.  Asynchronous on `stream`."""
+        check(self._lib.rt_hip_bloom_device(self._ctx, width, height, d_rgb_in, C.byref(params) if params is not None else None, d_rgb_out, d_layer_out, stream))
+
+    def render_bloomed(self, scene: RtHipScene, width: int, height: int, seed: int = 1, flags: int = 0, bloom_params: RtHipBloomParams | None = None, tonemap_params: RtHipTonemapParams | None = None, want_rgb: bool = False,
+                       stats: bool = True):
+        """rt_hip_render_bloomed: one frame traced, bloomed, metered and tone-mapped on the device — (rgba8 uint32[H, W], the MAPPED rgb
+        float32[H, W, 3] or None, stats dict of the traced frame, tone mapping's info dict)."""
+        stats_pod, info = RtHipStats(), RtHipTonemapInfo()
+        rgba = np.empty((height, width), dtype=np.uint32)
+        rgb = np.empty((height, width, 3), dtype=np.float32) if want_rgb else None
+        check(self._lib.rt_hip_render_bloomed(self._ctx, C.byref(scene), rgba.ctypes.data, width, height, seed, flags, C.byref(bloom_params) if bloom_params is not None else None,
+                                              C.byref(tonemap_params) if tonemap_params is not None else None, rgb.ctypes.data if rgb is not None else None, C.byref(stats_pod) if stats else None, C.byref(info)))
+        return rgba, rgb, stats_pod.as_dict() if stats else {}, info.as_dict()
 
     def render_tonemapped(self, scene: RtHipScene, width: int, height: int, seed: int = 1, flags: int = 0, params: RtHipTonemapParams | None = None, want_rgb: bool = False, stats: bool = True):
         """rt_hip_render_tonemapped: one frame traced, metered and tone-mapped on the device — (rgba8 uint32[H, W], the MAPPED rgb

@@ -26,6 +26,10 @@ extern "C"
 	__attribute__((weak)) rt_hip_status rt_hip_render_tonemapped(rt_hip_ctx* ctx, const rt_hip_scene* scene, uint32_t* pixels_rgba8888, uint32_t width, uint32_t height, uint64_t seed, uint32_t flags, const rt_hip_tonemap_params* params,
 																 float* rgb_f32, rt_hip_stats* stats, rt_hip_tonemap_info* out_info);
 	__attribute__((weak)) rt_hip_status rt_hip_tonemap_from_spec(const char* spec, rt_hip_tonemap_params* out_params);
+	// ... and after those (bloom_wanted below)
+	__attribute__((weak)) rt_hip_status rt_hip_render_bloomed(rt_hip_ctx* ctx, const rt_hip_scene* scene, uint32_t* pixels_rgba8888, uint32_t width, uint32_t height, uint64_t seed, uint32_t flags, const rt_hip_bloom_params* bloom_params,
+															  const rt_hip_tonemap_params* tonemap_params, float* rgb_f32, rt_hip_stats* stats, rt_hip_tonemap_info* out_tonemap_info);
+	__attribute__((weak)) rt_hip_status rt_hip_bloom_from_spec(const char* spec, rt_hip_bloom_params* out_params);
 }
 
 #include <algorithm>
@@ -286,6 +290,22 @@ namespace rt_hip_plugin
 		return spec;
 	}
 
+	// RT_HIP_BLOOM=default or KEY=VALUE,... (intensity, threshold, knee, scatter, levels; rt_headless --bloom) makes a one-shot render() of the
+	// two tracers ONE BLOOMED FRAME (rt_hip_render_bloomed): traced as without the variable, then the glow of what is
+	// brighter than the display added on the device, then exposed and mapped with RT_HIP_TONEMAP's curve — or, without that variable, with
+	// none:1, which is the plain square-root finish.  It is IGNORED, which is said once, for the reasons RT_HIP_TONEMAP is: a frame mode, the
+	// preview, a library that lacks the call, a text that cannot be read, a module that refuses (a renderer of several GPUs); the frames are
+	// rt_hip_render_tonemapped's then where RT_HIP_TONEMAP is on, and rt_hip_render's otherwise.  Unset or empty: off, and nothing is said.
+	inline const char* bloom_spec()
+	{
+		static const char* const spec = []
+		{
+			const char* bloom = std::getenv("RT_HIP_BLOOM");
+			return (bloom && *bloom) ? bloom : nullptr;
+		}();
+		return spec;
+	}
+
 	// The struct-of-arrays columns (soagen column accessors, src/soa.hpp), the two sampling scalars and the camera matrix as the POD
 	// the C ABI takes: pointers are borrowed for the call.  The matrix goes element-wise through m(r, c): independent of muu's storage
 	// order (accessor form: src/scene.cpp:179).  `view` is scene.camera.viewport(size of the frame) (mg_ray_tracer.cpp:180).
@@ -342,6 +362,9 @@ namespace rt_hip_plugin
 		bool upscale_unsupported = false;  // RT_HIP_UPSCALE on such a renderer, or with lights: likewise
 		bool tonemap_decided = false, tonemap_on = false; // RT_HIP_TONEMAP: looked at once; on: one-shot frames are rt_hip_render_tonemapped's
 		rt_hip_tonemap_params tonemap_params{};			  // ... with these, as rt_hip_tonemap_from_spec read them
+		bool bloom_decided = false, bloom_on = false;	  // RT_HIP_BLOOM: looked at once; on: one-shot frames are rt_hip_render_bloomed's
+		rt_hip_bloom_params bloom_params{};				  // ... with these, as rt_hip_bloom_from_spec read them
+		rt_hip_tonemap_params bloom_curve{};			  // ... and this curve: RT_HIP_TONEMAP's where that is on, none:1 otherwise
 		std::vector<std::string> light_names; // RT_HIP_LIGHTS: the material names the context's emission table was made from
 		bool lights_set = false;
 
@@ -402,6 +425,39 @@ namespace rt_hip_plugin
 			return false;
 		}
 
+		// RT_HIP_BLOOM, looked at once per renderer AFTER RT_HIP_TONEMAP was: true where its one-shot frames are to be bloomed; every reason why
+		// not is said here
+		bool bloom_wanted(uint32_t mode)
+		{
+			const char* const spec = bloom_spec();
+			if (!spec)
+				return false;
+			const char* const frame_mode = mode == RT_HIP_FLAG_PREVIEW	  ? nullptr
+										   : adaptive_threshold() >= 0.0f ? "RT_HIP_ADAPTIVE"
+										   : temporal_frames()			  ? "RT_HIP_TEMPORAL"
+										   : progressive_pass_samples()	  ? "RT_HIP_PROGRESSIVE"
+										   : upscale_factor()			  ? "RT_HIP_UPSCALE"
+																		  : nullptr;
+			if (mode == RT_HIP_FLAG_PREVIEW)
+				std::cerr << "error: hip_ray_tracer: RT_HIP_BLOOM is ignored: the preview has no float frame to bloom\n";
+			else if (frame_mode)
+				std::cerr << "error: hip_ray_tracer: RT_HIP_BLOOM is ignored: " << frame_mode << " is set, and only one-shot frames are bloomed\n";
+			else if (!rt_hip_render_bloomed || !rt_hip_bloom_from_spec || !rt_hip_tonemap_from_spec)
+				std::cerr << "error: hip_ray_tracer: RT_HIP_BLOOM is ignored: this librt_hip.so has no rt_hip_render_bloomed\n";
+			else if (rt_hip_bloom_from_spec(spec, &bloom_params) != RT_HIP_OK)
+				std::cerr << "error: hip_ray_tracer: " << rt_hip_last_error() << ": RT_HIP_BLOOM is ignored\n";
+			else if (tonemap_on)
+			{
+				bloom_curve = tonemap_params;
+				return true;
+			}
+			else if (rt_hip_tonemap_from_spec("none:1", &bloom_curve) != RT_HIP_OK) // (RT_HIP_TONEMAP unset, or ignored and said: the plain finish)
+				std::cerr << "error: hip_ray_tracer: " << rt_hip_last_error() << ": RT_HIP_BLOOM is ignored\n";
+			else
+				return true;
+			return false;
+		}
+
 		// one frame of `s` into `pixels` (width x height, never null); `names`: the scene's n_materials material names
 		void render(uint32_t mode, const rt_hip_scene& s, const std::string* names, size_t n_names, uint32_t* pixels, uint32_t width, uint32_t height) noexcept
 		{
@@ -424,6 +480,11 @@ namespace rt_hip_plugin
 			{
 				tonemap_decided = true;
 				tonemap_on = tonemap_wanted(mode);
+			}
+			if (!bloom_decided)
+			{
+				bloom_decided = true;
+				bloom_on = bloom_wanted(mode);
 			}
 
 			uint32_t lights = RT_HIP_FLAG_NONE; // (RT_HIP_LIGHTS: RT_HIP_FLAG_EMISSION, the table in place)
@@ -506,6 +567,20 @@ namespace rt_hip_plugin
 					std::cerr << "error: hip_ray_tracer: " << rt_hip_last_error() << ": RT_HIP_UPSCALE is ignored for this renderer\n";
 					upscale_unsupported = true;
 				}
+			if (bloom_on) // (one-shot frames of the two tracers only: bloom_wanted; no frame flag: the pixels come from a device buffer)
+			{
+				const rt_hip_status st = rt_hip_render_bloomed(ctx, &s, pixels, width, height, seed, accel_flags() | lights | mode, &bloom_params, &bloom_curve, nullptr, nullptr, nullptr);
+				if (st == RT_HIP_OK)
+					return;
+				if (st != RT_HIP_UNSUPPORTED)
+				{
+					std::cerr << "error: hip_ray_tracer: " << rt_hip_last_error() << "\n";
+					return;
+				}
+				// a multi-GPU or frame-group renderer: said once, and from here on every frame is the tone-mapped or the plain one (below)
+				std::cerr << "error: hip_ray_tracer: " << rt_hip_last_error() << ": RT_HIP_BLOOM is ignored for this renderer\n";
+				bloom_on = false;
+			}
 			if (tonemap_on) // (one-shot frames of the two tracers only: tonemap_wanted; no frame flag: the pixels come from a device buffer)
 			{
 				const rt_hip_status st = rt_hip_render_tonemapped(ctx, &s, pixels, width, height, seed, accel_flags() | lights | mode, &tonemap_params, nullptr, nullptr, nullptr);

@@ -15,7 +15,8 @@ Given a listing of rt_amd/csrc/bvh_build.hip instead, it lists the device builde
 they are expected to reserve no scratch at all.  A listing of rt_amd/csrc/denoise.hip lists the denoiser's kernels (guide_frame,
 atrous_pass<1 | 2 | 0>, finish_frame, mean_frame) in the same second table, under the same expectation; a listing of
 rt_amd/csrc/temporal.hip lists reproject_frame there, one of rt_amd/csrc/sky_band.hip the sky band's kernel, one of rt_amd/csrc/upsample.hip the guided
-upsampler's upsample_frame, and one of rt_amd/csrc/tonemap.hip tone mapping's luminance_histogram, exposure_from_histogram and tonemap_frame."""
+upsampler's upsample_frame, and one of rt_amd/csrc/tonemap.hip tone mapping's luminance_histogram, exposure_from_histogram and tonemap_frame, and one of rt_amd/csrc/bloom.hip bloom's bloom_prefilter, bloom_down, bloom_up and
+bloom_composite, with the LDS bytes a workgroup of each reserves."""
 import re
 import sys
 
@@ -36,7 +37,7 @@ for line in open(path):
         name = (m.group(1),)
         cur = {}
         continue
-    m = re.match(r"^_ZN6rt_hip12_GLOBAL__N_1\d+(guide_frame|finish_frame|mean_frame|atrous_pass|reproject_frame|sky_band_rows_kernel|upsample_frame|luminance_histogram|exposure_from_histogram|tonemap_frame)(?:ILi(\d)E)?E\w*:", line)
+    m = re.match(r"^_ZN6rt_hip12_GLOBAL__N_1\d+(guide_frame|finish_frame|mean_frame|atrous_pass|reproject_frame|sky_band_rows_kernel|upsample_frame|luminance_histogram|exposure_from_histogram|tonemap_frame|bloom_prefilter|bloom_down|bloom_up|bloom_composite)(?:ILi(\d)E)?E\w*:", line)
     if m:
         name = (m.group(1) + (f"<{m.group(2)}>" if m.group(2) else ""),)
         cur = {}
@@ -44,6 +45,9 @@ for line in open(path):
     if name:
         if re.match(r"^\s*scratch_(load|store)", line):
             cur["scratch_ops"] = cur.get("scratch_ops", 0) + 1
+        m = re.match(r"^; LDSByteSize: (\d+)", line)
+        if m:
+            cur["LDS"] = int(m.group(1))
         m = re.match(r"^; (NumVgprs|TotalNumSgprs|ScratchSize|Occupancy): (\d+)", line)
         if m:
             cur[m.group(1)] = int(m.group(2))
@@ -61,7 +65,7 @@ for (kernel, ns, sm, half, np_, gc), c in sorted(rows):
         flag, bad = "  <-- scratch", bad + 1
     print(f"{kernel:14s} {ns:3d} {sm:2d} {half:4d} {np_:2d} {gc:2d} {c.get('NumVgprs', -1):5d} {c.get('TotalNumSgprs', -1):5d} {c.get('ScratchSize', -1):7d} {c.get('scratch_ops', 0):4d} {c.get('Occupancy', -1):5d}{flag}")
 if builder:
-    print(f"{'builder kernel':16s} {'VGPR':>5s} {'SGPR':>5s} {'scratch':>7s} {'ops':>4s} {'waves':>5s}")
+    print(f"{'builder kernel':16s} {'VGPR':>5s} {'SGPR':>5s} {'scratch':>7s} {'ops':>4s} {'waves':>5s} {'LDS':>6s}")
     for kernel, c in builder:
-        print(f"{kernel:16s} {c.get('NumVgprs', -1):5d} {c.get('TotalNumSgprs', -1):5d} {c.get('ScratchSize', -1):7d} {c.get('scratch_ops', 0):4d} {c.get('Occupancy', -1):5d}")
+        print(f"{kernel:16s} {c.get('NumVgprs', -1):5d} {c.get('TotalNumSgprs', -1):5d} {c.get('ScratchSize', -1):7d} {c.get('scratch_ops', 0):4d} {c.get('Occupancy', -1):5d} {c.get('LDS', 0):6d}")
 sys.exit(1 if bad else 0)
