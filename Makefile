@@ -17,17 +17,17 @@ HIPFLAGS += -fvisibility=hidden
 # basic + plane 2.74 -> 2.62, tilted camera 2.80 -> 2.62 (profiles/r05/codegen_ab.txt).
 HIPFLAGS += -fno-slp-vectorize
 API_UNITS := context scene frame render frame_call passes multi group denoise temporal adaptive upsample tonemap bloom
-HIP_HDR  := rt_amd/csrc/kernels.hpp rt_amd/csrc/launch_plan.hpp rt_amd/csrc/progressive.hpp rt_amd/csrc/denoise.hpp rt_amd/csrc/denoise_rules.hpp rt_amd/csrc/temporal.hpp rt_amd/csrc/reproject_rules.hpp rt_amd/csrc/adaptive.hpp rt_amd/csrc/adaptive_rules.hpp rt_amd/csrc/upsample.hpp rt_amd/csrc/upsample_rules.hpp rt_amd/csrc/tonemap.hpp rt_amd/csrc/tonemap_rules.hpp rt_amd/csrc/bloom.hpp rt_amd/csrc/bloom_rules.hpp rt_amd/csrc/lights.hpp rt_amd/csrc/sky_band.hpp rt_amd/csrc/centre_ray.hpp rt_amd/csrc/frame_setup.hpp rt_amd/csrc/contract.hpp rt_amd/csrc/scan.hpp rt_amd/csrc/bvh_scan.hpp rt_amd/csrc/bvh.hpp rt_amd/csrc/box_bvh.hpp rt_amd/csrc/box_bvh_scan.hpp rt_amd/csrc/scan_streamed.hpp rt_amd/csrc/handover.hpp rt_amd/csrc/pixel_output.hpp rt_amd/csrc/lane_state.hpp rt_amd/csrc/queue_build.hpp rt_amd/csrc/camera_forms.hpp rt_amd/csrc/bvh_build.hpp rt_amd/csrc/bvh_build_device.hpp rt_amd/csrc/frame_group.hpp rt_amd/csrc/delivery.hpp rt_amd/csrc/internal.hpp include/rt_hip.h
+HIP_HDR  := rt_amd/csrc/kernels.hpp rt_amd/csrc/launch_plan.hpp rt_amd/csrc/progressive.hpp rt_amd/csrc/denoise.hpp rt_amd/csrc/denoise_rules.hpp rt_amd/csrc/temporal.hpp rt_amd/csrc/reproject_rules.hpp rt_amd/csrc/adaptive.hpp rt_amd/csrc/adaptive_rules.hpp rt_amd/csrc/upsample.hpp rt_amd/csrc/upsample_rules.hpp rt_amd/csrc/tonemap.hpp rt_amd/csrc/tonemap_rules.hpp rt_amd/csrc/bloom.hpp rt_amd/csrc/bloom_rules.hpp rt_amd/csrc/lights.hpp rt_amd/csrc/lens.hpp rt_amd/csrc/lens_rules.hpp rt_amd/csrc/sky_band.hpp rt_amd/csrc/centre_ray.hpp rt_amd/csrc/frame_setup.hpp rt_amd/csrc/contract.hpp rt_amd/csrc/scan.hpp rt_amd/csrc/bvh_scan.hpp rt_amd/csrc/bvh.hpp rt_amd/csrc/box_bvh.hpp rt_amd/csrc/box_bvh_scan.hpp rt_amd/csrc/scan_streamed.hpp rt_amd/csrc/handover.hpp rt_amd/csrc/pixel_output.hpp rt_amd/csrc/lane_state.hpp rt_amd/csrc/queue_build.hpp rt_amd/csrc/camera_forms.hpp rt_amd/csrc/bvh_build.hpp rt_amd/csrc/bvh_build_device.hpp rt_amd/csrc/frame_group.hpp rt_amd/csrc/delivery.hpp rt_amd/csrc/internal.hpp include/rt_hip.h
 HOST_SRC := rt_amd/host/host_capi.cpp rt_amd/host/scene.cpp rt_amd/host/toml_subset.cpp
 HOST_HDR := $(wildcard rt_amd/host/*.hpp) rt_amd/host/host_capi.h rt_amd/host/named_colours.inc include/rt_hip.h
 
-all: $(LIBDIR)/librt_hip.so $(LIBDIR)/librt_hip_kat.so $(LIBDIR)/librt_host.so rt_amd/bin/rt_headless tests/native/lbvh_reference tests/native/libbox_reference.so tests/native/libdenoise_reference.so tests/native/libreproject_reference.so tests/native/libadaptive_reference.so tests/native/liblight_reference.so tests/native/libdirect_reference.so tests/native/libupsample_reference.so tests/native/libtonemap_reference.so tests/native/libbloom_reference.so oracle
+all: $(LIBDIR)/librt_hip.so $(LIBDIR)/librt_hip_kat.so $(LIBDIR)/librt_host.so rt_amd/bin/rt_headless tests/native/lbvh_reference tests/native/libbox_reference.so tests/native/libdenoise_reference.so tests/native/libreproject_reference.so tests/native/libadaptive_reference.so tests/native/liblight_reference.so tests/native/libdirect_reference.so tests/native/libupsample_reference.so tests/native/libtonemap_reference.so tests/native/libbloom_reference.so tests/native/liblens_reference.so oracle
 
 # kernels.hip is compiled twice: the parity contract (contraction off), and RT_HIP_FLAG_FAST's arithmetic
 # (-DRT_HIP_FAST_BUILD -ffp-contract=fast: only launch_render_fast comes out of that one)
 FASTFLAGS := $(filter-out -ffp-contract=off,$(HIPFLAGS)) -ffp-contract=fast -DRT_HIP_FAST_BUILD
 OBJDIR   := build/obj$(NAME)
-HIP_OBJS := $(OBJDIR)/kernels.o $(OBJDIR)/kernels_fast.o $(API_UNITS:%=$(OBJDIR)/%.o) $(OBJDIR)/delivery.o $(OBJDIR)/bvh.o $(OBJDIR)/box_bvh.o $(OBJDIR)/bvh_build.o $(OBJDIR)/launch_plan.o $(OBJDIR)/frame_setup.o $(OBJDIR)/progressive.o $(OBJDIR)/denoise_params.o $(OBJDIR)/temporal_params.o $(OBJDIR)/adaptive_params.o $(OBJDIR)/upsample_params.o $(OBJDIR)/tonemap_params.o $(OBJDIR)/bloom_params.o $(OBJDIR)/lights.o $(OBJDIR)/sky_band.o $(OBJDIR)/sky_band_rule.o
+HIP_OBJS := $(OBJDIR)/kernels.o $(OBJDIR)/kernels_fast.o $(API_UNITS:%=$(OBJDIR)/%.o) $(OBJDIR)/delivery.o $(OBJDIR)/bvh.o $(OBJDIR)/box_bvh.o $(OBJDIR)/bvh_build.o $(OBJDIR)/launch_plan.o $(OBJDIR)/frame_setup.o $(OBJDIR)/progressive.o $(OBJDIR)/denoise_params.o $(OBJDIR)/temporal_params.o $(OBJDIR)/adaptive_params.o $(OBJDIR)/upsample_params.o $(OBJDIR)/tonemap_params.o $(OBJDIR)/bloom_params.o $(OBJDIR)/lights.o $(OBJDIR)/lens.o $(OBJDIR)/sky_band.o $(OBJDIR)/sky_band_rule.o
 
 $(OBJDIR)/kernels.o: rt_amd/csrc/kernels.hip $(HIP_HDR)
 	@mkdir -p $(OBJDIR)
@@ -104,6 +104,13 @@ $(OBJDIR)/bloom_params.o: rt_amd/csrc/bloom.cpp rt_amd/csrc/bloom.hpp rt_amd/csr
 $(OBJDIR)/lights.o: rt_amd/csrc/lights.cpp rt_amd/csrc/lights.hpp include/rt_hip.h
 	@mkdir -p $(OBJDIR)
 	$(CXX) -std=c++17 -O2 -fPIC -fvisibility=hidden -Wall -Wextra $(DEFS) -c $< -o $@
+
+# the thin lens' host-only rules (the lens' checks, rt_hip_lens_from_spec, the ten lens words of a frame): plain C++17 too, and the same source
+# is built into tests/native/liblens_reference.so, tests/native/lens_plan_dump and the program of `make sanitize-lens` on the CPU.
+# Contraction off, spelled out: the binary64 constants are defined by their order of operations
+$(OBJDIR)/lens.o: rt_amd/csrc/lens.cpp rt_amd/csrc/lens.hpp rt_amd/csrc/frame_setup.hpp rt_amd/csrc/launch_plan.hpp include/rt_hip.h
+	@mkdir -p $(OBJDIR)
+	$(CXX) -std=c++17 -O2 -fPIC -fvisibility=hidden -ffp-contract=off -Wall -Wextra $(DEFS) -c $< -o $@
 
 # the sky band's rule (sky_band_rows: how many rows from the top of a frame provably see nothing): plain C++17 too, and the same
 # source is built into tests/native/sky_band_dump and the program of `make sanitize-sky-band` on the CPU.  (sky_band.o is the band's kernel,
@@ -292,6 +299,22 @@ sanitize-bloom: tests/native/bloom_sanitize.cpp $(BLOOM_REF_SRC)
 	$(CXX) -O1 -g -std=c++17 -ffp-contract=off -fno-fast-math -fno-math-errno -mfma -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer $< tests/native/bloom_reference.cpp rt_amd/csrc/bloom.cpp -o build/bloom_sanitize
 	build/bloom_sanitize
 
+# the CPU restatement of RT_HIP_FLAG_THIN_LENS: light_reference.cpp's way — the oracle's own translation unit, only
+# render_pixel's sample loop restated — with the rules of rt_amd/csrc/lens_rules.hpp, the text the device runs, and lens.cpp and
+# frame_setup.cpp as they are; g++ alone, the oracle's strict flags; tests/lens_reference.py binds it
+LENS_REF_SRC := tests/native/lens_reference.cpp rt_amd/csrc/lens_rules.hpp rt_amd/csrc/lens.cpp rt_amd/csrc/lens.hpp rt_amd/csrc/frame_setup.cpp rt_amd/csrc/frame_setup.hpp rt_amd/csrc/launch_plan.hpp oracle/cpu_ref.cpp oracle/cpu_ref.h include/rt_hip.h
+tests/native/liblens_reference.so: $(LENS_REF_SRC)
+	$(CXX) -O2 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -fno-math-errno -mfma -Wall -Wextra -shared $< rt_amd/csrc/lens.cpp rt_amd/csrc/frame_setup.cpp -o $@ -lpthread
+
+# `make sanitize-lens`: the parser, the lens' checks and the lens words behind a main() of their own — every well-formed and malformed text
+# of tests/test_lens_host.py, truncated and oversized specs, every refused value, the words of an axis-aligned, a tilted and a 1-pixel
+# frame and of a matrix without an eye — under AddressSanitizer and UndefinedBehaviorSanitizer.  CPU only, nothing is loaded into python;
+# the binary goes to build/ and is run at once
+sanitize-lens: tests/native/lens_sanitize.cpp rt_amd/csrc/lens.cpp rt_amd/csrc/lens.hpp rt_amd/csrc/frame_setup.cpp rt_amd/csrc/frame_setup.hpp include/rt_hip.h
+	@mkdir -p build
+	$(CXX) -O1 -g -std=c++17 -ffp-contract=off -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer $< rt_amd/csrc/lens.cpp rt_amd/csrc/frame_setup.cpp -o build/lens_sanitize
+	build/lens_sanitize
+
 oracle:
 	$(MAKE) -C oracle
 
@@ -307,7 +330,7 @@ oracle/_ref/soagen_columns: tests/native/soagen_columns.cpp $(LIBDIR)/librt_hip.
 endif
 
 clean:
-	rm -f $(LIBDIR)/*.so rt_amd/bin/rt_headless tests/native/lbvh_reference tests/native/libbox_reference.so tests/native/libdenoise_reference.so tests/native/libreproject_reference.so tests/native/libadaptive_reference.so tests/native/liblight_reference.so tests/native/libdirect_reference.so tests/native/libupsample_reference.so tests/native/libtonemap_reference.so tests/native/libbloom_reference.so
+	rm -f $(LIBDIR)/*.so rt_amd/bin/rt_headless tests/native/lbvh_reference tests/native/libbox_reference.so tests/native/libdenoise_reference.so tests/native/libreproject_reference.so tests/native/libadaptive_reference.so tests/native/liblight_reference.so tests/native/libdirect_reference.so tests/native/libupsample_reference.so tests/native/libtonemap_reference.so tests/native/libbloom_reference.so tests/native/liblens_reference.so
 	$(MAKE) -C oracle clean
 
-.PHONY: all oracle clean variant sanitize-temporal sanitize-box-bvh sanitize-adaptive sanitize-lights sanitize-sky-band sanitize-upsample sanitize-tonemap sanitize-bloom sanitize-plugin
+.PHONY: all oracle clean variant sanitize-temporal sanitize-box-bvh sanitize-adaptive sanitize-lights sanitize-sky-band sanitize-upsample sanitize-tonemap sanitize-bloom sanitize-plugin sanitize-lens

@@ -322,7 +322,28 @@ enum
 	 * surfaces.  Nothing is promised about speed.  Works wherever RT_HIP_FLAG_EMISSION works; ignored with RT_HIP_FLAG_PREVIEW;
 	 * refused by name by both progressive entry points, both adaptive entry points, rt_hip_render_temporal,
 	 * rt_hip_denoise_progressive and rt_hip_guide_device.  A library older than this flag refuses the bit (unknown flag bits). */
-	RT_HIP_FLAG_DIRECT_LIGHT = 1u << 17
+	RT_HIP_FLAG_DIRECT_LIGHT = 1u << 17,
+	/* A THIN-LENS CAMERA (opt-in): depth of field.  Every sample's primary ray starts on a disk of the context's
+	 * lens (rt_hip_set_lens: aperture_radius around the eye, in the camera's plane) and passes the point where the pinhole's ray
+	 * meets the plane focus_distance along the view direction: what lies on that plane is sharp, everything else is blurred.  The
+	 * lens point takes ONE more generator step of the sample's own stream, directly after the jitter step (sample 0 draws no
+	 * jitter but does draw the lens step), mapped to the disk by a concentric map with polynomial sine and cosine — no sin, no
+	 * cos, no rejection (rt_amd/csrc/lens_rules.hpp).  The reference has no lens: the contract is this module's own, and the
+	 * PROMISE is that frame, float mean and `segments` are bit for bit those of the CPU restatement
+	 * (tests/native/lens_reference.cpp over the same header).  With aperture_radius == 0 the frame is the flag-less frame in every
+	 * respect; with an aperture it is a one-shot frame of the parity arithmetic on the resident kernel (RT_HIP_KERNEL_RESIDENT;
+	 * scenes of the scalar-register kernel's size too) or, with RT_HIP_FLAG_BVH and for scenes of the streamed kernel's size, the
+	 * hierarchy kernel (RT_HIP_KERNEL_BVH), in whole chunks, without a sky band.  Nothing is promised about speed.
+	 * Works with RT_HIP_FLAG_SM_MATERIALS, RT_HIP_FLAG_BVH, RT_HIP_FLAG_BVH_DEVICE_BUILD, RT_HIP_FLAG_STATS,
+	 * RT_HIP_FLAG_PERSISTENT_FRAME and RT_HIP_FLAG_FORCE_WHOLE_CHUNKS, in rt_hip_render, rt_hip_render_device,
+	 * rt_hip_render_tonemapped and rt_hip_render_bloomed, with a partition and on every kind of context; ignored with
+	 * RT_HIP_FLAG_PREVIEW.  Refused with RT_HIP_INVALID_ARGUMENT when no lens is set.  Refused (RT_HIP_UNSUPPORTED, the message
+	 * names the flag) for a matrix without a finite eye (a lens needs a perspective matrix), with RT_HIP_FLAG_FAST,
+	 * RT_HIP_FLAG_FORCE_TILED, _FORCE_RESIDENT, _FORCE_STREAMED, RT_HIP_FLAG_FORCE_HALF_CHUNKS, RT_HIP_FLAG_TRACE_BOXES,
+	 * RT_HIP_FLAG_BOX_BVH, RT_HIP_FLAG_EMISSION and RT_HIP_FLAG_DIRECT_LIGHT, and by both progressive entry points, both adaptive
+	 * entry points, rt_hip_render_temporal, rt_hip_render_upscaled and rt_hip_guide_device.  A library older than this flag
+	 * refuses the bit (unknown flag bits). */
+	RT_HIP_FLAG_THIN_LENS = 1u << 18
 };
 
 typedef struct rt_hip_ctx rt_hip_ctx;
@@ -1021,6 +1042,31 @@ RT_HIP_API rt_hip_status rt_hip_set_emission(rt_hip_ctx* ctx, const float* emiss
  * that is negative, NaN or infinite.  out_emission_rgb receives 3 * n_materials floats (untouched on failure).
  */
 RT_HIP_API rt_hip_status rt_hip_lights_from_spec(const char* spec, const char* const* material_names, uint32_t n_materials, float* out_emission_rgb);
+
+/* ---- a thin-lens camera (RT_HIP_FLAG_THIN_LENS): additions to ABI 6 — rt_hip_scene keeps its size --------------- */
+
+/* world units; the distance is measured along the view direction */
+typedef struct rt_hip_lens
+{
+	float aperture_radius; /* finite, >= 0; 0: frames with the flag are the flag-less frames */
+	float focus_distance;  /* finite, > 0 */
+} rt_hip_lens;
+
+/*
+ * The context's LENS, copied inside the call.  aperture_radius must be finite and >= 0, focus_distance finite and > 0: anything
+ * else is RT_HIP_INVALID_ARGUMENT, the message naming the field.  NULL clears the lens.  The lens is state of the context: it
+ * survives scene uploads, and on a context from rt_hip_create_multi it reaches every member device.  Without
+ * RT_HIP_FLAG_THIN_LENS no frame reads it.
+ */
+RT_HIP_API rt_hip_status rt_hip_set_lens(rt_hip_ctx* ctx, const rt_hip_lens* lens);
+
+/*
+ * A lens from a text: "aperture=0.05,focus=4.2" (both keys, each once, in either order; blanks around keys, numbers and
+ * separators are ignored).  Host-only; touches no device.  RT_HIP_INVALID_ARGUMENT, with a message that says why: an unknown or
+ * repeated key, a missing key, a missing '=', an empty item, anything that is not a number, and a value rt_hip_set_lens refuses.
+ * out_lens is untouched on failure.
+ */
+RT_HIP_API rt_hip_status rt_hip_lens_from_spec(const char* spec, rt_hip_lens* out_lens);
 
 /* ---- tone mapping for HDR frames: device auto-exposure, three curves --------------------------------------- */
 /*

@@ -140,6 +140,12 @@ RT_HIP_API rt_hip_status rt_hip_kat_direct_octahedral(rt_hip_ctx* ctx, uint32_t 
  * out[5 i ..] = (w.x, w.y, w.z, weight, aimed as 0 / 1). */
 RT_HIP_API rt_hip_status rt_hip_kat_direct_aim(rt_hip_ctx* ctx, uint32_t n, const uint32_t* ka, const uint32_t* kb, const float* in, const float* radius, uint32_t n_lights, float* out);
 
+/* RT_HIP_FLAG_THIN_LENS's rules (rt_amd/csrc/lens_rules.hpp) as the lens builds of the kernels compute them; must equal
+ * the same header compiled with g++ (tests/native/lens_reference.cpp) bit for bit.  ka, kb: n pairs of numerators, each below 2^24.
+ * ray[9] = the pinhole's ray (origin, normalised direction) and the eye; lens_words[10] = U, V, fwd, focus ->
+ * out[9 i ..] = (lx, ly, origin.xyz, direction.xyz, bent as 0 / 1): the disk point and the lens ray, normalised. */
+RT_HIP_API rt_hip_status rt_hip_kat_lens(rt_hip_ctx* ctx, uint32_t n, const uint32_t* ka, const uint32_t* kb, const float* ray, const float* lens_words, float* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,6 +34,7 @@ RT_HIP_FLAG_TRACE_BOXES = 1 << 13  # the traced frame hits the scene's boxes too
 RT_HIP_FLAG_BOX_BVH = 1 << 14  # with RT_HIP_FLAG_TRACE_BOXES: the boxes through a hierarchy of their own, no 256-box cap, same frame
 RT_HIP_FLAG_EMISSION = 1 << 16  # materials with a row > 0 in the context's emission table are lights; bit 15 is unassigned
 RT_HIP_FLAG_DIRECT_LIGHT = 1 << 17  # with RT_HIP_FLAG_EMISSION: lambert vertices sample the sphere lights directly
+RT_HIP_FLAG_THIN_LENS = 1 << 18  # primary rays start on the context's lens and meet on its focus plane: depth of field
 RT_HIP_TONEMAP_NONE, RT_HIP_TONEMAP_REINHARD, RT_HIP_TONEMAP_ACES = 0, 1, 2  # rt_hip_tonemap_params.curve
 RT_HIP_MULTI_PEER_COPY = 1 << 0
 RT_HIP_MULTI_DIRECT_FRAME = 1 << 1
@@ -196,6 +197,15 @@ class RtHipUpscaleInfo(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class RtHipLens(C.Structure):
+    """``rt_hip_lens`` (include/rt_hip.h): the thin lens of RT_HIP_FLAG_THIN_LENS, in world units; the distance along the view direction."""
+
+    _fields_ = [("aperture_radius", C.c_float), ("focus_distance", C.c_float)]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class RtHipTonemapParams(C.Structure):
     """``rt_hip_tonemap_params`` (include/rt_hip.h): the curve, the meter's rank window, manual or metered exposure and its limits."""
 
@@ -341,6 +351,8 @@ RT_HIP_SYMBOLS = [
     ("rt_hip_adaptive_last_info", C.c_int, [C.POINTER(RtHipAdaptiveInfo)]),
     ("rt_hip_set_emission", C.c_int, [C.c_void_p, c_float_p, C.c_uint32]),
     ("rt_hip_lights_from_spec", C.c_int, [C.c_char_p, C.POINTER(C.c_char_p), C.c_uint32, c_float_p]),
+    ("rt_hip_set_lens", C.c_int, [C.c_void_p, C.POINTER(RtHipLens)]),
+    ("rt_hip_lens_from_spec", C.c_int, [C.c_char_p, C.POINTER(RtHipLens)]),
     ("rt_hip_tonemap_default_params", C.c_int, [C.POINTER(RtHipTonemapParams)]),
     ("rt_hip_tonemap_from_spec", C.c_int, [C.c_char_p, C.POINTER(RtHipTonemapParams)]),
     ("rt_hip_tonemap_device", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(RtHipTonemapParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -371,6 +383,7 @@ RT_HIP_KAT_SYMBOLS = [
     ("rt_hip_kat_bvh_build", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rt_hip_kat_bvh_build_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rt_hip_kat_closest_hit_bvh_device", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("rt_hip_kat_lens", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rt_hip_kat_closest_hit_boxes", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rt_hip_kat_closest_hit_boxes_bvh", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rt_hip_kat_box_bvh_build", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -459,6 +459,28 @@ extern "C" rt_hip_status rt_hip_set_emission(rt_hip_ctx* ctx, const float* emiss
 	}
 }
 
+// RT_HIP_FLAG_THIN_LENS's lens (rt_hip.h): context state, copied here, on every member of a multi-GPU context.  The ten
+// words the lens builds trace from are derived per frame (render.hip: they depend on the frame's matrix and size).
+extern "C" rt_hip_status rt_hip_set_lens(rt_hip_ctx* ctx, const rt_hip_lens* lens)
+{
+	if (!ctx)
+		return fail(RT_HIP_INVALID_ARGUMENT, "rt_hip_set_lens: NULL context");
+	if (lens)
+	{
+		const lens_check values = check_lens("rt_hip_set_lens", *lens);
+		if (values.status)
+			return fail(values.status, "%s", values.message);
+	}
+	ctx->lens = lens ? *lens : rt_hip_lens{};
+	ctx->have_lens = lens != nullptr;
+	for (rt_hip_ctx* member : ctx->peers)
+	{
+		member->lens = ctx->lens;
+		member->have_lens = ctx->have_lens;
+	}
+	return ok();
+}
+
 extern "C" void rt_hip_destroy(rt_hip_ctx* ctx)
 {
 	if (!ctx)

@@ -201,7 +201,8 @@ namespace
 						{ RT_HIP_FLAG_PERSISTENT_FRAME, "RT_HIP_FLAG_PERSISTENT_FRAME" },
 						{ RT_HIP_FLAG_BOX_BVH, "RT_HIP_FLAG_BOX_BVH" }, // (the guide kernel keeps its linear scan over at most box_max_count boxes)
 						{ RT_HIP_FLAG_EMISSION, "RT_HIP_FLAG_EMISSION" }, // (the guide's albedo knows no lights: temporal frames and the guide itself)
-						{ RT_HIP_FLAG_DIRECT_LIGHT, "RT_HIP_FLAG_DIRECT_LIGHT" } }; // (its modifier)
+						{ RT_HIP_FLAG_DIRECT_LIGHT, "RT_HIP_FLAG_DIRECT_LIGHT" }, // (its modifier)
+						{ RT_HIP_FLAG_THIN_LENS, "RT_HIP_FLAG_THIN_LENS" } };	  // (the guide is the pinhole's centre ray: temporal and upscaled frames, and the guide itself)
 		for (const auto& flag : refused)
 			if (flags & flag.bit)
 				return flag.name;

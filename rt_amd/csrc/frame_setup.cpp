@@ -30,14 +30,29 @@ namespace rt_hip
 			return refuse(check, RT_HIP_INVALID_ARGUMENT, "rt_hip_render_device: empty frame %ux%u", width, height);
 		if (static_cast<uint64_t>(width) * height > 0xFFFFFFFFull)
 			return refuse(check, RT_HIP_INVALID_ARGUMENT, "rt_hip_render_device: %ux%u exceeds the 32-bit pixel index of image_view", width, height);
-		if (flags & ~static_cast<uint32_t>(RT_HIP_FLAG_FORCE_TILED | RT_HIP_FLAG_FORCE_RESIDENT | RT_HIP_FLAG_PERSISTENT_FRAME | RT_HIP_FLAG_SM_MATERIALS | RT_HIP_FLAG_PREVIEW | RT_HIP_FLAG_FORCE_STREAMED | RT_HIP_FLAG_FAST | RT_HIP_FLAG_STATS | RT_HIP_FLAG_FORCE_HALF_CHUNKS | RT_HIP_FLAG_FORCE_WHOLE_CHUNKS | RT_HIP_FLAG_BVH | RT_HIP_FLAG_BVH_DEVICE_BUILD | RT_HIP_FLAG_TRACE_BOXES | RT_HIP_FLAG_BOX_BVH | RT_HIP_FLAG_EMISSION | RT_HIP_FLAG_DIRECT_LIGHT))
+		if (flags & ~static_cast<uint32_t>(RT_HIP_FLAG_FORCE_TILED | RT_HIP_FLAG_FORCE_RESIDENT | RT_HIP_FLAG_PERSISTENT_FRAME | RT_HIP_FLAG_SM_MATERIALS | RT_HIP_FLAG_PREVIEW | RT_HIP_FLAG_FORCE_STREAMED | RT_HIP_FLAG_FAST | RT_HIP_FLAG_STATS | RT_HIP_FLAG_FORCE_HALF_CHUNKS | RT_HIP_FLAG_FORCE_WHOLE_CHUNKS | RT_HIP_FLAG_BVH | RT_HIP_FLAG_BVH_DEVICE_BUILD | RT_HIP_FLAG_TRACE_BOXES | RT_HIP_FLAG_BOX_BVH | RT_HIP_FLAG_EMISSION | RT_HIP_FLAG_DIRECT_LIGHT | RT_HIP_FLAG_THIN_LENS))
 			return refuse(check, RT_HIP_UNSUPPORTED, "rt_hip_render_device: unknown flag bits 0x%x", flags);
 		if ((flags & RT_HIP_FLAG_BVH) && (flags & (RT_HIP_FLAG_FORCE_TILED | RT_HIP_FLAG_FORCE_RESIDENT | RT_HIP_FLAG_FORCE_STREAMED)))
 			return refuse(check, RT_HIP_UNSUPPORTED, "rt_hip_render_device: RT_HIP_FLAG_BVH chooses its own kernel (not with RT_HIP_FLAG_FORCE_TILED / _RESIDENT / _STREAMED)");
 		if ((flags & RT_HIP_FLAG_BVH) && (flags & RT_HIP_FLAG_FAST))
 			return refuse(check, RT_HIP_UNSUPPORTED, "rt_hip_render_device: RT_HIP_FLAG_BVH is built for the parity contract's arithmetic only (not with RT_HIP_FLAG_FAST)");
 		if (flags & RT_HIP_FLAG_PREVIEW)
-			flags &= ~static_cast<uint32_t>(RT_HIP_FLAG_BVH | RT_HIP_FLAG_BVH_DEVICE_BUILD | RT_HIP_FLAG_TRACE_BOXES | RT_HIP_FLAG_BOX_BVH | RT_HIP_FLAG_EMISSION | RT_HIP_FLAG_DIRECT_LIGHT); // one ray per pixel: the preview keeps its own scan, which draws boxes already (and shades by albedo: it knows no lights)
+			flags &= ~static_cast<uint32_t>(RT_HIP_FLAG_BVH | RT_HIP_FLAG_BVH_DEVICE_BUILD | RT_HIP_FLAG_TRACE_BOXES | RT_HIP_FLAG_BOX_BVH | RT_HIP_FLAG_EMISSION | RT_HIP_FLAG_DIRECT_LIGHT | RT_HIP_FLAG_THIN_LENS); // one ray per pixel: the preview keeps its own scan, which draws boxes already (and shades by albedo: it knows no lights), through the pixel's centre (no lens)
+		// the lens builds exist for the parity contract's tile-per-wave whole-chunk kernels, without boxes and without lights
+		// (launch_plan.cpp): whatever the context's lens holds, the flag does not go with one that asks for another kernel
+		if (flags & RT_HIP_FLAG_THIN_LENS)
+		{
+			if (flags & RT_HIP_FLAG_FAST)
+				return refuse(check, RT_HIP_UNSUPPORTED, "rt_hip_render_device: RT_HIP_FLAG_THIN_LENS is built for the parity contract's arithmetic only (not with RT_HIP_FLAG_FAST)");
+			if (flags & (RT_HIP_FLAG_FORCE_TILED | RT_HIP_FLAG_FORCE_RESIDENT | RT_HIP_FLAG_FORCE_STREAMED))
+				return refuse(check, RT_HIP_UNSUPPORTED, "rt_hip_render_device: RT_HIP_FLAG_THIN_LENS chooses its own kernel (not with RT_HIP_FLAG_FORCE_TILED / _RESIDENT / _STREAMED)");
+			if (flags & RT_HIP_FLAG_FORCE_HALF_CHUNKS)
+				return refuse(check, RT_HIP_UNSUPPORTED, "rt_hip_render_device: RT_HIP_FLAG_THIN_LENS is built for whole chunks only (not with RT_HIP_FLAG_FORCE_HALF_CHUNKS)");
+			if (flags & (RT_HIP_FLAG_TRACE_BOXES | RT_HIP_FLAG_BOX_BVH))
+				return refuse(check, RT_HIP_UNSUPPORTED, "rt_hip_render_device: RT_HIP_FLAG_THIN_LENS has no build that traces boxes (not with RT_HIP_FLAG_TRACE_BOXES / RT_HIP_FLAG_BOX_BVH)");
+			if (flags & (RT_HIP_FLAG_EMISSION | RT_HIP_FLAG_DIRECT_LIGHT))
+				return refuse(check, RT_HIP_UNSUPPORTED, "rt_hip_render_device: RT_HIP_FLAG_THIN_LENS has no build that knows lights (not with RT_HIP_FLAG_EMISSION / RT_HIP_FLAG_DIRECT_LIGHT)");
+		}
 		// the light builds exist for the parity contract's tile-per-wave whole-chunk kernels, without boxes (launch_plan.cpp): whatever the
 		// table holds, the flag does not go with one that asks for another kernel
 		// RT_HIP_FLAG_DIRECT_LIGHT modifies RT_HIP_FLAG_EMISSION: refused without it and wherever it is refused, by its own name

@@ -40,6 +40,7 @@
 #include "progressive.hpp"
 #include "adaptive.hpp"
 #include "lights.hpp"
+#include "lens.hpp"
 #include "sky_band.hpp"
 
 #include <rccl/rccl.h>
@@ -316,7 +317,7 @@ namespace rt_hip
 	struct frame_delivery; // below: the module-owned frame and the threads that carry it to the caller's buffer
 
 	// (RT_HIP_FLAG_PERSISTENT_FRAME and RT_HIP_FLAG_STATS are rt_hip_render's own: they do not travel to the launch)
-	constexpr uint32_t render_flag_mask = RT_HIP_FLAG_FORCE_TILED | RT_HIP_FLAG_FORCE_RESIDENT | RT_HIP_FLAG_SM_MATERIALS | RT_HIP_FLAG_PREVIEW | RT_HIP_FLAG_FORCE_STREAMED | RT_HIP_FLAG_FAST | RT_HIP_FLAG_FORCE_HALF_CHUNKS | RT_HIP_FLAG_FORCE_WHOLE_CHUNKS | RT_HIP_FLAG_BVH | RT_HIP_FLAG_BVH_DEVICE_BUILD | RT_HIP_FLAG_TRACE_BOXES | RT_HIP_FLAG_BOX_BVH | RT_HIP_FLAG_EMISSION | RT_HIP_FLAG_DIRECT_LIGHT;
+	constexpr uint32_t render_flag_mask = RT_HIP_FLAG_FORCE_TILED | RT_HIP_FLAG_FORCE_RESIDENT | RT_HIP_FLAG_SM_MATERIALS | RT_HIP_FLAG_PREVIEW | RT_HIP_FLAG_FORCE_STREAMED | RT_HIP_FLAG_FAST | RT_HIP_FLAG_FORCE_HALF_CHUNKS | RT_HIP_FLAG_FORCE_WHOLE_CHUNKS | RT_HIP_FLAG_BVH | RT_HIP_FLAG_BVH_DEVICE_BUILD | RT_HIP_FLAG_TRACE_BOXES | RT_HIP_FLAG_BOX_BVH | RT_HIP_FLAG_EMISSION | RT_HIP_FLAG_DIRECT_LIGHT | RT_HIP_FLAG_THIN_LENS;
 
 }
 
@@ -415,6 +416,11 @@ struct rt_hip_ctx
 	uint32_t sampled_lights = 0; // n of the resident scene under the table (valid with the tables)
 	const uint32_t* light_scatter_direct = nullptr;
 	const uint32_t* light_scatter_sm_direct = nullptr;
+	// RT_HIP_FLAG_THIN_LENS: the lens (rt_hip_set_lens: context state, survives scene uploads).  A frame with the flag and an
+	// aperture derives its ten words from it and the frame's matrix (lens.cpp) and hands them to the lens builds in frame_params words only
+	// the homogeneous camera form reads (render.hip): no kernel argument is added or moved.
+	rt_hip_lens lens{};
+	bool have_lens = false;
 	// Opt-in (RT_HIP_FLAG_PERSISTENT_FRAME, frame groups): the CALLER's buffer, page-locked and mapped into the GPU's address
 	// space while it keeps arriving at the same address: the kernel renders straight into it.  The caller then owes the
 	// module rt_hip_forget_frame before that memory is unmapped (rt_hip.h).

@@ -16,6 +16,12 @@
 #include "bvh_build.hpp"
 #include "bvh_build_device.hpp"
 #include "direct_light_rules.hpp"
+// (RT_HIP_FLAG_THIN_LENS's rules take their leaf function from the includer, as kernels.hip hands it in)
+namespace rt_hip::lens::leaf
+{
+	__device__ __forceinline__ float divide(float a, float b) { return rt_hip::divide(a, b); }
+}
+#include "lens_rules.hpp"
 
 #include <algorithm>
 #include <vector>
@@ -278,6 +284,25 @@ namespace
 			const float* const v = in + 9u * i;
 			const direct_light::aim<vec3> a = direct_light::aim_at(ka[i], kb[i], vec3{ v[0], v[1], v[2] }, vec3{ v[3], v[4], v[5] }, vec3{ v[6], v[7], v[8] }, radius[i], n_lights, contract_inv_sqrt{});
 			out[5u * i + 0u] = a.w.x, out[5u * i + 1u] = a.w.y, out[5u * i + 2u] = a.w.z, out[5u * i + 3u] = a.weight, out[5u * i + 4u] = a.aimed ? 1.0f : 0.0f;
+		}
+	}
+
+	// RT_HIP_FLAG_THIN_LENS's rules header as the lens builds of the render kernels run it: the disk point of each pair of numerators, and the
+	// ray (in[0..2] origin, in[3..5] normalised direction, in[6..8] eye) bent through it by the lens words in[9..18], normalised as the
+	// kernels' tail normalises a new direction
+	__global__ void kat_lens(uint32_t n, const uint32_t* __restrict__ ka, const uint32_t* __restrict__ kb, const float* __restrict__ in, float* __restrict__ out)
+	{
+		const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+		if (i < n)
+		{
+			const lens::disk_point on_disk = lens::disk(ka[i], kb[i]);
+			const vec3 o = { in[0], in[1], in[2] }, d = { in[3], in[4], in[5] }, eye = { in[6], in[7], in[8] };
+			const lens::words<vec3> w = { { in[9], in[10], in[11] }, { in[12], in[13], in[14] }, { in[15], in[16], in[17] }, in[18] };
+			const lens::bent_ray<vec3> bent = lens::bend(d, eye, w, on_disk);
+			const vec3 origin = bent.bent ? bent.origin : o;
+			const vec3 dir = bent.bent ? bent.toward * inv_sqrt_rn(dot(bent.toward, bent.toward)) : d;
+			float* const r = out + 9u * i;
+			r[0] = on_disk.x, r[1] = on_disk.y, r[2] = origin.x, r[3] = origin.y, r[4] = origin.z, r[5] = dir.x, r[6] = dir.y, r[7] = dir.z, r[8] = bent.bent ? 1.0f : 0.0f;
 		}
 	}
 
@@ -826,6 +851,33 @@ extern "C" rt_hip_status rt_hip_kat_direct_aim(rt_hip_ctx* ctx, uint32_t n, cons
 	if (!in)
 		return kat_fail(RT_HIP_INVALID_ARGUMENT, "rt_hip_kat_direct_aim: invalid argument");
 	return kat_direct("rt_hip_kat_direct_aim", ctx, n, ka, kb, in, radius, n_lights, out);
+}
+
+extern "C" rt_hip_status rt_hip_kat_lens(rt_hip_ctx* ctx, uint32_t n, const uint32_t* ka, const uint32_t* kb, const float* ray, const float* lens_words, float* out)
+{
+	if (!ctx || !n || !ka || !kb || !ray || !lens_words || !out)
+		return kat_fail(RT_HIP_INVALID_ARGUMENT, "rt_hip_kat_lens: invalid argument");
+	for (uint32_t i = 0; i < n; i++)
+		if ((ka[i] | kb[i]) >> 24)
+			return kat_fail(RT_HIP_INVALID_ARGUMENT, "rt_hip_kat_lens: item %u: a numerator must be below 2^24", i);
+	RT_HIP_KAT_TRY(hipSetDevice(ctx->device));
+	const size_t words = static_cast<size_t>(n) * 4u, in_bytes = 2u * words + 19u * sizeof(float), out_bytes = static_cast<size_t>(n) * 9u * sizeof(float);
+	scratch input, output;
+	RT_HIP_KAT_TRY(input.reserve(in_bytes));
+	RT_HIP_KAT_TRY(output.reserve(out_bytes));
+	unsigned char* const host = input.host.as<unsigned char>();
+	std::memcpy(host, ka, words);
+	std::memcpy(host + words, kb, words);
+	std::memcpy(host + 2u * words, ray, 9u * sizeof(float));
+	std::memcpy(host + 2u * words + 9u * sizeof(float), lens_words, 10u * sizeof(float));
+	RT_HIP_KAT_TRY(hipMemcpy(input.device.ptr, input.host.ptr, in_bytes, hipMemcpyHostToDevice));
+	const unsigned char* const d = input.device.as<unsigned char>();
+	hipLaunchKernelGGL(kat_lens, dim3((n + block_threads - 1) / block_threads), dim3(block_threads), 0, nullptr, n, reinterpret_cast<const uint32_t*>(d), reinterpret_cast<const uint32_t*>(d + words),
+					   reinterpret_cast<const float*>(d + 2u * words), output.device.as<float>());
+	RT_HIP_KAT_TRY(hipGetLastError());
+	RT_HIP_KAT_TRY(hipMemcpy(output.host.ptr, output.device.ptr, out_bytes, hipMemcpyDeviceToHost));
+	std::memcpy(out, output.host.ptr, out_bytes);
+	return RT_HIP_OK;
 }
 
 extern "C" rt_hip_status rt_hip_kat_exhaustive_math(rt_hip_ctx* ctx, uint64_t out_mismatches[3], uint32_t out_first[3])

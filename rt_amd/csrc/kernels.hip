@@ -56,6 +56,12 @@
 #include "queue_build.hpp"
 #include "direct_light_rules.hpp"
 #include "camera_forms.hpp"
+// (RT_HIP_FLAG_THIN_LENS's rules take their leaf function from the includer: the contract's correctly rounded quotient)
+namespace rt_hip::lens::leaf
+{
+	__device__ __forceinline__ float divide(float a, float b) { return rt_hip::divide(a, b); }
+}
+#include "lens_rules.hpp"
 
 #ifdef RT_HIP_FAST_BUILD
 #define render_queue render_queue_fast
@@ -134,6 +140,7 @@ namespace rt_hip
 			using build = queue_build<SCAN, HALF, NP, GC>;
 			constexpr int NS = build::NS;
 			constexpr bool PASS = build::PASS, ADAPT = build::ADAPT, BOXES = build::BOXES, BOXTREE = build::BOXTREE, LIGHTS = build::LIGHTS, DIRECT = build::DIRECT;
+			constexpr bool LENS = build::LENS; // (RT_HIP_FLAG_THIN_LENS, DESIGN.md §3.17: the restart's second step and the lens ray)
 			constexpr bool RESIDENT = build::RESIDENT, RESIDENT_SCALAR_SCAN = build::RESIDENT_SCALAR_SCAN, BVH = build::BVH, ROLLING = build::ROLLING;
 			constexpr bool INDEXED = build::INDEXED, SCALAR_SEGMENTS = build::SCALAR_SEGMENTS;
 			constexpr uint32_t slot_floats = build::slot_floats;
@@ -1148,7 +1155,7 @@ namespace rt_hip
 									   fma(p.ray_j1[2], jx, fma(p.ray_j2[2], jy, st.base_z)) };
 							st.origin = { p.ray_eye[0] + toward.x, p.ray_eye[1] + toward.y, p.ray_eye[2] + toward.z }; // (toward = near - eye)
 						}
-						else if (EYE_ONLY || p.eye_form) // (wave-uniform)
+						else if (EYE_ONLY || LENS || p.eye_form) // (wave-uniform; a lens frame always has an eye: lens.hpp, check_lens_frame)
 						{
 							// a perspective matrix that is no pinhole's in binary32 — a camera that is not axis-aligned: rounding noise in
 							// its w row.  Every near-to-far line passes through the eye E; the near point relative to it (times N.w) and
@@ -1199,6 +1206,23 @@ namespace rt_hip
 							toward = { fma(F[0], N[3], -(N[0] * F[3])), fma(F[1], N[3], -(N[1] * F[3])), fma(F[2], N[3], -(N[2] * F[3])) };
 							if (N[3] * F[3] < 0.0f)
 								toward = { -toward.x, -toward.y, -toward.z };
+						}
+						if constexpr (LENS)
+						{
+							// the LENS STEP (§3.17; lens_rules.hpp): one more step of the sample's own stream under the restarting lanes' mask, directly
+							// behind the jitter step — sample 0, which has rewound to its window's start, draws it from there — then the primary ray
+							// just made, normalised as the tail below would have, is bent through the step's point of the lens.  The ten lens words
+							// lie in the words of p that only the homogeneous form reads (lens.hpp, put_lens_words); a lane whose ray does not meet
+							// the focus plane in front of the lens keeps the pinhole's ray, by select.
+							const uint32_t lens_word = next_step_word(st.counter, st.keys);
+							const lens::disk_point on_disk = lens::disk((lens_word * step_mul_a) >> 8, (lens_word * step_mul_b) >> 8);
+							const vec3 d = toward * inv_sqrt_rn(dot(toward, toward));
+							const bool through_pinhole = PINHOLE_ONLY || (!NEVER_PINHOLE && p.pinhole);
+							const vec3 eye = { through_pinhole ? p.ray_eye[0] : p.eye_e[0], through_pinhole ? p.ray_eye[1] : p.eye_e[1], through_pinhole ? p.ray_eye[2] : p.eye_e[2] };
+							const lens::words<vec3> lens_words = { { p.mx[0], p.mx[1], p.mx[2] }, { p.my[0], p.my[1], p.my[2] }, { p.k_near[0], p.k_near[1], p.k_near[2] }, p.mx[3] };
+							const lens::bent_ray<vec3> bent = lens::bend(d, eye, lens_words, on_disk);
+							st.origin = { bent.bent ? bent.origin.x : st.origin.x, bent.bent ? bent.origin.y : st.origin.y, bent.bent ? bent.origin.z : st.origin.z };
+							toward = { bent.bent ? bent.toward.x : toward.x, bent.bent ? bent.toward.y : toward.y, bent.bent ? bent.toward.z : toward.z };
 						}
 						toward2 = dot(toward, toward);
 						st.throughput = { 1.0f, 1.0f, 1.0f };
@@ -1431,6 +1455,8 @@ namespace rt_hip
 					return render_queue<tree ? scan_bvh_pass : scan_resident_pass, SM, false, NP, GC>;
 				if (build.direct) // (RT_HIP_FLAG_DIRECT_LIGHT with a sampled light: implies lights, never a pass; named last — the order of mention is the code object's)
 					return render_queue<tree ? scan_bvh_direct : scan_resident_direct, SM, false, NP, GC>;
+				if (build.lens) // (RT_HIP_FLAG_THIN_LENS with an aperture: never a pass, never with boxes or lights; named after every older build)
+					return render_queue<tree ? scan_bvh_lens : scan_resident_lens, SM, false, NP, GC>;
 			}
 #endif
 			if constexpr (!SM) // (the sm table keeps whole chunks: one set of kernels fewer to build)

@@ -238,9 +238,16 @@ namespace rt_hip
 		const bool lights = (request.flags & RT_HIP_FLAG_EMISSION) && request.n_lights != 0u && !pass && !boxes;
 		if (lights)
 			kernel = (kernel == RT_HIP_KERNEL_BVH || kernel == RT_HIP_KERNEL_STREAMED) ? RT_HIP_KERNEL_BVH : RT_HIP_KERNEL_RESIDENT;
+		// A lens (RT_HIP_FLAG_THIN_LENS and an aperture radius above 0 in the context's lens) is planned like lights: the lens builds are builds
+		// of the two tile-per-wave kernels, in whole chunks; scenes of the scalar-register kernels' size take the resident one, scenes of the
+		// streamed kernel's the hierarchy.  (The API refuses the flag with passes, boxes, lights and the FORCE_ flags.)  Without the flag, or
+		// with a radius of 0, nothing below differs from the frame as it always was.
+		const bool lens = (request.flags & RT_HIP_FLAG_THIN_LENS) && request.lens_aperture > 0.0f && !pass && !boxes && !lights;
+		if (lens)
+			kernel = (kernel == RT_HIP_KERNEL_BVH || kernel == RT_HIP_KERNEL_STREAMED) ? RT_HIP_KERNEL_BVH : RT_HIP_KERNEL_RESIDENT;
 		plan.variant = pixels ? kernel : static_cast<uint32_t>(RT_HIP_KERNEL_NONE);
 		const bool big_scene = plan.big_scene = kernel == RT_HIP_KERNEL_TILED || kernel == RT_HIP_KERNEL_STREAMED;
-		queue_params queue = choose_queue(pass ? request.pass_samples : request.samples_per_pixel, request.width, request.local_rows, big_scene, request.host_frame, (pass || boxes || lights) ? 0 : half_chunk_choice(request.flags),
+		queue_params queue = choose_queue(pass ? request.pass_samples : request.samples_per_pixel, request.width, request.local_rows, big_scene, request.host_frame, (pass || boxes || lights || lens) ? 0 : half_chunk_choice(request.flags),
 															 request.n_spheres + request.n_planes, kernel == RT_HIP_KERNEL_STREAMED && request.n_spheres >= sparse_launch_min_spheres);
 		// An adaptive pass: the wave's stop mask is one ballot of its tile's state words — a tile of at most 64 pixels.  choose_queue cuts
 		// 128-pixel tiles for one-chunk passes of frames beyond 6M pixels only; those are halved here (the short side first, as it would).
@@ -260,6 +267,7 @@ namespace rt_hip
 		plan.build.box_tree = box_tree;
 		plan.build.lights = lights;
 		plan.build.direct = lights && request.n_sampled_lights != 0u; // (the caller counts sampled lights under RT_HIP_FLAG_DIRECT_LIGHT only)
+		plan.build.lens = lens;
 		plan.first_chunk = pass ? request.pass_first_sample / sample_chunk : 0u;
 
 		// small scenes: one wave per tile, four tiles side by side per workgroup.  Big scenes: a persistent launch — what

@@ -132,8 +132,13 @@ namespace rt_hip
 		// the DIRECT builds of the light builds (kernel_build::direct; RT_HIP_FLAG_DIRECT_LIGHT with at least one sampled light):
 		// a lambert vertex aims a shadow segment at a sampled sphere light before it scatters — light builds in everything else
 		scan_resident_direct = -14,
-		scan_bvh_direct = -15
+		scan_bvh_direct = -15,
+		// the LENS builds of the same two scans (kernel_build::lens; RT_HIP_FLAG_THIN_LENS with an aperture): the restart draws
+		// one more generator step and bends the primary ray it has just made through a point of the lens — the same scan, whole chunks only
+		scan_resident_lens = -16,
+		scan_bvh_lens = -17
 	};
+	constexpr bool scan_has_lens(int code) { return code == scan_resident_lens || code == scan_bvh_lens; }
 	constexpr bool scan_has_direct(int code) { return code == scan_resident_direct || code == scan_bvh_direct; }
 	constexpr bool scan_has_lights(int code) { return code == scan_resident_lights || code == scan_bvh_lights || scan_has_direct(code); }
 	constexpr bool scan_is_adaptive(int code) { return code == scan_resident_adapt || code == scan_bvh_adapt; }
@@ -142,9 +147,9 @@ namespace rt_hip
 	constexpr bool scan_has_box_tree(int code) { return code == scan_bvh_boxtree; }
 	constexpr int scan_of(int code) // the scan a build's code stands for
 	{
-		return (code == scan_resident_pass || code == scan_resident_boxes || code == scan_resident_adapt || code == scan_resident_lights || code == scan_resident_direct)
+		return (code == scan_resident_pass || code == scan_resident_boxes || code == scan_resident_adapt || code == scan_resident_lights || code == scan_resident_direct || code == scan_resident_lens)
 				   ? static_cast<int>(scan_resident)
-				   : ((code == scan_bvh_pass || code == scan_bvh_boxes || code == scan_bvh_boxtree || code == scan_bvh_adapt || code == scan_bvh_lights || code == scan_bvh_direct) ? static_cast<int>(scan_bvh) : code);
+				   : ((code == scan_bvh_pass || code == scan_bvh_boxes || code == scan_bvh_boxtree || code == scan_bvh_adapt || code == scan_bvh_lights || code == scan_bvh_direct || code == scan_bvh_lens) ? static_cast<int>(scan_bvh) : code);
 	}
 	// the rolling kernels are launched persistent: as many workgroups as the device keeps resident (launch_cache, kernels.hpp)
 	constexpr bool scan_is_persistent(int scan) { return scan == scan_tiled || scan == scan_streamed || scan == scan_streamed_dense; }
@@ -185,6 +190,10 @@ namespace rt_hip
 		// RT_HIP_FLAG_DIRECT_LIGHT: how many SAMPLED lights the resident scene has under that table.  With none the frame is
 		// planned as the RT_HIP_FLAG_EMISSION frame, field for field — the plan looks at this count, not at the flag.
 		uint32_t n_sampled_lights = 0;
+		// RT_HIP_FLAG_THIN_LENS: the aperture radius of the context's lens.  Without the flag, or with a radius of 0, a frame is
+		// planned as it always was, field for field — the plan looks at the radius, not at the flag alone; with an aperture it is planned
+		// like a light frame, onto the lens builds of the two tile-per-wave kernels.
+		float lens_aperture = 0.0f;
 	// LDS bytes a workgroup of the device may ask for (the context reads it off the device's properties); 0: workgroup_lds_bytes.  A plan
 	// of a tile-per-wave kernel whose tables and chunk sums need more is refused, whatever the build: only the hierarchy kernel's — 24 KiB
 	// of stacks in front of the slots — can, from 3409 samples (a frame's, or a pass's) at a limit of 64 KiB.
@@ -206,6 +215,7 @@ namespace rt_hip
 		bool adaptive;		  // an adaptive pass: the scan's ADAPT build (scan_resident_adapt / scan_bvh_adapt; implies `pass`)
 		bool lights;		  // RT_HIP_FLAG_EMISSION with at least one light: the scan's LIGHT build (scan_resident_lights / scan_bvh_lights)
 		bool direct;		  // ... and at least one sampled light (RT_HIP_FLAG_DIRECT_LIGHT): its DIRECT build (scan_resident_direct / scan_bvh_direct; `lights` is set too)
+		bool lens;			  // RT_HIP_FLAG_THIN_LENS with an aperture: the scan's LENS build (scan_resident_lens / scan_bvh_lens)
 	};
 
 	struct launch_plan

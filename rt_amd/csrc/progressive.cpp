@@ -31,7 +31,8 @@ namespace rt_hip
 						{ RT_HIP_FLAG_BOX_BVH, "RT_HIP_FLAG_BOX_BVH" }, // (named first: it modifies the flag below)
 						{ RT_HIP_FLAG_TRACE_BOXES, "RT_HIP_FLAG_TRACE_BOXES" }, // (the box builds have no pass build)
 						{ RT_HIP_FLAG_EMISSION, "RT_HIP_FLAG_EMISSION" },		  // (nor have the light builds: progressive and adaptive passes)
-						{ RT_HIP_FLAG_DIRECT_LIGHT, "RT_HIP_FLAG_DIRECT_LIGHT" } }; // (its modifier, DESIGN.md §3.13: by name, not as an unknown bit)
+						{ RT_HIP_FLAG_DIRECT_LIGHT, "RT_HIP_FLAG_DIRECT_LIGHT" }, // (its modifier, DESIGN.md §3.13: by name, not as an unknown bit)
+						{ RT_HIP_FLAG_THIN_LENS, "RT_HIP_FLAG_THIN_LENS" } };	  // (nor have the lens builds)
 		for (const auto& flag : refused)
 			if (flags & flag.bit)
 				return flag.name;

@@ -35,6 +35,7 @@ namespace rt_hip
 	// waves per SIMD a build is compiled for (the RT_HIP_WAVES_* above)
 	// (direct: a direct build of RT_HIP_FLAG_DIRECT_LIGHT, which carries the sample's direct sum, the pending contribution, the aimed sphere and
 	// the vertex's normal across the shadow query — about ten more live registers than its light build: a case of its own, one wave fewer)
+	// (a lens build of RT_HIP_FLAG_THIN_LENS keeps its scan's count: at 7 and at 5 waves its restart spills nothing, profiles/r33/kernel_registers_lens.txt)
 	constexpr int waves_per_simd(int NS, int NP, bool direct = false)
 	{
 		if (direct)
@@ -176,7 +177,16 @@ namespace rt_hip
 		// no argument is added or moved, no LDS is taken; every other instantiation keeps its symbol and its instructions.
 		static constexpr bool DIRECT = scan_has_direct(SCAN);
 
+		// LENS (RT_HIP_FLAG_THIN_LENS; scan_resident_lens, scan_bvh_lens; the same two kernels, whole chunks only): a restarting
+		// lane takes a SECOND generator step under the restarting lanes' mask — the lens step, directly behind the jitter step; sample 0 draws
+		// it from the window's start — maps its two numerators to a point of the unit disk and bends the primary ray it has just made through
+		// that point of the lens (lens_rules.hpp).  The ten lens words travel in the frame_params words only the homogeneous camera form reads
+		// (mx, my, k_near: lens.hpp, put_lens_words) — a lens frame never takes that form, and these builds do not compile it: no argument is
+		// added or moved, every other instantiation keeps its symbol and its instructions.
+		static constexpr bool LENS = scan_has_lens(SCAN);
+
 		static_assert(!PASS || !HALF, "passes are built for whole chunks only");
+		static_assert(!LENS || (!HALF && scan_of(SCAN) <= 0), "the lens builds are built for whole chunks of the tile-per-wave table kernels only");
 		static_assert(!BOXES || !HALF, "the box builds are built for whole chunks only");
 		static_assert(!LIGHTS || (!HALF && scan_of(SCAN) <= 0), "the light builds are built for whole chunks of the tile-per-wave table kernels only");
 	};

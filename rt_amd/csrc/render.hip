@@ -109,7 +109,17 @@ rt_hip_status render_device(rt_hip_ctx* ctx, uint32_t width, uint32_t height, ui
 	wanted.samples_per_pixel = pass ? pass->first_sample + pass->n_samples : ctx->samples_per_pixel, wanted.max_bounces = ctx->max_bounces;
 	wanted.seed = seed, wanted.whole_frame_buffers = whole_frame_buffers;
 	std::copy(ctx->inverse_view_projection, ctx->inverse_view_projection + 16, wanted.inverse_view_projection);
-	const frame_params f = make_frame_params(wanted);
+	frame_params f = make_frame_params(wanted);
+	// RT_HIP_FLAG_THIN_LENS: the frame is checked against the context's lens and its own camera before anything is enqueued (the preview has
+	// dropped the flag).  With an aperture of 0 the frame is the flag-less frame in every respect: the flag ends here.
+	if (flags & RT_HIP_FLAG_THIN_LENS)
+	{
+		const lens_check lens = check_lens_frame("rt_hip_render_device", ctx->have_lens, f);
+		if (lens.status)
+			return fail(lens.status, "%s", lens.message);
+		if (!(ctx->lens.aperture_radius > 0.0f))
+			flags &= ~static_cast<uint32_t>(RT_HIP_FLAG_THIN_LENS);
+	}
 
 	// every decision of the launch is made here, once: the buffers below are prepared from the plan the launch code then follows
 	launch_plan plan{}; // (the preview: nothing to plan)
@@ -135,6 +145,7 @@ rt_hip_status render_device(rt_hip_ctx* ctx, uint32_t width, uint32_t height, ui
 			RT_HIP_TRY(hipSetDevice(ctx->device));
 			request.n_sampled_lights = ctx->sampled_lights;
 		}
+		request.lens_aperture = (flags & RT_HIP_FLAG_THIN_LENS) ? ctx->lens.aperture_radius : 0.0f;
 		request.lds_limit = ctx->workgroup_lds_bytes;
 		plan = plan_launch(request);
 		// the refusals of the plan come before anything is enqueued — the hierarchy's build included
@@ -195,7 +206,10 @@ rt_hip_status render_device(rt_hip_ctx* ctx, uint32_t width, uint32_t height, ui
 		// is asked once per (scene, camera, size, flags): an unmoved camera's further frames pay a comparison.  Only the two callers that
 		// render one whole frame in one launch offer a band (`sky_band`), and never for a pass: a pass build reads its first chunk where
 		// the other tile-per-wave builds read the band's height, and its accumulator is no business of the band's kernel.
-		if (ctx->sky_band_enabled && sky_band && !pass)
+		// (A lens frame never takes the band: the band's proof is about rays that leave the eye.)
+		if (plan.build.lens)
+			put_lens_words(f, make_lens_words(f, ctx->inverse_view_projection, ctx->lens)); // (the ten words, where only the homogeneous form reads)
+		if (ctx->sky_band_enabled && sky_band && !pass && !plan.build.lens)
 		{
 			frame_params asked = f;
 			asked.frame_key_a = asked.frame_key_b = 0u; // (the seed does not move a ray)

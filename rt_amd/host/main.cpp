@@ -46,6 +46,10 @@
 //                           the renderer as RT_HIP_BLOOM: rt_hip_render_bloomed): SPEC is default, or KEY=VALUE items separated
 //                           by ',' with the keys intensity, threshold, knee, scatter and levels.  With --tonemap that curve follows; alone the
 //                           finish is none:1, the plain square root.  Refused where --tonemap is
+//   --lens aperture=A,focus=F   every frame is taken through a thin lens of radius A that is sharp at distance F along the view direction
+//                           (exported to the renderer as RT_HIP_LENS: rt_hip_set_lens and RT_HIP_FLAG_THIN_LENS).  One-shot
+//                           frames of a hip renderer only: not with --progressive, --adaptive, --temporal, --denoise, --upscale, --boxes or
+//                           --light; it composes with --tonemap and --bloom
 //   --dolly DX,DY,DZ        the camera moves by that much in world space before every frame after the first (camera::pose)
 //   --shared-frame NAME --rank R --world N   this process is rank R of N rt_headless processes that render ONE frame
 //                together (one per GPU: RT_HIP_DEVICE picks this one's): the back buffer is every process's mapping of the
@@ -159,7 +163,7 @@ namespace
 
 int main(int argc, char** argv)
 {
-	std::string scene_path, renderer_name, out_path, shared_name, lights, tonemap, bloom;
+	std::string scene_path, renderer_name, out_path, shared_name, lights, tonemap, bloom, lens;
 	bool direct_light = false;
 	unsigned width = 800, height = 600, spp = 0, bounces = 0, frames = 1, rank = 0, world = 1, progressive = 0;
 	bool frames_given = false;
@@ -288,6 +292,17 @@ int main(int argc, char** argv)
 			}
 			::setenv("RT_HIP_TONEMAP", tonemap.c_str(), 1); // (read by the plug-in: every one-shot render() is one rt_hip_render_tonemapped frame)
 		}
+		else if (arg == "--lens"sv)
+		{
+			lens = value();
+			rt_hip_lens parsed{};
+			if (rt_hip_lens_from_spec(lens.c_str(), &parsed) != RT_HIP_OK)
+			{
+				error("--lens expects aperture=A,focus=F with A >= 0 and F > 0 (", rt_hip_last_error(), ")");
+				return 2;
+			}
+			::setenv("RT_HIP_LENS", lens.c_str(), 1); // (read by the plug-in: rt_hip_set_lens, and RT_HIP_FLAG_THIN_LENS on every one-shot render())
+		}
 		else if (arg == "--bloom"sv)
 		{
 			bloom = value();
@@ -317,7 +332,7 @@ int main(int argc, char** argv)
 			world = static_cast<unsigned>(std::strtoul(value(), nullptr, 10));
 		else if (arg == "--help"sv || arg == "-h"sv)
 		{
-			log("usage: rt_headless [--list] [--scene file.toml] [--renderer name] [--size WxH] [--spp N] [--bounces N] [--seed N] [--frames N] [--out file.ppm] [--progressive SAMPLES] [--denoise] [--boxes [--box-bvh]] [--temporal] [--adaptive THRESHOLD] [--upscale FACTOR] [--light KEY=R,G,B]... [--direct-light] [--tonemap CURVE[:EXPOSURE]] [--bloom SPEC] [--dolly DX,DY,DZ] [--shared-frame NAME --rank R --world N]");
+			log("usage: rt_headless [--list] [--scene file.toml] [--renderer name] [--size WxH] [--spp N] [--bounces N] [--seed N] [--frames N] [--out file.ppm] [--progressive SAMPLES] [--denoise] [--boxes [--box-bvh]] [--temporal] [--adaptive THRESHOLD] [--upscale FACTOR] [--light KEY=R,G,B]... [--direct-light] [--tonemap CURVE[:EXPOSURE]] [--bloom SPEC] [--lens aperture=A,focus=F] [--dolly DX,DY,DZ] [--shared-frame NAME --rank R --world N]");
 			return 0;
 		}
 		else
@@ -387,6 +402,11 @@ int main(int argc, char** argv)
 	if (!lights.empty() && (progressive || adaptive || temporal || denoise || boxes || std::string_view{ desc->name }.substr(0, 3) != "hip"sv))
 	{
 		error("--light makes materials lights in one-shot frames of a hip renderer (not with --progressive, --adaptive, --temporal, --denoise or --boxes, not '", desc->name, "')");
+		return 2;
+	}
+	if (!lens.empty() && (progressive || adaptive || temporal || denoise || upscale || boxes || !lights.empty() || std::string_view{ desc->name }.substr(0, 3) != "hip"sv))
+	{
+		error("--lens takes one-shot frames of a hip renderer through a thin lens (not with --progressive, --adaptive, --temporal, --denoise, --upscale, --boxes or --light, not '", desc->name, "')");
 		return 2;
 	}
 	if (direct_light && lights.empty())

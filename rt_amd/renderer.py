@@ -155,6 +155,13 @@ def adaptive_default_params() -> RtHipAdaptiveParams:
     return params
 
 
+def lens_from_spec(spec: str) -> capi.RtHipLens:
+    """rt_hip_lens_from_spec: a lens from ``aperture=A,focus=F`` (pure host code).  Raises RtHipError for a malformed spec."""
+    lens = capi.RtHipLens()
+    check(capi.hip_lib().rt_hip_lens_from_spec(spec.encode(), C.byref(lens)))
+    return lens
+
+
 def lights_from_spec(spec: str, material_names=None, n_materials: int | None = None) -> np.ndarray:
     """rt_hip_lights_from_spec: an emission table float32[n_materials, 3] from ``KEY=R,G,B;KEY=V;...`` (pure host code).  An
     all-digit KEY is a material index, any other a material name (every material of that name).  Raises RtHipError with the item
@@ -254,6 +261,15 @@ class HipRayTracer:
             return
         table = np.ascontiguousarray(emission, dtype=np.float32).reshape(-1, 3)
         check(self._lib.rt_hip_set_emission(self._ctx, table.ctypes.data_as(capi.c_float_p), len(table)))
+
+    def set_lens(self, aperture_radius: float | None = None, focus_distance: float = 1.0) -> None:
+        """rt_hip_set_lens: the context's thin lens (None clears it).  Frames rendered with RT_HIP_FLAG_THIN_LENS start their primary
+        rays on a disk of that radius around the eye and are sharp on the plane `focus_distance` along the view direction
+        (DESIGN.md §3.17); the lens is copied, survives scene uploads and reaches every member device."""
+        if aperture_radius is None:
+            check(self._lib.rt_hip_set_lens(self._ctx, None))
+            return
+        check(self._lib.rt_hip_set_lens(self._ctx, C.byref(capi.RtHipLens(aperture_radius, focus_distance))))
 
     # ---- drop-in ------------------------------------------------------------------------------------------
     def render(self, scene: RtHipScene, width: int, height: int, seed: int = 1, flags: int = 0, want_rgb: bool = False, out: np.ndarray | None = None, stats: bool = True):
@@ -585,6 +601,17 @@ class HipRayTracer:
         radius = np.ascontiguousarray(radius, dtype=np.float32)
         out = np.empty((ka.size, 5), dtype=np.float32)
         capi.check_kat(capi.kat_lib().rt_hip_kat_direct_aim(self._ctx, ka.size, ka.ctypes.data, kb.ctypes.data, vectors.ctypes.data, radius.ctypes.data, n_lights, out.ctypes.data))
+        return out
+
+    def kat_lens(self, ka: np.ndarray, kb: np.ndarray, ray: np.ndarray, lens_words: np.ndarray) -> np.ndarray:
+        """rt_amd/csrc/lens_rules.hpp on the device, as the lens builds run it: ray float32[9] = (origin, normalised direction, eye),
+        lens_words float32[10] = (U, V, fwd, focus) -> float32[n, 9] = (lx, ly, origin, direction, bent)."""
+        ka = np.ascontiguousarray(ka, dtype=np.uint32)
+        kb = np.ascontiguousarray(kb, dtype=np.uint32)
+        ray = np.ascontiguousarray(ray, dtype=np.float32).reshape(9)
+        lens_words = np.ascontiguousarray(lens_words, dtype=np.float32).reshape(10)
+        out = np.empty((ka.size, 9), dtype=np.float32)
+        capi.check_kat(capi.kat_lib().rt_hip_kat_lens(self._ctx, ka.size, ka.ctypes.data, kb.ctypes.data, ray.ctypes.data, lens_words.ctypes.data, out.ctypes.data))
         return out
 
     def kat_exhaustive_math(self):

@@ -30,6 +30,9 @@ extern "C"
 	__attribute__((weak)) rt_hip_status rt_hip_render_bloomed(rt_hip_ctx* ctx, const rt_hip_scene* scene, uint32_t* pixels_rgba8888, uint32_t width, uint32_t height, uint64_t seed, uint32_t flags, const rt_hip_bloom_params* bloom_params,
 															  const rt_hip_tonemap_params* tonemap_params, float* rgb_f32, rt_hip_stats* stats, rt_hip_tonemap_info* out_tonemap_info);
 	__attribute__((weak)) rt_hip_status rt_hip_bloom_from_spec(const char* spec, rt_hip_bloom_params* out_params);
+	// ... and after those (lens_wanted below)
+	__attribute__((weak)) rt_hip_status rt_hip_set_lens(rt_hip_ctx* ctx, const rt_hip_lens* lens);
+	__attribute__((weak)) rt_hip_status rt_hip_lens_from_spec(const char* spec, rt_hip_lens* out_lens);
 }
 
 #include <algorithm>
@@ -306,6 +309,22 @@ namespace rt_hip_plugin
 		return spec;
 	}
 
+	// RT_HIP_LENS=aperture=A,focus=F (rt_headless --lens) gives the one-shot frames of the two tracers a THIN LENS (RT_HIP_FLAG_THIN_LENS,
+	// DESIGN.md §3.17): the text is read once (rt_hip_lens_from_spec), the lens handed to the context (rt_hip_set_lens) and the flag added to
+	// rt_hip_render, rt_hip_render_tonemapped and rt_hip_render_bloomed.  It is IGNORED, which is said once, where a frame mode
+	// (RT_HIP_ADAPTIVE, RT_HIP_TEMPORAL, RT_HIP_PROGRESSIVE, RT_HIP_UPSCALE) or RT_HIP_LIGHTS is set, where the library lacks the calls, where
+	// the text cannot be read and where the module refuses the lens: the frames are the pinhole's then.  The preview ignores it without a
+	// word (it is one ray through the pixel's centre).  Unset or empty: off, and nothing is said.
+	inline const char* lens_spec()
+	{
+		static const char* const spec = []
+		{
+			const char* lens = std::getenv("RT_HIP_LENS");
+			return (lens && *lens) ? lens : nullptr;
+		}();
+		return spec;
+	}
+
 	// The struct-of-arrays columns (soagen column accessors, src/soa.hpp), the two sampling scalars and the camera matrix as the POD
 	// the C ABI takes: pointers are borrowed for the call.  The matrix goes element-wise through m(r, c): independent of muu's storage
 	// order (accessor form: src/scene.cpp:179).  `view` is scene.camera.viewport(size of the frame) (mg_ray_tracer.cpp:180).
@@ -365,6 +384,7 @@ namespace rt_hip_plugin
 		bool bloom_decided = false, bloom_on = false;	  // RT_HIP_BLOOM: looked at once; on: one-shot frames are rt_hip_render_bloomed's
 		rt_hip_bloom_params bloom_params{};				  // ... with these, as rt_hip_bloom_from_spec read them
 		rt_hip_tonemap_params bloom_curve{};			  // ... and this curve: RT_HIP_TONEMAP's where that is on, none:1 otherwise
+		bool lens_decided = false, lens_on = false;		  // RT_HIP_LENS: looked at once; on: the context holds the lens and one-shot frames carry RT_HIP_FLAG_THIN_LENS
 		std::vector<std::string> light_names; // RT_HIP_LIGHTS: the material names the context's emission table was made from
 		bool lights_set = false;
 
@@ -458,6 +478,31 @@ namespace rt_hip_plugin
 			return false;
 		}
 
+		// RT_HIP_LENS, looked at once per renderer (the context exists): true where its one-shot frames carry the lens, which the context then
+		// holds; every reason why not is said here
+		bool lens_wanted(uint32_t mode)
+		{
+			const char* const spec = lens_spec();
+			if (!spec || mode == RT_HIP_FLAG_PREVIEW)
+				return false;
+			const char* const other = adaptive_threshold() >= 0.0f ? "RT_HIP_ADAPTIVE"
+									  : temporal_frames()		   ? "RT_HIP_TEMPORAL"
+									  : progressive_pass_samples() ? "RT_HIP_PROGRESSIVE"
+									  : upscale_factor()		   ? "RT_HIP_UPSCALE"
+									  : lights_spec()			   ? "RT_HIP_LIGHTS"
+																   : nullptr;
+			rt_hip_lens lens{};
+			if (other)
+				std::cerr << "error: hip_ray_tracer: RT_HIP_LENS is ignored: " << other << " is set, and only one-shot frames without lights are taken through a lens\n";
+			else if (!rt_hip_set_lens || !rt_hip_lens_from_spec)
+				std::cerr << "error: hip_ray_tracer: RT_HIP_LENS is ignored: this librt_hip.so has no rt_hip_set_lens\n";
+			else if (rt_hip_lens_from_spec(spec, &lens) != RT_HIP_OK || rt_hip_set_lens(ctx, &lens) != RT_HIP_OK)
+				std::cerr << "error: hip_ray_tracer: " << rt_hip_last_error() << ": RT_HIP_LENS is ignored\n";
+			else
+				return true;
+			return false;
+		}
+
 		// one frame of `s` into `pixels` (width x height, never null); `names`: the scene's n_materials material names
 		void render(uint32_t mode, const rt_hip_scene& s, const std::string* names, size_t n_names, uint32_t* pixels, uint32_t width, uint32_t height) noexcept
 		{
@@ -487,9 +532,17 @@ namespace rt_hip_plugin
 				bloom_on = bloom_wanted(mode);
 			}
 
+			if (!lens_decided)
+			{
+				lens_decided = true;
+				lens_on = lens_wanted(mode);
+			}
+
 			uint32_t lights = RT_HIP_FLAG_NONE; // (RT_HIP_LIGHTS: RT_HIP_FLAG_EMISSION, the table in place)
 			if (!light_flags(mode, names, n_names, lights))
 				return;
+			// (RT_HIP_LENS: one-shot frames only — lens_wanted has said no wherever a frame mode or lights are set — and the preview drops it)
+			const uint32_t lens = lens_on ? static_cast<uint32_t>(RT_HIP_FLAG_THIN_LENS) : static_cast<uint32_t>(RT_HIP_FLAG_NONE);
 
 			if (mode != RT_HIP_FLAG_PREVIEW)
 				if (const float threshold = adaptive_threshold(); threshold >= 0.0f && !adaptive_unsupported)
@@ -569,7 +622,7 @@ namespace rt_hip_plugin
 				}
 			if (bloom_on) // (one-shot frames of the two tracers only: bloom_wanted; no frame flag: the pixels come from a device buffer)
 			{
-				const rt_hip_status st = rt_hip_render_bloomed(ctx, &s, pixels, width, height, seed, accel_flags() | lights | mode, &bloom_params, &bloom_curve, nullptr, nullptr, nullptr);
+				const rt_hip_status st = rt_hip_render_bloomed(ctx, &s, pixels, width, height, seed, accel_flags() | lights | lens | mode, &bloom_params, &bloom_curve, nullptr, nullptr, nullptr);
 				if (st == RT_HIP_OK)
 					return;
 				if (st != RT_HIP_UNSUPPORTED)
@@ -583,7 +636,7 @@ namespace rt_hip_plugin
 			}
 			if (tonemap_on) // (one-shot frames of the two tracers only: tonemap_wanted; no frame flag: the pixels come from a device buffer)
 			{
-				const rt_hip_status st = rt_hip_render_tonemapped(ctx, &s, pixels, width, height, seed, accel_flags() | lights | mode, &tonemap_params, nullptr, nullptr, nullptr);
+				const rt_hip_status st = rt_hip_render_tonemapped(ctx, &s, pixels, width, height, seed, accel_flags() | lights | lens | mode, &tonemap_params, nullptr, nullptr, nullptr);
 				if (st == RT_HIP_OK)
 					return;
 				if (st != RT_HIP_UNSUPPORTED)
@@ -595,7 +648,7 @@ namespace rt_hip_plugin
 				std::cerr << "error: hip_ray_tracer: " << rt_hip_last_error() << ": RT_HIP_TONEMAP is ignored for this renderer\n";
 				tonemap_on = false;
 			}
-			if (rt_hip_render(ctx, &s, pixels, width, height, seed, frame_flags() | accel_flags() | lights | mode, nullptr, nullptr) != RT_HIP_OK)
+			if (rt_hip_render(ctx, &s, pixels, width, height, seed, frame_flags() | accel_flags() | lights | lens | mode, nullptr, nullptr) != RT_HIP_OK)
 				std::cerr << "error: hip_ray_tracer: " << rt_hip_last_error() << "\n";
 		}
 	};
